@@ -2,7 +2,22 @@
 """Benchmark of the G+D training step on N MI355X.  Headline: images/sec of StyleGAN2-ADA at 256x256, bf16.
 
     python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--workload sg2ada|ffhq_sg2|sg2attent|big_gan]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps, writes the outputs (--dump-outputs) and prints the result line: nothing else.
+--full adds what the headline figure does not need: the launch log of the timed region (`roofline`, `target_kernel`,
+`kernel_ms_per_step`, ...), the reference recipe's precision split on the headline workload (`secondary`, unless --no-secondary),
+the CPU baseline (unless --no-cpu-baseline) and, with N > 1, the gradient-exchange figures (`comm`).  --launch-log and
+--kernel-breakdown switch the launch log on by themselves.
+
+--dump-outputs DIR: after the timed steps, the gradients the last one computed, as DIR/grad_<module>.npy, float32.  train_iteration
+returns nothing: each phase leaves its network's gradient in the flat buckets of that network's gradient reducers
+(StepEngine.dp_modules: G_mapping, G_synthesis and D for the StyleGAN2 workloads; G and D for BigGAN), and Adam then updates the weights
+in place.  Each file holds one reducer's buckets, concatenated.  After the last timed step that is the gradient of the step's last phase
+that trained the network, after all-reduce and nan_to_num, as Adam applied it.  A file of more than DUMP_MAX_ELEMS values is written as
+a fixed, seeded sample of its positions.  Inputs (weights, latents, reals, noise) are seeded, so the same arguments
+give the same inputs in every run.
 
 A "step" is one iteration of the reference's training loop body (train_parts/trainers.py:711-765) on synthetic inputs: every phase
 that is due (Gmain / Dmain each iteration, lazy regularisers every `interval`-th), each phase = zero_grad -> accumulation rounds of
@@ -24,10 +39,10 @@ place of fp16, applied to more blocks than its default num_fp16_res = 4); BigGAN
 config's value and each rank takes batch // N of it in rounds of min(batch_gpu, batch // N) -- the reference's own partitioning
 (trainers.py:524,737).
 
-Prints ONE JSON line on rank 0 (README / DESIGN.md explain the fields).  `roofline` is measured live: the library brackets every kernel
-launch of the timed region with hipEvents on the launch stream (sbg_prof_*), and the dominant kernel kind's algorithmic flops / summed
-duration is reported against the dense bf16 MFMA peak.  `cpu_baseline` times the CPU oracle (oracle/, the fixture-pinned restatement of
-the reference's eager CPU path) on a bounded sample of the same workload.
+Prints ONE JSON line on rank 0 (README / DESIGN.md explain the fields).  With --full, `roofline` is measured live: the library brackets
+every kernel launch of the timed region with hipEvents on the launch stream (sbg_prof_*), and the dominant kernel kind's algorithmic
+flops / summed duration is reported against the dense bf16 MFMA peak.  `cpu_baseline` (--full) times the CPU oracle (oracle/, the
+fixture-pinned restatement of the reference's eager CPU path) on a bounded sample of the same workload.
 """
 import argparse
 import json
@@ -45,6 +60,7 @@ HBM_PEAK_GBS = 8000.0
 
 RES, Z_DIM, BATCH, BATCH_GPU = 256, 512, 64, 32
 ADAM = dict(lr=0.0025, betas=[0, 0.99], eps=1e-8)
+DUMP_MAX_ELEMS = 4 << 20            # values per file in --dump-outputs: 3 gradient reducers x 16 MiB of float32 at most
 
 
 def _bf16_blocks(res):
@@ -124,6 +140,18 @@ def summarize_kernels(records):
         k = out.setdefault(r['kind'], dict(launches=0, ms=0.0, flops=0.0, bytes=0.0))
         k['launches'] += 1; k['ms'] += r['ms']; k['flops'] += r['flops']; k['bytes'] += r['bytes']
     return out
+
+
+def dump_outputs(eng, out_dir):
+    """--dump-outputs: the gradients of the last step -> out_dir/grad_<module>.npy (float32, see the module docstring)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, reducer in eng.dp_modules.items():
+        flat = torch.cat([b.flat.detach().reshape(-1).float() for b in reducer._buckets])
+        if flat.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(flat.numel(), DUMP_MAX_ELEMS, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        np.save(os.path.join(out_dir, f'grad_{name}.npy'), flat.cpu().numpy())
 
 
 # kernel kind of the launch log -> kernel names in the rocprofv3 traces
@@ -324,11 +352,15 @@ def init_ranks(args):
 def measure(args, device, world, rank, name, *, res=None, nfp=None, scaling='weak', steps=None, warmup=None, ada=None, batch_arg=None,
             batch_gpu_arg=None, headline=True):
     """Build the workload's engine, run `warmup` untimed and `steps` timed steps (barrier + synchronize on both sides, MAX over ranks) and
-    return the result record (rank 0: everything; other ranks: None)."""
+    return the result record (rank 0: everything; other ranks: None).  The launch log and the gradient-exchange figures are collected
+    only with --full (the launch log also with --launch-log / --kernel-breakdown)."""
     from style_big_gan_amd import _lib
     wl = workload(name, res, nfp)
     res = wl['res']
     steps = steps if steps is not None else wl['steps']
+    if steps < 1:
+        raise SystemExit(f'bench.py: --steps {steps}: at least one timed step')
+    profile = args.full or bool(args.launch_log) or args.kernel_breakdown
     warmup = args.warmup if warmup is None else warmup
     cfg_batch = batch_arg or wl['batch']
     if scaling == 'strong':
@@ -370,11 +402,12 @@ def measure(args, device, world, rank, name, *, res=None, nfp=None, scaling='wea
         torch.distributed.all_reduce(bad)
     if bad.item() > 0:
         raise SystemExit(f'bench.py: {int(bad.item())} non-finite gradient elements during warm-up ({nonfinite} on rank {rank}): no value is reported')
-    eng.collect_comm_stats(True, nonfinite=False)
+    eng.collect_comm_stats(args.full, nonfinite=False)
     eng.batch_idx = 0       # the timed region starts on an iteration on which every phase is due: K steps contain ceil(K / interval) of each
     barrier()
-    _lib.prof_enable(True)
-    _lib.prof_fetch()
+    if profile:
+        _lib.prof_enable(True)
+        _lib.prof_fetch()
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]      # per-step durations (torch's stream = the launch stream)
     t0 = time.perf_counter()
     marks[0].record()
@@ -383,8 +416,10 @@ def measure(args, device, world, rank, name, *, res=None, nfp=None, scaling='wea
         marks[i + 1].record()
     barrier()
     elapsed = time.perf_counter() - t0
-    _lib.prof_enable(False)
-    records = _lib.prof_fetch()
+    records = []
+    if profile:
+        _lib.prof_enable(False)
+        records = _lib.prof_fetch()
     step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(steps))
 
     t = torch.tensor([elapsed], dtype=torch.float64, device=device)
@@ -392,9 +427,12 @@ def measure(args, device, world, rank, name, *, res=None, nfp=None, scaling='wea
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
     elapsed = float(t.item())
 
+    if rank == 0 and headline and args.dump_outputs:
+        dump_outputs(eng, args.dump_outputs)
+
     # gradient exchange: what the compute stream waited for (not hidden under backward) vs the same all-reduces alone on the wire
     comm = None
-    if world > 1:
+    if world > 1 and args.full:
         comm = {}
         for ph in eng.phases:
             st = eng.comm_stats.get(ph.name)
@@ -484,13 +522,16 @@ def measure(args, device, world, rank, name, *, res=None, nfp=None, scaling='wea
                                       if dtype == 'bf16' else 'fp32 storage, ')
                                    + ('ADA off' if ada is None else f'ADA bgc on (p0 = {ada}, target 0.6; secondary measurement)'),
                        'global_batch': global_batch, 'per_rank_batch': batch, 'parallelism': f'dp{world}'},
-            'roofline': roofline, 'target_kernel': target,
             'ms_per_step_median': round(step_ms[len(step_ms) // 2], 2),
-            'step_tflops': round(total_flops / (elapsed * 1e3) / 1e9, 1),
-            'kernel_ms_per_step': {k: v['ms_per_step'] for k, v in breakdown.items()},
-            'sbg_kernel_time_frac_of_step': round(total_ms / (elapsed * 1e3), 3),
             'nonfinite_grads': sum(nonfinite.values()),
         }
+        if profile:
+            out.update({
+                'roofline': roofline, 'target_kernel': target,
+                'step_tflops': round(total_flops / (elapsed * 1e3) / 1e9, 1),
+                'kernel_ms_per_step': {k: v['ms_per_step'] for k, v in breakdown.items()},
+                'sbg_kernel_time_frac_of_step': round(total_ms / (elapsed * 1e3), 3),
+            })
         if comm is not None:
             out['comm'] = comm
     eng.close()
@@ -520,8 +561,13 @@ def main():
     ap.add_argument('--scaling', default='weak', choices=['weak', 'strong', 'both'],
                     help="weak (default; the mode the >= 6x at 8 GPUs target is stated for): per-rank batch fixed; strong: global batch fixed; "
                          "both: the weak line with the strong-scaling run in its `secondary` list")
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-secondary', action='store_true', help='headline workload: skip the reference-recipe precision run (num_fp16_res 4) after the headline loop')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline figure does not need: launch log (roofline, per-kernel times), the secondary precision run, '
+                         'the CPU baseline, the gradient-exchange figures')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write the gradients the last one computed as DIR/grad_<module>.npy')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
+    ap.add_argument('--no-secondary', action='store_true', help='--full, headline workload: skip the reference-recipe precision run (num_fp16_res 4) after the headline loop')
     ap.add_argument('--res', type=int, default=None, help='resolution override (sg2attent: 32 or 256; otherwise debug only)')
     ap.add_argument('--batch', type=int, default=None, help='per-rank batch (weak) / global batch (strong); default: the config\'s')
     ap.add_argument('--batch-gpu', type=int, default=None)
@@ -573,7 +619,7 @@ def main():
         rec = measure(args, device, world, rank, args.workload, nfp=args.num_fp16_res, scaling='strong', steps=args.steps, headline=False, **common)
         if rank == 0:
             secondary.append(slim(rec))
-    if plain_headline and not args.no_secondary and world == 1:
+    if args.full and plain_headline and not args.no_secondary and world == 1:
         # the reference recipe's precision split (bf16 in the 4 highest resolutions, fp32 storage below) on the same clock, same process
         rec = measure(args, device, world, rank, 'sg2ada', nfp=4, scaling=first_scaling, steps=args.steps, headline=False, **common)
         if rank == 0:
@@ -583,10 +629,11 @@ def main():
         out['ranks_seen'] = ranks_seen
         out['scaling_note'] = ('weak: every rank runs the config\'s batch (global batch x N); strong: the config\'s global batch split over the ranks '
                                '(reference trainers.py:524).  The >= 6x at 8 GPUs target of BASELINE.json is stated for the WEAK line.')
-        cpu = None
-        if world == 1 and not args.no_cpu_baseline and args.workload == 'sg2ada':
-            cpu = cpu_baseline(res=args.res or RES)
-        out['cpu_baseline'] = cpu
+        if args.full:
+            cpu = None
+            if world == 1 and not args.no_cpu_baseline and args.workload == 'sg2ada':
+                cpu = cpu_baseline(res=args.res or RES)
+            out['cpu_baseline'] = cpu
         if secondary:
             out['secondary'] = secondary
         print(json.dumps(out))

@@ -690,7 +690,25 @@ def gen_augment():
     save("augment", arrays, dict(cases=cases))
 
 
+# ---------------------------------------------------------------------------------------------------------------- configs
+
+CONFIG_NAMES = ["dcgan", "sg2ada", "big_gan", "ffhq_sg2", "sg2attent"]       # the five BASELINE.json names
+
+
+def gen_configs():
+    """the reference's own configs/*.yaml, parsed (yaml.safe_load), as JSON data: test_config_cpu writes each back as yaml and loads it
+    through arguments.load_config"""
+    import yaml
+    configs = {}
+    for name in CONFIG_NAMES:
+        with open(os.path.join(REF, "configs", name + ".yaml")) as fh:
+            configs[name] = yaml.safe_load(fh)
+        assert json.loads(json.dumps(configs[name])) == configs[name], name
+    save("reference_configs", {}, dict(configs=configs))
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["upfirdn2d", "bias_act", "conv2d_resample", "modulated_conv2d", "networks", "biggan", "augment", "sg2attent", "host_step", "metrics", "datasets"]
+    which = sys.argv[1:] or ["upfirdn2d", "bias_act", "conv2d_resample", "modulated_conv2d", "networks", "biggan", "augment", "sg2attent", "host_step", "metrics", "datasets",
+                             "configs"]
     for name in which:
         globals()["gen_" + name]()

@@ -224,20 +224,20 @@ def test_image_folder_and_sampler_against_the_reference(tmp_path):
         assert [int(next(it)) for _ in range(60)] == g.npz[f"sampler{j}"].tolist(), kw
 
 
-REFERENCE_CONFIGS = "/root/reference/configs"
-
-
 @pytest.mark.parametrize("name", ["dcgan", "sg2ada", "big_gan", "ffhq_sg2", "sg2attent"])
 def test_reference_yaml_files_load_unchanged(name, tmp_path):
     """the reference's OWN configs/*.yaml (the five BASELINE.json names) through arguments.load_config + trainer.setup_arguments, as they are:
-    container-only (the reference does not travel to the GPU box).  Data comes from the synthetic stand-in -- the yaml's data paths
-    (./data/*.zip) do not exist here -- and wandb logging keys are carried but unused."""
-    path = os.path.join(REFERENCE_CONFIGS, name + ".yaml")
-    if not os.path.isfile(path):
-        pytest.skip("reference checkout not present (GPU box)")
+    tests/golden/reference_configs.npz holds them parsed (make_golden.py), and each is written back as a yaml file here.  Data comes from
+    the synthetic stand-in -- the yaml's data paths (./data/*.zip) do not exist here -- and wandb logging keys are carried but unused."""
+    from golden_util import Golden
     from style_big_gan_amd.train_parts.trainers import trainers
-    raw = yaml.safe_load(open(path))
-    argv = ["exp.config_dir=" + REFERENCE_CONFIGS, f"exp.config={name}.yaml", "exp.name=t", "data.dataset=synthetic", "data.num_classes=10",
+    raw = Golden("reference_configs").meta["configs"][name]
+    config_dir = str(tmp_path / "configs")
+    os.makedirs(config_dir)
+    with open(os.path.join(config_dir, name + ".yaml"), "w") as fh:
+        yaml.safe_dump(raw, fh)
+    assert yaml.safe_load(open(os.path.join(config_dir, name + ".yaml"))) == raw
+    argv = ["exp.config_dir=" + config_dir, f"exp.config={name}.yaml", "exp.name=t", "data.dataset=synthetic", "data.num_classes=10",
             "data.resolution=" + {"dcgan": "32", "sg2ada": "256", "big_gan": "128", "ffhq_sg2": "1024", "sg2attent": "32"}[name]]
     cfg = arguments.load_config(argv)
     assert cfg.exp.trainer == raw["exp"]["trainer"] and cfg.gen.batch == raw["gen"]["batch"]

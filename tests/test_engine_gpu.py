@@ -284,3 +284,31 @@ def test_cat0_is_cat_with_views_backward(dev):
     assert misc.cat0([a]) is a
     mixed = misc.cat0([a, b.to(torch.bfloat16)])          # dtypes differ: plain torch.cat semantics (type promotion)
     assert mixed.dtype == torch.float32
+
+
+def test_bench_dump_outputs_are_the_timed_steps_gradients(tmp_path):
+    """bench.py --dump-outputs on the headline workload, in a process of its own: after the timed steps rank 0 writes one float32 file
+    per gradient reducer, sampled to DUMP_MAX_ELEMS values, finite and mostly non-zero (the buckets are zeros until a step fills them),
+    64 MB at most in all; the result line still counts the steps asked for"""
+    import json
+    import os
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 2 and line["ms_per_step"] > 0
+    assert sorted(os.listdir(out)) == ["grad_D.npy", "grad_G_mapping.npy", "grad_G_synthesis.npy"]
+    total = 0
+    for f in sorted(os.listdir(out)):
+        a = np.load(out / f)
+        total += os.path.getsize(out / f)
+        assert a.dtype == np.float32 and 0 < a.size <= bench.DUMP_MAX_ELEMS and np.isfinite(a).all(), f
+        assert np.count_nonzero(a) > a.size // 2, f
+    assert total <= 64e6
