@@ -137,6 +137,7 @@ static inline unsigned sbg_stream_grid(int64_t work_items, int block)
 bool sbg_prof_on();
 int  sbg_prof_open(hipStream_t s, int kind, double flops, double bytes, const int* dims, int ndims);
 void sbg_prof_close(hipStream_t s, int slot);
+void sbg_prof_set_dim(int slot, int i, int v);     // amend a logged launch's shape key once the dispatch has picked its kernel
 
 struct SbgProfScope {
     hipStream_t s; int slot;
@@ -144,4 +145,5 @@ struct SbgProfScope {
         if (sbg_prof_on()) slot = sbg_prof_open(stream, kind, flops, bytes, dims.begin(), (int)dims.size());
     }
     ~SbgProfScope() { if (slot >= 0) sbg_prof_close(s, slot); }
+    void set_dim(int i, int v) { if (slot >= 0) sbg_prof_set_dim(slot, i, v); }
 };

@@ -94,6 +94,13 @@ void sbg_prof_close(hipStream_t s, int slot)
     g_prof_log[slot].closed = true;
 }
 
+void sbg_prof_set_dim(int slot, int i, int v)
+{
+    std::lock_guard<std::mutex> lk(g_prof_mu);
+    if (slot < 0 || slot >= (int)g_prof_log.size() || i < 0 || i >= 7) return;
+    g_prof_log[slot].rec.dims[i] = v;
+}
+
 extern "C" int sbg_prof_enable(int on)
 {
     return g_prof_enabled.exchange(on ? 1 : 0);

@@ -697,19 +697,26 @@ static bool launch_fir_mfma_rpw(const UpfirdnArgs& a, hipStream_t stream)
     return true;
 }
 
+// Kernel that served an upfirdn2d launch: the launch log records 10000 * variant + 16 * upx + downx in dims[6].
+enum FirVariant { FIR_V_NONE = 0, FIR_V_SLIDE = 1, FIR_V_TILE = 2, FIR_V_SLIDE_EDGE = 3, FIR_V_TILE_EDGE = 4, FIR_V_FIXED44 = 5, FIR_V_GENERIC = 6,
+                  FIR_V_VEC8 = 7, FIR_V_SCALAR = 8 };
+
+// -> FIR_V_SLIDE / FIR_V_TILE when a matrix-core kernel took the launch, FIR_V_NONE otherwise
 template <class T>
-static bool launch_fir_mfma(const UpfirdnArgs& a, hipStream_t stream)
+static int launch_fir_mfma(const UpfirdnArgs& a, hipStream_t stream)
 {
     static const char* e = sbg_env("SBG_FIR_RPW");        // experiment switch: tile kernels (1 = 4 x 32 tiles, 2 = 8 x 32, 4 = 16 x 32) instead of the sliding window
-    if (a.tail == 2) return a.outH >= 16 && launch_fir_slide<T>(a, stream);      // the backward tail exists in the sliding-window kernel only
-    if (!e && a.outH >= 16) return launch_fir_slide<T>(a, stream);
-    if (e && atoi(e) == 1) return launch_fir_mfma_rpw<T, 1>(a, stream);
-    if (e && atoi(e) == 4) return launch_fir_mfma_rpw<T, 4>(a, stream);
-    return launch_fir_mfma_rpw<T, 2>(a, stream);
+    if (a.tail == 2) return (a.outH >= 16 && launch_fir_slide<T>(a, stream)) ? FIR_V_SLIDE : FIR_V_NONE;      // the backward tail exists in the sliding-window kernel only
+    if (!e && a.outH >= 16) return launch_fir_slide<T>(a, stream) ? FIR_V_SLIDE : FIR_V_NONE;
+    bool ok;
+    if (e && atoi(e) == 1)      ok = launch_fir_mfma_rpw<T, 1>(a, stream);
+    else if (e && atoi(e) == 4) ok = launch_fir_mfma_rpw<T, 4>(a, stream);
+    else                        ok = launch_fir_mfma_rpw<T, 2>(a, stream);
+    return ok ? FIR_V_TILE : FIR_V_NONE;
 }
 
-template <class T> static bool try_fir_mfma(const UpfirdnArgs& a, hipStream_t stream) { return launch_fir_mfma<T>(a, stream); }
-template <> bool try_fir_mfma<float>(const UpfirdnArgs&, hipStream_t) { return false; }
+template <class T> static int try_fir_mfma(const UpfirdnArgs& a, hipStream_t stream) { return launch_fir_mfma<T>(a, stream); }
+template <> int try_fir_mfma<float>(const UpfirdnArgs&, hipStream_t) { return FIR_V_NONE; }
 
 template <class T>
 static int launch_upfirdn(const UpfirdnArgs& a0, bool vec8, bool exact16, hipStream_t stream)
@@ -718,7 +725,7 @@ static int launch_upfirdn(const UpfirdnArgs& a0, bool vec8, bool exact16, hipStr
     const double es = sizeof(T) == 4 ? 4 : 2;
     SbgProfScope prof(stream, SBG_K_UPFIRDN2D, 0.0,
                       es * ((double)a.N * a.C * a.inH * a.inW + (double)a.N * a.C * a.outH * a.outW),
-                      {a.N, a.C, a.inH, a.inW, a.outH, a.outW, a.upx * 16 + a.downx});
+                      {a.N, a.C, a.inH, a.inW, a.outH, a.outW, a.upx * 16 + a.downx});      // dims[6] gains the variant digit below
     const bool mfma_ok = vec8 && exact16 && sizeof(T) == 2 && a.upx == 1 && a.upy == 1 && a.downx == 1 && a.downy == 1 && a.fw == 4 && a.fh == 4 && (a.C % 64) == 0
                          && a.outW >= 16 && a.outH >= 8 && sbg_env("SBG_FIR_NO_MFMA") == nullptr;
     // A few columns beyond a multiple of the 32-column strips (the 2 res + 1 wide outputs of the discriminator's low-pass in front of a strided
@@ -726,37 +733,46 @@ static int launch_upfirdn(const UpfirdnArgs& a0, bool vec8, bool exact16, hipStr
     // strips take the multiple of 32 and the register-blocked kernel the remaining columns, as a launch over the shifted sub-rectangle.
     const int rem = a.outW % 32;
     static const char* no_edge = sbg_env("SBG_FIR_NO_EDGE");
+    const int code = a.upx * 16 + a.downx;
     if (mfma_ok && !a.tail && !no_edge && rem >= 1 && rem <= 4 && a.outW > 32) {
         UpfirdnArgs m = a, e = a;
         m.outW = a.outW - rem;
         e.outW = rem; e.padx0 = a.padx0 - m.outW; e.y = (void*)((T*)a.y + (int64_t)m.outW * a.osx);
-        if (try_fir_mfma<T>(m, stream)) {
+        if (const int v = try_fir_mfma<T>(m, stream)) {
             const int xblocks = (e.outW + FIR_TX - 1) / FIR_TX, yblocks = (e.outH + FIR_TY - 1) / FIR_TY;
             e.total = (int64_t)e.N * yblocks * xblocks * (e.C >> 3);
             SBG_LAUNCH((upfirdn2d_fir_fixed_kernel<T, 4, 4>), dim3(sbg_stream_grid(e.total, 256)), dim3(256), 0, stream, e, xblocks, yblocks);
             SBG_HIP_LAUNCH_CHECK();
+            prof.set_dim(6, 10000 * (v == FIR_V_SLIDE ? FIR_V_SLIDE_EDGE : FIR_V_TILE_EDGE) + code);
             return SBG_OK;
         }
     }
-    if (mfma_ok && try_fir_mfma<T>(a, stream)) {
+    int variant = mfma_ok ? try_fir_mfma<T>(a, stream) : FIR_V_NONE;
+    if (variant != FIR_V_NONE) {
         // matrix-core FIR
     } else if (a.tail) {
         return sbg_fail(SBG_ERR_UNSUPPORTED, "upfirdn2d: fused tail requested but the matrix-core FIR path does not take this launch");
     } else if (vec8 && a.upx == 1 && a.upy == 1 && a.downx == 1 && a.downy == 1 && a.fw <= FIR_MAXF && a.fh <= FIR_MAXF && a.fw * a.fh > 1) {
         const int xblocks = (a.outW + FIR_TX - 1) / FIR_TX, yblocks = (a.outH + FIR_TY - 1) / FIR_TY;
         a.total = (int64_t)a.N * yblocks * xblocks * (a.C >> 3);
-        if (a.fw == 4 && a.fh == 4)
+        if (a.fw == 4 && a.fh == 4) {
+            variant = FIR_V_FIXED44;
             SBG_LAUNCH((upfirdn2d_fir_fixed_kernel<T, 4, 4>), dim3(sbg_stream_grid(a.total, 256)), dim3(256), 0, stream, a, xblocks, yblocks);
-        else
+        } else {
+            variant = FIR_V_GENERIC;
             SBG_LAUNCH((upfirdn2d_fir_kernel<T>), dim3(sbg_stream_grid(a.total, 256)), dim3(256), 0, stream, a, xblocks, yblocks);
+        }
     } else if (vec8) {
+        variant = FIR_V_VEC8;
         a.total = (int64_t)a.N * a.outH * a.outW * (a.C >> 3);
         SBG_LAUNCH((upfirdn2d_kernel<T, 8>), dim3(sbg_stream_grid(a.total, 256)), dim3(256), 0, stream, a);
     } else {
+        variant = FIR_V_SCALAR;
         a.total = (int64_t)a.N * a.outH * a.outW * a.C;
         SBG_LAUNCH((upfirdn2d_kernel<T, 1>), dim3(sbg_stream_grid(a.total, 256)), dim3(256), 0, stream, a);
     }
     SBG_HIP_LAUNCH_CHECK();
+    prof.set_dim(6, 10000 * variant + code);
     return SBG_OK;
 }
 
