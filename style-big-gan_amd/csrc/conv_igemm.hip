@@ -384,12 +384,7 @@ static int dispatch_conv(ConvArgs& a, int64_t x_bytes, int64_t w_bytes, bool all
     const bool dma = allow_dma && x_bytes < (int64_t)SBG_OOB_OFFSET && w_bytes < (int64_t)SBG_OOB_OFFSET;
     // tile choice: few output channels -> pixel-heavy tile; otherwise 128 x 128.
     if (dma) {
-        const char* v = sbg_env("SBG_CONV_TILE");      // experiment switch (tile / pipeline-depth variants)
-        const int variant = v ? atoi(v) : 0;
         if (a.Cout <= 64) return launch_conv_dma<MF, 64, 256, 1, 4, 4, 1>(a, (unsigned)x_bytes, (unsigned)w_bytes, stream);
-        if (variant == 1) return launch_conv_dma<MF, 128, 256, 2, 4, 3, 4>(a, (unsigned)x_bytes, (unsigned)w_bytes, stream);   // 8 waves, 2 WG/CU
-        if (variant == 2) return launch_conv_dma<MF, 128, 256, 2, 4, 4, 2>(a, (unsigned)x_bytes, (unsigned)w_bytes, stream);   // 8 waves, 1 WG/CU
-        if (variant == 3) return launch_conv_dma<MF, 128, 128, 2, 4, 4, 4>(a, (unsigned)x_bytes, (unsigned)w_bytes, stream);   // 8 waves, 128^2
         return launch_conv_dma<MF, 128, 128, 2, 2, 4, 2>(a, (unsigned)x_bytes, (unsigned)w_bytes, stream);
     }
     if (a.Cout <= 64)  return launch_conv<MF, 64, 256, 1, 4>(a, stream);
@@ -398,11 +393,9 @@ static int dispatch_conv(ConvArgs& a, int64_t x_bytes, int64_t w_bytes, bool all
 
 } // namespace
 
-static int phase_min_tiles()        // experiment switch: smallest tile count for which a transposed convolution runs as ONE multi-phase launch
-{
-    static const char* e = sbg_env("SBG_PHASE_MIN_TILES");
-    return e ? atoi(e) : 16;            // 256 -> 16: the 4x4 .. 32x32 up-sampling layers as one launch instead of four latency-bound ones (-1.4 ms per step)
-}
+// Smallest tile count for which a transposed convolution runs as ONE multi-phase launch.  256 -> 16: the 4x4 .. 32x32 up-sampling layers
+// as one launch instead of four latency-bound ones (-1.4 ms per step).
+static constexpr int kPhaseMinTiles = 16;
 
 extern "C" int sbg_conv2d_igemm(const sbg_conv_params* q, sbg_stream_t stream)
 {
@@ -434,7 +427,7 @@ extern "C" int sbg_conv2d_igemm(const sbg_conv_params* q, sbg_stream_t stream)
     a.stride = q->stride; a.ntaps = q->ntaps;
     for (int t = 0; t < SBG_MAX_TAPS; t++) { a.tap_dy[t] = q->tap_dy[t]; a.tap_dx[t] = q->tap_dx[t]; a.tap_slab[t] = q->tap_slab[t]; }
     a.accumulate = q->accumulate;
-    a.P = (int)P; a.ptiles = a.ctiles = 0; a.debug = sbg_experiment() << 8; a.lds_params = 0; a.ksplit = 1; a.y_split_stride = 0;
+    a.P = (int)P; a.ptiles = a.ctiles = 0; a.lds_params = 0; a.ksplit = 1; a.y_split_stride = 0;
     a.nphase = 1; a.ph_rot_div = 1;
     for (int i = 0; i < 4; i++) { a.ph_tap0[i] = 0; a.ph_ntaps[i] = 0; a.ph_OH[i] = 0; a.ph_OW[i] = 0; a.ph_P[i] = 0; a.ph_yoff[i] = 0; }
     hipStream_t s = (hipStream_t)stream;
@@ -442,7 +435,7 @@ extern "C" int sbg_conv2d_igemm(const sbg_conv_params* q, sbg_stream_t stream)
     for (int t = 0; t < q->ntaps; t++) { SBG_CHECK(q->tap_slab[t] >= 0, "conv2d_igemm: negative weight slab"); if (q->tap_slab[t] > maxslab) maxslab = q->tap_slab[t]; }
     const int64_t x_bytes = 2 * ((int64_t)(q->N - 1) * q->xs_n + (int64_t)(q->IH - 1) * q->xs_h + (int64_t)(q->IW - 1) * q->xs_w + q->Cin);
     const int64_t w_bytes = 2 * ((int64_t)maxslab * q->ws_slab + (int64_t)(q->Cout - 1) * q->ws_co + q->Cin);
-    const bool allow_dma = sbg_env("SBG_CONV_NO_DMA") == nullptr && q->xs_n >= 0 && q->xs_h >= 0 && q->xs_w >= 0 && q->ws_slab >= 0 && q->ws_co >= 0;
+    const bool allow_dma = q->xs_n >= 0 && q->xs_h >= 0 && q->xs_w >= 0 && q->ws_slab >= 0 && q->ws_co >= 0;
     if (q->nphase > 1) {
         // phases: one persistent launch when the shape fits that kernel, otherwise one launch per phase through this same entry point
         SBG_CHECK(q->nphase <= 4, "conv2d_igemm: at most 4 phases");
@@ -471,7 +464,7 @@ extern "C" int sbg_conv2d_igemm(const sbg_conv_params* q, sbg_stream_t stream)
             a.nphase = 1;
         }
         const int64_t tiles = ((ptot / q->nphase + 255) / 256) * q->nphase * ((q->Cout + 127) / 128);
-        if (allow_dma && q->Cout > 64 && tiles >= phase_min_tiles() && x_bytes < (int64_t)0x80000000u && w_bytes < (int64_t)0x80000000u && sbg_env("SBG_CONV_NO_PHASES") == nullptr) {
+        if (allow_dma && q->Cout > 64 && tiles >= kPhaseMinTiles && x_bytes < (int64_t)0x80000000u && w_bytes < (int64_t)0x80000000u) {
             a.nphase = q->nphase;
             const int rc = sbg_conv_k64_dispatch(a, q->xdtype == SBG_BF16, x_bytes, w_bytes, nullptr, 1, s);
             if (rc >= 0) return rc;

@@ -229,11 +229,6 @@ __global__ __launch_bounds__(512, 2) void conv_k64_kernel(ConvArgs p, unsigned x
     constexpr int LEAD = NSTAGE - 1;
     constexpr int A_BYTES = BC * 128, B_BYTES = BP * 128, STAGE = A_BYTES + B_BYTES;
 
-#ifdef SBG_K64_DEBUG     // ablations for diagnosis: 1 = no MFMA, 2 = no DMA inside the K loop, 4 = no fragment reads, 8 = no epilogue
-    const int dbg = p.debug;
-#else
-    constexpr int dbg = 0;
-#endif
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -301,7 +296,6 @@ __global__ __launch_bounds__(512, 2) void conv_k64_kernel(ConvArgs p, unsigned x
             for (int i = 0; i < TC; i++) fa[ks][i] = *reinterpret_cast<const short8_t*>(sa + i * 16 * 128 + (frag_off ^ (ks * 64)));
     };
     auto mma = [&]() {
-        if (dbg & 1) return;
 #pragma unroll
         for (int ks = 0; ks < 2; ks++)
 #pragma unroll
@@ -386,8 +380,8 @@ __global__ __launch_bounds__(512, 2) void conv_k64_kernel(ConvArgs p, unsigned x
         for (int s = 0; s < nsteps; s++) {
             if (!grpY) { if (s + 1 < nsteps) wait_vmcnt_const<C>(); else wait_vmcnt_const<0>(); }     // step s; step s + 1 may be in flight
             __builtin_amdgcn_s_barrier();                // B_a
-            if (!(dbg & 4)) { read_a(stage); read_b(stage); }
-            if (s + LEAD < nsteps && !(dbg & 2)) issue_next();
+            read_a(stage); read_b(stage);
+            if (s + LEAD < nsteps) issue_next();
             if (grpY) { if (s + 2 < nsteps) wait_vmcnt_const<C>(); else wait_vmcnt_const<0>(); }      // step s + 1; step s + 2 may be in flight
             __builtin_amdgcn_s_waitcnt(0xC07F);          // lgkmcnt(0)
             __builtin_amdgcn_s_barrier();                // B_b
@@ -400,7 +394,6 @@ __global__ __launch_bounds__(512, 2) void conv_k64_kernel(ConvArgs p, unsigned x
     }
 
     // ---- epilogue ---------------------------------------------------------------------------------------------------
-    if (dbg & 8) return;
     conv_epilogue8<TC, TP>(p, acc, c0 + wc, fg, [&](int j, int& n, int& oy, int& ox) {
         const int pix = p0 + wp + 16 * j + fr;
         const int pp = pix < p.P ? pix : 0;
@@ -433,25 +426,10 @@ __global__ __launch_bounds__(768, 3) void conv_halo_ld_kernel(ConvArgs p, unsign
     constexpr int WPIECES = BC / 8 / 2;                // weight pieces per weight loader per step
     constexpr int HPL = (HPIECES + 1) / 2;             // halo pieces per halo loader per slice
 
-#ifdef SBG_K64_DEBUG     // ablations for diagnosis: 1 = no MFMA, 4 = no fragment reads, 8 = no epilogue, 16 = no B_b barrier wait... (timing only)
-    const int dbg = p.debug;
-#else
-    constexpr int dbg = 0;
-#endif
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* const sH = smem + NSTAGE * STAGE;
     unsigned char* const sP = sH + 2 * HALO_BYTES;     // epilogue parameters of the tile being computed: two buffers (tile parity) of 3 KiB
     constexpr int PARAM_BYTES = 3072;
-#ifdef SBG_K64_STAMPS    // diagnosis build (scratch/halo_stamps.py): lane 0 of waves 0, 4, 8, 10 of workgroup 0 writes its clock in front of and behind every
-                         // barrier into the head of y (4096 records per wave pair); the outputs of that launch are garbage
-    unsigned long long* const stamp_base = (unsigned long long*)p.y + (threadIdx.x >> 7) * 4096;
-    const bool stamp_on = blockIdx.x == 0 && (threadIdx.x & 63) == 0 && ((threadIdx.x >> 6) == 0 || (threadIdx.x >> 6) == 4 || (threadIdx.x >> 6) == 8 || (threadIdx.x >> 6) == 10);
-    int stamp_i = 0;
-#define SBG_BARRIER() do { if (stamp_on && stamp_i < 4000) stamp_base[stamp_i] = __builtin_amdgcn_s_memtime(); stamp_i++; __builtin_amdgcn_s_barrier(); \
-                           if (stamp_on && stamp_i < 4000) stamp_base[stamp_i] = __builtin_amdgcn_s_memtime(); stamp_i++; } while (0)
-#else
-#define SBG_BARRIER() __builtin_amdgcn_s_barrier()
-#endif
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -518,8 +496,8 @@ __global__ __launch_bounds__(768, 3) void conv_halo_ld_kernel(ConvArgs p, unsign
         // The loader's HPL pieces of a slice with everything per-lane worked out ONCE: rel[i] = byte offset of piece i's halo pixel (py, px) and k-slot from the halo's
         // origin, flag bits {py == 0, py == PH - 1, px == 0, px == PW - 1, no pixel} (5 per piece, 6 pieces per word).  Per slice the origin's byte offset
         // and the tile's edge mask are scalars, so an issue is ~5 vector instructions instead of ~25 (a division by PW, two range tests, three multiplies).
-        // The loader waves share their SIMDs with the compute waves and were the last to arrive at every second barrier (scratch/halo_stamps.py):
-        // +3 .. 4.5 % (scratch/kbench_ab.py).
+        // The loader waves share their SIMDs with the compute waves and were the last to arrive at every second barrier (clock stamps at every barrier):
+        // +3 .. 4.5 %.
         int rel[HPL]; unsigned ef[(HPL + 5) / 6];
 #pragma unroll
         for (int w_ = 0; w_ < (HPL + 5) / 6; w_++) ef[w_] = 0;
@@ -555,14 +533,14 @@ __global__ __launch_bounds__(768, 3) void conv_halo_ld_kernel(ConvArgs p, unsign
         // The 22 pieces of the next slice go out TWO per half-step (behind each of the slice's first eleven barriers), not as one burst behind
         // the first: an LDS-DMA instruction costs its wave ~100+ cycles beside the compute waves' fragment reads, every wave of the workgroup
         // meets at the next barrier, and a burst of 22 made that one half-step ~4x as long as the 32 MFMAs it should hide behind.  Measured
-        // (scratch/kbench_ab.py, interleaved rounds on one device, [64, C, R, R] (*) [C, C, 3, 3]): C = 128 @ 256^2 1070 -> 1160 TF,
+        // (interleaved rounds on one device, [64, C, R, R] (*) [C, C, 3, 3]): C = 128 @ 256^2 1070 -> 1160 TF,
         // 256 @ 128^2 1154 -> 1300, 512 @ 64^2 1214 -> 1389, 512 @ 32^2 1273 -> 1390; three or four per half-step 1090-1110 / 1220-1250 /
         // 1280-1310.  (One piece behind each of the later barriers instead of two behind the first eleven: no difference.)
         constexpr int per = 2;                           // pieces per half-step
         for (int c = 0; c < nslices; c++) {
             wait_vmcnt_const<0>();                       // halo(c) has landed
-            SBG_BARRIER();                // 18c
-            const bool more = c + 1 < nslices && !(dbg & 2) && !(dbg & 32);       // 32: halo loads only
+            __builtin_amdgcn_s_barrier();                // 18c
+            const bool more = c + 1 < nslices;
             if (more) {
                 if (++chunk == kchunks) { chunk = 0; tile += G; tc = advance(tc); }
             }
@@ -576,11 +554,11 @@ __global__ __launch_bounds__(768, 3) void conv_halo_ld_kernel(ConvArgs p, unsign
                 }
                 if (i == 12 && lh == 0 && p.lds_params && cchunk == kchunks - 1) issue_params(ctile, cpar);
                 if (i == 16 && p.lds_params && c + 1 == nslices) wait_vmcnt_const<0>();      // the LAST tile's parameters have no later slice whose first barrier would cover them
-                SBG_BARRIER();
+                __builtin_amdgcn_s_barrier();
             });
             if (++cchunk == kchunks) { cchunk = 0; ctile += G; cpar ^= 1; }
         }
-        SBG_BARRIER();                    // 2S
+        __builtin_amdgcn_s_barrier();                    // 2S
         return;
     }
     if (wave >= 8) {
@@ -645,14 +623,14 @@ __global__ __launch_bounds__(768, 3) void conv_halo_ld_kernel(ConvArgs p, unsign
             else if (newer == 2) wait_vmcnt_const<2 * WPIECES>();
             else if (newer == 1) wait_vmcnt_const<1 * WPIECES>();
             else wait_vmcnt_const<0>();
-            SBG_BARRIER();                // 2s
-            const bool go = s >= 1 && issued < S && !(dbg & 2) && !(dbg & 16);      // step s + 3 -> the stage step s - 1 was read from (16: weight loads only)
+            __builtin_amdgcn_s_barrier();                // 2s
+            const bool go = s >= 1 && issued < S;      // step s + 3 -> the stage step s - 1 was read from
             if (go) { issue_prep(); issue_part(0, split ? WPIECES / 2 : WPIECES); }
-            SBG_BARRIER();                // 2s + 1
+            __builtin_amdgcn_s_barrier();                // 2s + 1
             if (go) { if (split) issue_part(WPIECES / 2, WPIECES); issue_done(); issued++; }
             else if (s >= 1 && issued < S) issued++;
         }
-        SBG_BARRIER();                    // 2S
+        __builtin_amdgcn_s_barrier();                    // 2S
         return;
     }
 
@@ -686,7 +664,6 @@ __global__ __launch_bounds__(768, 3) void conv_halo_ld_kernel(ConvArgs p, unsign
     int tpar = 0, done_par = 0;                          // parity of the current / finished tile's ordinal: its parameter buffer
     auto epilogue = [&](const TileC& tc) __attribute__((always_inline)) {
         const LdsParams lp{(lds_cfloat*)(sP + done_par * PARAM_BYTES), wc, TW};
-        if (!(dbg & 8))
         conv_epilogue8<TC, TP, true>(p, acc, tc.c0 + wc, fg, [&](int j, int& n, int& oy, int& ox) {
             const int sg = wpi * TP + j, r = sg / SEG, cseg = (sg - r * SEG) * 16;
             n = tc.tn; oy = tc.y0 + r; ox = tc.x0 + cseg + fr;
@@ -697,16 +674,15 @@ __global__ __launch_bounds__(768, 3) void conv_halo_ld_kernel(ConvArgs p, unsign
 #pragma unroll
             for (int j = 0; j < TP; j++) acc[i][j] = float4_t{0.f, 0.f, 0.f, 0.f};
     };
-    if (grpY) SBG_BARRIER();              // 0
+    if (grpY) __builtin_amdgcn_s_barrier();              // 0
     for (int c = 0; c < nslices; c++) {
         const unsigned char* hb = sH + par * HALO_BYTES;
         static_for<NT>([&](auto tap_tag) {
             constexpr int t = decltype(tap_tag)::value;
             const int shift = __builtin_amdgcn_readlane(tbl_shift, t);
             const unsigned char* sa = smem + stage * STAGE + wc * 128;
-            SBG_BARRIER();                // B_a: the stage and the halo buffer of this step have landed
+            __builtin_amdgcn_s_barrier();                // B_a: the stage and the halo buffer of this step have landed
             if (t == 0 && pend) { epilogue(done); pend = false; }
-            if (!(dbg & 4)) {
 #pragma unroll
             for (int ks = 0; ks < 2; ks++)
 #pragma unroll
@@ -718,11 +694,9 @@ __global__ __launch_bounds__(768, 3) void conv_halo_ld_kernel(ConvArgs p, unsign
 #pragma unroll
                 for (int ks = 0; ks < 2; ks++) fb[ks][j] = *reinterpret_cast<const short8_t*>(hb + (o ^ (ks * 64)));
             }
-            }
             __builtin_amdgcn_s_waitcnt(0xC07F);          // lgkmcnt(0): fragments are in registers, this wave no longer reads the stage
-            SBG_BARRIER();                // B_b
+            __builtin_amdgcn_s_barrier();                // B_b
             __builtin_amdgcn_sched_barrier(0);
-            if (!(dbg & 1))
 #pragma unroll
             for (int ks = 0; ks < 2; ks++)
 #pragma unroll
@@ -738,18 +712,17 @@ __global__ __launch_bounds__(768, 3) void conv_halo_ld_kernel(ConvArgs p, unsign
         // X defers its epilogue behind the next step's B_a (Y is then in its last MFMA phase).  With a fused tail (its arithmetic makes the epilogue
         // ~40 % longer) Y runs its own right away, behind its last MFMA, in the interval in which X runs X's: the two groups' tail arithmetic and
         // stores side by side take less than one after the other (deferred like X's, Y's epilogue filled a second ~3850-cycle interval while X
-        // waited at the next barrier; scratch/halo_stamps.py).  Measured, interleaved rounds: with tail +3 / +1.7 / +1 % (128 / 256 / 512 channels),
+        // waited at the next barrier; clock stamps).  Measured, interleaved rounds: with tail +3 / +1.7 / +1 % (128 / 256 / 512 channels),
         // plain stores -1 % -- a plain launch keeps both deferred.
         if (grpY && p.lds_params) epilogue(done); else pend = true;
         chunk = 0; tile += G;
         if (tile < ntiles) cur = advance(cur);
     }
     if (pend) epilogue(done);
-    if (!grpY) SBG_BARRIER();             // 2S
+    if (!grpY) __builtin_amdgcn_s_barrier();             // 2S
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-#undef SBG_BARRIER
 // Gather kernel with loader waves: the 128 x 256 tile of conv_k64_kernel in the persistent 12-wave structure of
 // conv_halo_ld_kernel.  Waves 8-9 stream the weight tile, waves 10-11 gather the 256 pixel rows of the tap (im2col on the
 // fly, out-of-image rows at an out-of-range offset); three 48 KB stages, the loads of step s + 2 are issued while step s
@@ -990,7 +963,7 @@ static int launch_halo_ld(ConvArgs& a, unsigned x_bytes, unsigned w_bytes, hipSt
                           && ((((uintptr_t)a.oscale) & 15) == 0) && ((((uintptr_t)a.bias) & 15) == 0) && a.ydtype != SBG_F16;
         const bool nz_ok = !a.noise || (((((uintptr_t)a.noise) & 15) == 0) && (a.noise_sn & 3) == 0 && (a.OW & 3) == 0
                                         && (int64_t)a.N * (a.noise_sn > 0 ? a.noise_sn : 0) + (int64_t)a.OH * a.OW < (1ll << 28));
-        a.lds_params = !plain && fast && nz_ok && (int64_t)a.N * a.Cout < (1ll << 28) && !((a.debug >> 8) & 32);      // experiment bit 32: parameters from global memory
+        a.lds_params = !plain && fast && nz_ok && (int64_t)a.N * a.Cout < (1ll << 28);
     }
     static_assert(lds <= 160 * 1024, "LDS budget");
     a.ctiles = (a.Cout + 127) / 128;
@@ -1087,16 +1060,14 @@ __global__ __launch_bounds__(256) void conv_ksplit_reduce_epi_kernel(const float
 }
 
 template <class MF>
-static int dispatch_k64(ConvArgs& a, int level, unsigned xb, unsigned wb, hipStream_t stream)
+static int dispatch_k64(ConvArgs& a, unsigned xb, unsigned wb, hipStream_t stream)
 {
     if (a.nphase > 1) return launch_gather_ld<MF>(a, xb, wb, stream);       // multi-phase launches exist only in the persistent gather kernel
     // halo kernel: stride 1, nine taps with |offset| <= 1, output grid == input grid, tile-aligned, enough tiles to fill the chip
-    bool halo = level >= 2 && a.stride == 1 && a.ntaps == 9 && a.OH == a.IH && a.OW == a.IW;
+    bool halo = a.stride == 1 && a.ntaps == 9 && a.OH == a.IH && a.OW == a.IW;
     for (int t = 0; halo && t < 9; t++) halo = a.tap_dy[t] >= -1 && a.tap_dy[t] <= 1 && a.tap_dx[t] >= -1 && a.tap_dx[t] <= 1;
     const int64_t tiles256 = (int64_t)((a.P + 255) / 256) * ((a.Cout + 127) / 128);
     if (halo && a.Cout > 64 && tiles256 >= 256) {
-        const int rc8 = sbg_conv_halo8_dispatch(a, std::is_same<MF, bf16_mfma>::value, xb, wb, stream);
-        if (rc8 != -1) return rc8;
         if (a.OW % 32 == 0 && a.OH % 8 == 0)  return launch_halo_ld<MF, 8, 32>(a, xb, wb, stream);
         if (a.OW % 16 == 0 && a.OH % 16 == 0) return launch_halo_ld<MF, 16, 16>(a, xb, wb, stream);
     }
@@ -1105,9 +1076,8 @@ static int dispatch_k64(ConvArgs& a, int level, unsigned xb, unsigned wb, hipStr
     if (tiles256 < 256) return launch_k64<MF, 128, 128, 2, 4>(a, xb, wb, stream);
     // short reductions (transposed-conv phases: 1-4 taps) gain from the persistent pipeline; measured: +4..10 % at <= 8 K-steps per tile,
     // -5 % at 18+ (the 8-wave kernel's in-wave DMA issue overlaps better there)
-    static const char* egl = sbg_env("SBG_K64_GATHER_LD");        // experiment switch: 0 never, 1 always
     const int ksteps = a.ntaps * ((a.Cin + 63) >> 6);
-    if (egl ? atoi(egl) != 0 : (ksteps >= 2 && ksteps <= 8)) return launch_gather_ld<MF>(a, xb, wb, stream);      // 1 step: store-bound, the plain kernel wins
+    if (ksteps >= 2 && ksteps <= 8) return launch_gather_ld<MF>(a, xb, wb, stream);      // 1 step: store-bound, the plain kernel wins
     return launch_k64<MF, 128, 256, 2, 4>(a, xb, wb, stream);
 }
 
@@ -1133,14 +1103,6 @@ int sbg_conv_k64_dispatch(ConvArgs& a, bool bf16, int64_t x_bytes, int64_t w_byt
 {
     if (x_bytes >= (int64_t)SBG_OOB_OFFSET || w_bytes >= (int64_t)SBG_OOB_OFFSET) return -1;
     if (a.xs_n < 0 || a.xs_h < 0 || a.xs_w < 0 || a.ws_slab < 0 || a.ws_co < 0) return -1;
-    // experiment switch: SBG_CONV_K64 = 0 off / 1 gather only / 2 (default) gather + halo
-    const char* e1 = sbg_env("SBG_CONV_K64");
-    const int level = e1 ? atoi(e1) : 2;
-    if (level <= 0) return -1;
-#ifdef SBG_K64_DEBUG
-    { const char* e3 = sbg_env("SBG_K64_ABL"); a.debug = (a.debug & ~255) | (e3 ? atoi(e3) & 255 : 0); }
-#endif
-    a.debug = (a.debug & 255) | (sbg_experiment() << 8);      // variants under A/B test (sbg_experiment_set)
     const unsigned xb = (unsigned)x_bytes, wb = (unsigned)w_bytes;
     const int64_t y_numel = (int64_t)a.P * a.Cout;
     const bool dense_y = a.ys_w == a.Cout && a.ys_h == (int64_t)a.OW * a.Cout && a.ys_n == (int64_t)a.OH * a.OW * a.Cout;
@@ -1153,7 +1115,7 @@ int sbg_conv_k64_dispatch(ConvArgs& a, bool bf16, int64_t x_bytes, int64_t w_byt
         void* y = a.y; const int acc = a.accumulate;
         b.y = workspace; b.accumulate = 0; b.ksplit = k; b.y_split_stride = y_numel;
         b.ydtype = SBG_F32; b.act = SBG_ACT_LINEAR; b.gain = 1.f; b.clamp = -1.f; b.bias = nullptr; b.noise = nullptr; b.oscale = nullptr;    // raw fp32 slabs
-        const int rc = bf16 ? dispatch_k64<bf16_mfma>(b, level, xb, wb, stream) : dispatch_k64<f16_mfma>(b, level, xb, wb, stream);
+        const int rc = bf16 ? dispatch_k64<bf16_mfma>(b, xb, wb, stream) : dispatch_k64<f16_mfma>(b, xb, wb, stream);
         if (rc != SBG_OK) return rc;
         if (simple) {
             unsigned grid = (unsigned)((y_numel + 15) / 16); if (grid > 4096) grid = 4096;
@@ -1165,6 +1127,6 @@ int sbg_conv_k64_dispatch(ConvArgs& a, bool bf16, int64_t x_bytes, int64_t w_byt
         SBG_HIP_LAUNCH_CHECK();
         return SBG_OK;
     }
-    if (bf16) return dispatch_k64<bf16_mfma>(a, level, xb, wb, stream);
-    return dispatch_k64<f16_mfma>(a, level, xb, wb, stream);
+    if (bf16) return dispatch_k64<bf16_mfma>(a, xb, wb, stream);
+    return dispatch_k64<f16_mfma>(a, xb, wb, stream);
 }

@@ -189,8 +189,6 @@ static int launch_thin(const ConvArgs& a, int maxP, int pitch, int lds, hipStrea
 // Returns SBG_OK / an error, or -1 when the launch is not a thin one (the caller then uses the wide kernels).
 int sbg_conv_thin_dispatch(ConvArgs& a, bool bf16, hipStream_t stream)
 {
-    static const char* off = sbg_env("SBG_CONV_NO_THIN");
-    if (off) return -1;
     if ((a.Cin & 7) || a.Cin > 64 || a.Cout > 64 || a.Cout < 1) return -1;
     if (!((a.Cin <= 32) || (a.Cout <= 32))) return -1;                 // 64 x 64 stays with the wide kernels
     if (a.ksplit > 1 || a.ntaps < 1) return -1;
@@ -216,16 +214,13 @@ int sbg_conv_thin_dispatch(ConvArgs& a, bool bf16, hipStream_t stream)
     SbgProfScope prof(stream, SBG_K_CONV_IGEMM, 2.0 * macs * a.Cout * (double)a.Cin,
                       2.0 * a.N * a.IH * a.IW * (double)a.Cin + 2.0 * a.ntaps * a.Cout * (double)a.Cin + ys * outpix * (double)a.Cout * (a.accumulate ? 2 : 1),
                       {(int)outpix, a.Cout, a.Cin, a.ntaps, a.stride, a.OH, 6000000 + TCs * 16});
-    // one or two output fragments: eight pixel fragments per wave (the A fragment read, the tap decode and the bounds math are shared by twice
-    // the pixels; measured: see DESIGN.md); four output fragments keep four (accumulator registers)
-    static const char* tp4 = sbg_env("SBG_THIN_TP4");
-    const bool wide = TCs <= 2 && tp4 && atoi(tp4) == 0 && maxP >= (1 << 16);       // measured no better than four rows per wave: off unless SBG_THIN_TP4=0
+    // four pixel fragments per wave (eight, sharing the A fragment read and the tap decode over twice the pixels, measured no better: DESIGN.md)
     if (bf16) {
-        if (TCs == 1) return wide ? launch_thin<bf16_mfma, 1, 8>(a, maxP, pitch, lds, stream) : launch_thin<bf16_mfma, 1, 4>(a, maxP, pitch, lds, stream);
-        if (TCs == 2) return wide ? launch_thin<bf16_mfma, 2, 8>(a, maxP, pitch, lds, stream) : launch_thin<bf16_mfma, 2, 4>(a, maxP, pitch, lds, stream);
+        if (TCs == 1) return launch_thin<bf16_mfma, 1, 4>(a, maxP, pitch, lds, stream);
+        if (TCs == 2) return launch_thin<bf16_mfma, 2, 4>(a, maxP, pitch, lds, stream);
         return launch_thin<bf16_mfma, 4, 4>(a, maxP, pitch, lds, stream);
     }
-    if (TCs == 1) return wide ? launch_thin<f16_mfma, 1, 8>(a, maxP, pitch, lds, stream) : launch_thin<f16_mfma, 1, 4>(a, maxP, pitch, lds, stream);
-    if (TCs == 2) return wide ? launch_thin<f16_mfma, 2, 8>(a, maxP, pitch, lds, stream) : launch_thin<f16_mfma, 2, 4>(a, maxP, pitch, lds, stream);
+    if (TCs == 1) return launch_thin<f16_mfma, 1, 4>(a, maxP, pitch, lds, stream);
+    if (TCs == 2) return launch_thin<f16_mfma, 2, 4>(a, maxP, pitch, lds, stream);
     return launch_thin<f16_mfma, 4, 4>(a, maxP, pitch, lds, stream);
 }

@@ -136,7 +136,7 @@ __global__ __launch_bounds__(512) void conv_up2_kernel(ConvArgs p, unsigned x_by
     auto dma_w = [&](int chunk, int k, int slot, bool live) { dma_w_piece(chunk, k, slot, live, 0); dma_w_piece(chunk, k, slot, live, 1); };
     // `late`: a step's four DMA instructions go out one behind each group of eight MFMAs, not together in front of the step's first fragment
     // read: all eight waves leave the barrier together, so four back-to-back LDS-DMA issues (~100 cycles each) kept the matrix pipe idle at the
-    // head of every step.  Measured (scratch/kbench_ab.py, one device, interleaved): [64,256,128^2] -> 128 725 -> 781 TF, [64,512,64^2] -> 256
+    // head of every step.  Measured (one device, interleaved): [64,256,128^2] -> 128 725 -> 781 TF, [64,512,64^2] -> 256
     // 841 -> 936, [64,512,32^2] -> 512 826 -> 918 (border launch included).  
     constexpr bool late = true;              // (the early form is in the history: as a run-time switch it cost nine spilled registers)
 
@@ -273,8 +273,6 @@ static int launch_up2(const ConvArgs& a, unsigned x_bytes, unsigned w_bytes, int
 // the last row of the phases that have Hm + 1 rows, the last column of those with Wm + 1 columns -- as phases of an ordinary launch.
 int sbg_conv_up2_dispatch(ConvArgs& a, bool bf16, int64_t x_bytes, int64_t w_bytes, sbg_conv_params* border, const sbg_conv_params* q, hipStream_t stream)
 {
-    static const char* off = sbg_env("SBG_CONV_NO_UP2");
-    if (off) return -1;
     if (a.nphase != 4 || a.stride != 1 || a.ksplit > 1 || a.accumulate) return -1;
     if (a.ph_ntaps[0] != 4 || a.ph_ntaps[1] != 2 || a.ph_ntaps[2] != 2 || a.ph_ntaps[3] != 1) return -1;
     if ((a.Cout % 8) != 0 || (a.Cin % 8) != 0 || a.Cout < 64 || a.Cin < 64) return -1;

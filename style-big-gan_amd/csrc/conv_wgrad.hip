@@ -48,7 +48,6 @@ struct WgradArgs {
     int atiles, btiles;
     int tap0;               // first tap handled by this launch (out slab offset)
     int ntaps_total;
-    int experiment;         // sbg_experiment() at launch: variants under A/B test
 };
 
 // Workgroup -> (a tile, b tile, pixel split).  Workgroups are dealt round-robin to the eight XCDs, each with its own L2: all channel
@@ -240,11 +239,6 @@ __global__ __launch_bounds__(512) void conv_wgrad_rows_kernel(WgradArgs p, unsig
     // S = stride between the coarse (a) and fine (b) grids: b pixel = S * a pixel + tap, taps = (dy0 + i, dx0 + j), i, j in 0..2
     static_assert(BCA == 64 || BCA == 128, "a tile of 64 or 128 channels");
     static_assert(NSTAGE >= 2 && NSTAGE <= 6, "2..6 stages (the wait ladder covers five chunks in flight)");
-#ifdef SBG_WGRAD_ABL_CT     // timing-only ablation builds (scratch/wgrad_abl.py): 1 = no MFMA, 2 = no DMA inside the loop, 4 = no fragment reads
-    constexpr int ABL = SBG_WGRAD_ABL_CT;
-#else
-    constexpr int ABL = 0;
-#endif
     constexpr int BCB = 64, NT = 9, DEPTH = NSTAGE - 1;     // NSTAGE = 2 (one chunk of loads in flight) lets two workgroups share a CU where three stages would not fit twice
     constexpr int TA = BCA / 32;                               // 16-channel a fragments per wave
     constexpr int APIECES = BCA / 16;                          // a-tile = BCA / 64 sub-tiles of [32 pixels][64 channels], 4 pieces each
@@ -321,7 +315,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_rows_kernel(WgradArgs p, unsig
         for (int i = 0; i < PIECES; i++) issue_piece(cc, i);
     };
     // `late`: the DMA instructions of chunk s + DEPTH go out spread over the tap loop, each behind a tap's MFMAs, instead of together right
-    // behind the barrier (where all eight waves issued them at once and the matrix pipe waited).  Measured (scratch/kbench_ab.py, one device,
+    // behind the barrier (where all eight waves issued them at once and the matrix pipe waited).  Measured (one device,
     // interleaved rounds, 64 images): 128 x 128 @ 256^2 1060 -> 1135 TF, 256 x 256 @ 128^2 1149 -> 1227, 512 x 512 @ 64^2 1204 -> 1285,
     // stride 2: 256 x 128 917 -> 1016, 512 x 256 966 -> 1081.  
     constexpr bool late = true;
@@ -372,7 +366,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_rows_kernel(WgradArgs p, unsig
             else                                       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
         __builtin_amdgcn_s_barrier();
-        const bool more = !(ABL & 2) && s + DEPTH < nloc;
+        const bool more = s + DEPTH < nloc;
         ChunkC nxt = chunk_coords(more ? s + DEPTH : s);
         if (more && !late) {
 #pragma unroll
@@ -384,42 +378,31 @@ __global__ __launch_bounds__(512) void conv_wgrad_rows_kernel(WgradArgs p, unsig
         // without the loads, 325 us MFMA only).  The explicit vmcnt(PIECES) + barrier above is the real dependence.
         const unsigned stage = lds_base + (unsigned)((s % NSTAGE) * STAGE);
         short4_t alo[TA], ahi[TA], blo[3], bhi[3];
-        if constexpr ((ABL & 4) != 0) {
-#pragma unroll
-            for (int i = 0; i < TA; i++) alo[i] = ahi[i] = short4_t{(short)s, 1, 2, 3};
-#pragma unroll
-            for (int i = 0; i < 3; i++) blo[i] = bhi[i] = short4_t{(short)s, 3, 2, 1};
-        }
         sbg_static_for<TA>([&](auto it) {
             constexpr int i = decltype(it)::value;
-            if constexpr ((ABL & 4) == 0) {
-                lds_tr_issue<0>(alo[i], stage + (unsigned)offA[i]);
-                lds_tr_issue<16 * 128>(ahi[i], stage + (unsigned)offA[i]);
-            }
+            lds_tr_issue<0>(alo[i], stage + (unsigned)offA[i]);
+            lds_tr_issue<16 * 128>(ahi[i], stage + (unsigned)offA[i]);
         });
         unsigned pb[3];
 #pragma unroll
         for (int d = 0; d < 3; d++) pb[d] = stage + (unsigned)offB[d];
         auto issue_b = [&](auto tt) {
             constexpr int t = decltype(tt)::value, dyi = t / 3, dxi = t % 3, OFF = A_BYTES + dyi * PROW * 128;
-            if constexpr ((ABL & 4) == 0) {
-                lds_tr_issue<OFF>(blo[t % 3], pb[dxi]);
-                lds_tr_issue<OFF + 16 * 128>(bhi[t % 3], pb[dxi]);
-            }
+            lds_tr_issue<OFF>(blo[t % 3], pb[dxi]);
+            lds_tr_issue<OFF + 16 * 128>(bhi[t % 3], pb[dxi]);
         };
         issue_b(std::integral_constant<int, 0>{});
         issue_b(std::integral_constant<int, 1>{});
         sbg_static_for<9>([&](auto tt) {
             constexpr int t = decltype(tt)::value;
             if constexpr (t + 2 < 9) issue_b(std::integral_constant<int, t + 2>{});
-            if constexpr ((ABL & 4) == 0)
-                lds_wait<(t + 2 < 9 ? 4 : t + 1 < 9 ? 2 : 0)>(blo[t % 3], bhi[t % 3]);      // the reads of taps t + 1 and t + 2 may still be in flight
+            lds_wait<(t + 2 < 9 ? 4 : t + 1 < 9 ? 2 : 0)>(blo[t % 3], bhi[t % 3]);      // the reads of taps t + 1 and t + 2 may still be in flight
             // (the a reads precede tap 0's and LDS returns in order: they have landed)
             const short8_t fb = short8_t{blo[t % 3][0], blo[t % 3][1], blo[t % 3][2], blo[t % 3][3], bhi[t % 3][0], bhi[t % 3][1], bhi[t % 3][2], bhi[t % 3][3]};
 #pragma unroll
             for (int i = 0; i < TA; i++) {
                 const short8_t fa_i = short8_t{alo[i][0], alo[i][1], alo[i][2], alo[i][3], ahi[i][0], ahi[i][1], ahi[i][2], ahi[i][3]};
-                if constexpr ((ABL & 1) == 0) acc[t][i] = Mfma<MF>::run(fa_i, fb, acc[t][i]);
+                acc[t][i] = Mfma<MF>::run(fa_i, fb, acc[t][i]);
             }
             if (more && late) {      // pieces i with i * 9 / PIECES == t: spread evenly over the nine taps
                 sbg_static_for<PIECES>([&](auto pt) {
@@ -575,8 +558,7 @@ struct ThinPlan { bool ok; int dymin, dxmin, RY, PCOLS, wave_lds, nwg; };
 static ThinPlan thin_plan(const sbg_wgrad_params* q)
 {
     ThinPlan t; t.ok = false;
-    static const char* off = sbg_env("SBG_WGRAD_NO_THIN");
-    if (off || q->Ca > 32 || q->Cb > 32 || q->Ca * q->Cb > 512 || q->ntaps > 9 || q->ntaps < 1 || q->stride < 1 || q->stride > 2 || q->N < 1) return t;
+    if (q->Ca > 32 || q->Cb > 32 || q->Ca * q->Cb > 512 || q->ntaps > 9 || q->ntaps < 1 || q->stride < 1 || q->stride > 2 || q->N < 1) return t;
     int dy0 = q->tap_dy[0], dy1 = dy0, dx0 = q->tap_dx[0], dx1 = dx0;
     for (int i = 1; i < q->ntaps; i++) {
         if (q->tap_dy[i] < dy0) dy0 = q->tap_dy[i]; if (q->tap_dy[i] > dy1) dy1 = q->tap_dy[i];
@@ -594,13 +576,7 @@ static ThinPlan thin_plan(const sbg_wgrad_params* q)
     return t;
 }
 
-static void plan_split_target(WgradArgs& a, int bca, int bcb, int target);
-static void plan_split(WgradArgs& a, int bca, int bcb)
-{
-    static const char* e = sbg_env("SBG_WGRAD_TARGET");      // experiment switch: workgroups aimed for (tiles x pixel splits)
-    plan_split_target(a, bca, bcb, e ? atoi(e) : 1024);
-}
-static void plan_split_target(WgradArgs& a, int bca, int bcb, int target)
+static void plan_split(WgradArgs& a, int bca, int bcb, int target)     // target = workgroups aimed for (tiles x pixel splits)
 {
     a.atiles = (a.Ca + bca - 1) / bca;
     a.btiles = (a.Cb + bcb - 1) / bcb;
@@ -618,22 +594,21 @@ static bool use_big_tile(int ntaps) { return ntaps == 1; }
 
 static int rows_bca(const WgradArgs& a)      // a-tile width of the rows kernel: 128 halves the staged bytes per MFMA
 {
-    static const char* e = sbg_env("SBG_WGRAD_BCA");
-    if (e) return atoi(e) == 64 ? 64 : 128;
     // 128 wherever there are 128 a channels: half the staged bytes and 0.72 instead of 1.22 fragment reads per MFMA.  (While the compiler still
     // guarded the fragment reads with vmcnt(0), the wide tile lost 7-10 % at stride 1 up to 512 channels: one workgroup per CU, nothing overlapped.)
     return a.Ca >= 128 ? 128 : 64;
 }
 
-static int rows_nstage(int stride, int bca)   // stages of the rows kernel (LDS: stages x (a + patch pieces) + 1 KiB).  Measured flat from 2 to 6 stages at one
-{                                             // workgroup per CU (the L2 -> LDS stream is not latency bound); what matters is that two workgroups still fit where registers allow two
+// Stages of the rows kernel (LDS: stages x (a + patch pieces) + 1 KiB).  Measured flat from 2 to 6 stages at one workgroup per CU (the L2 -> LDS
+// stream is not latency bound); what matters is that two workgroups still fit where registers allow two.
+static constexpr int rows_nstage(int stride, int bca)
+{
     if (bca == 128) return 4;                 // 4 x 23 + 1 = 93 KB (stride 1) / 4 x 35 + 1 = 141 KB (stride 2): one workgroup per CU (195 VGPRs)
     return stride == 1 ? 4 : 2;               // 4 x 19 + 1 = 77 KB / 2 x 31 + 1 = 63 KB: two per CU
 }
 
 static bool rows_kernel_ok(const sbg_wgrad_params* q, const WgradArgs& a)
 {
-    if (sbg_env("SBG_WGRAD_NO_DMA")) return false;
     if ((q->stride != 1 && q->stride != 2) || (q->PW % 32) != 0 || q->ntaps != 9) return false;
     for (int t = 0; t < 9; t++)          // the kernel hard-codes a row-major 3x3 tap window starting at (dy[0], dx[0])
         if (q->tap_dy[t] != q->tap_dy[0] + t / 3 || q->tap_dx[t] != q->tap_dx[0] + t % 3) return false;
@@ -660,9 +635,9 @@ static int fill_args(const sbg_wgrad_params* q, WgradArgs& a)
     a.stride = q->stride; a.ntaps = q->ntaps; a.accumulate = q->accumulate;
     for (int t = 0; t < SBG_MAX_TAPS; t++) { a.tap_dy[t] = q->tap_dy[t]; a.tap_dx[t] = q->tap_dx[t]; }
     a.P = (int64_t)q->N * q->PH * q->PW;
-    a.tap0 = 0; a.ntaps_total = q->ntaps; a.experiment = sbg_experiment();
-    if (use_big_tile(q->ntaps)) plan_split(a, 128, 128); else plan_split(a, 64, 64);
-    if (rows_kernel_ok(q, a)) plan_split_target(a, rows_bca(a), 64, 512);      // one resident workgroup per CU: two waves of workgroups, half the slab traffic
+    a.tap0 = 0; a.ntaps_total = q->ntaps;
+    if (use_big_tile(q->ntaps)) plan_split(a, 128, 128, 1024); else plan_split(a, 64, 64, 1024);
+    if (rows_kernel_ok(q, a)) plan_split(a, rows_bca(a), 64, 512);      // one resident workgroup per CU: two waves of workgroups, half the slab traffic
     const ThinPlan tp = thin_plan(q);
     if (tp.ok) { a.atiles = a.btiles = 1; a.nsplit = 4 * tp.nwg; a.chunks_per_split = 0; }      // one slab per wave (conv_wgrad_thin_kernel)
     return SBG_OK;
@@ -731,24 +706,18 @@ extern "C" int sbg_conv2d_wgrad(const sbg_wgrad_params* q, sbg_stream_t stream)
         auto stage_kib = [](int S, int BCA) { const int ppr = (S * 31 + 3 + 7) / 8; return BCA / 16 + 3 * ppr; };
         // Depth of the L2 -> LDS pipeline.  The stream is latency bound (ablation: the loads alone take 350 us on the 128-channel 256^2 layer whatever
         // the tile, with 46 or 76 KB in flight per CU: ~1.3 us per round trip), so the kernel wants as many chunks in flight as LDS holds.
-        static const char* ens = sbg_env("SBG_WGRAD_NSTAGE");
-        int nst = rows_nstage(s_, bca);
-        if (ens && atoi(ens) >= 2 && atoi(ens) <= 6 && (atoi(ens) * stage_kib(s_, bca) + 1) <= 160) nst = atoi(ens);
-        const int lds = (nst * stage_kib(s_, bca) + 1) * 1024;
+        const int lds = (rows_nstage(s_, bca) * stage_kib(s_, bca) + 1) * 1024;
         SbgProfScope prof(s, SBG_K_CONV_WGRAD, 2.0 * (double)a.P * a.Ca * (double)a.Cb * a.ntaps,
                           2.0 * (double)a.P * a.Ca + 2.0 * (double)a.N * a.BH * a.BW * a.Cb + 4.0 * a.ntaps * (double)a.Ca * a.Cb * (a.nsplit > 1 ? a.nsplit : 1),
                           {(int)(a.P > INT32_MAX ? INT32_MAX : a.P), a.Ca, a.Cb, a.ntaps, a.stride, a.nsplit, 1000000 + bca * 1000 + 64});      // 1xxxxxx = rows kernel (profiles/summarize.py joins the launch log with the kernel trace on this)
         const dim3 grid(wgrad_grid(a));
-#define SBG_ROWS_LAUNCH(MFT, SS, BB, NS) do { auto kern = conv_wgrad_rows_kernel<MFT, SS, BB, NS>; \
+#define SBG_ROWS_LAUNCH(MFT, SS, BB) do { auto kern = conv_wgrad_rows_kernel<MFT, SS, BB, rows_nstage(SS, BB)>; \
         if (lds > 64 * 1024 && !SBG_RAISE_LDS_ONCE(kern, lds)) return sbg_fail(SBG_ERR_LAUNCH, "conv2d_wgrad: cannot raise the dynamic LDS limit to %d bytes", lds); \
         SBG_LAUNCH(kern, grid, dim3(512), lds, s, a, ab, bb); } while (0)
-#define SBG_ROWS_NS(MFT, SS, BB) do { switch (nst) { case 2: SBG_ROWS_LAUNCH(MFT, SS, BB, 2); break; case 3: SBG_ROWS_LAUNCH(MFT, SS, BB, 3); break; \
-        case 4: SBG_ROWS_LAUNCH(MFT, SS, BB, 4); break; case 5: SBG_ROWS_LAUNCH(MFT, SS, BB, 5); break; default: SBG_ROWS_LAUNCH(MFT, SS, BB, 6); break; } } while (0)
-        if (s_ == 1 && bca == 64)       { if (bf) SBG_ROWS_NS(bf16_mfma, 1, 64);  else SBG_ROWS_NS(f16_mfma, 1, 64); }
-        else if (s_ == 1)               { if (bf) SBG_ROWS_NS(bf16_mfma, 1, 128); else SBG_ROWS_NS(f16_mfma, 1, 128); }
-        else if (bca == 64)             { if (bf) SBG_ROWS_NS(bf16_mfma, 2, 64);  else SBG_ROWS_NS(f16_mfma, 2, 64); }
-        else                            { if (bf) SBG_ROWS_NS(bf16_mfma, 2, 128); else SBG_ROWS_NS(f16_mfma, 2, 128); }
-#undef SBG_ROWS_NS
+        if (s_ == 1 && bca == 64)       { if (bf) SBG_ROWS_LAUNCH(bf16_mfma, 1, 64);  else SBG_ROWS_LAUNCH(f16_mfma, 1, 64); }
+        else if (s_ == 1)               { if (bf) SBG_ROWS_LAUNCH(bf16_mfma, 1, 128); else SBG_ROWS_LAUNCH(f16_mfma, 1, 128); }
+        else if (bca == 64)             { if (bf) SBG_ROWS_LAUNCH(bf16_mfma, 2, 64);  else SBG_ROWS_LAUNCH(f16_mfma, 2, 64); }
+        else                            { if (bf) SBG_ROWS_LAUNCH(bf16_mfma, 2, 128); else SBG_ROWS_LAUNCH(f16_mfma, 2, 128); }
 #undef SBG_ROWS_LAUNCH
         SBG_HIP_LAUNCH_CHECK();
     } else if (use_big_tile(a.ntaps)) {

@@ -7,7 +7,7 @@ std::string& sbg_err_slot()
     return slot;
 }
 
-extern "C" int sbg_version(void) { return 2; }
+extern "C" int sbg_version(void) { return 3; }
 
 bool sbg_launch_geometry_ok(dim3 grid, dim3 block, size_t lds_bytes, const char* kernel, const char* file, int line)
 {
@@ -21,36 +21,7 @@ bool sbg_launch_geometry_ok(dim3 grid, dim3 block, size_t lds_bytes, const char*
     return ok;
 }
 
-#include <atomic>
-#include <cstdlib>
-#include <cstring>
-#include <map>
-#include <mutex>
-
-const char* sbg_env(const char* name)
-{
-    static std::mutex mu;
-    static std::map<std::string, std::pair<bool, std::string>> seen;
-    std::lock_guard<std::mutex> lk(mu);
-    auto it = seen.find(name);
-    if (it == seen.end()) {
-        const char* v = getenv(name);
-        it = seen.emplace(name, std::make_pair(v != nullptr, std::string(v ? v : ""))).first;
-    }
-    return it->second.first ? it->second.second.c_str() : nullptr;
-}
-
 extern "C" const char* sbg_last_error(void) { return sbg_err_slot().c_str(); }
-
-// Experiment word: kernel variants that are A/B-tested in ONE process (interleaved rounds on one device: scratch/kbench.py) select on its bits.
-// Initial value from SBG_EXPERIMENT; sbg_experiment_set returns the previous value.  Not part of the product's contract.
-static std::atomic<int>& sbg_experiment_word()
-{
-    static std::atomic<int> w{[] { const char* e = getenv("SBG_EXPERIMENT"); return e ? atoi(e) : 0; }()};
-    return w;
-}
-int sbg_experiment() { return sbg_experiment_word().load(std::memory_order_relaxed); }
-extern "C" int sbg_experiment_set(int v) { return sbg_experiment_word().exchange(v); }
 
 // ------------------------------------------------------------------------------------------------
 // Launch timing log.

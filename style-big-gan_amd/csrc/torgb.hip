@@ -299,8 +299,7 @@ extern "C" int sbg_torgb_fwd(const void* x, const float* wmod, const float* bias
     hipStream_t stream = (hipStream_t)stream_;
     SbgProfScope prof(stream, SBG_K_TORGB, 2.0 * N * O * (double)C * HW, (double)N * HW * (2.0 * C + 4.0 * O), {N, C, O, (int)HW, 0, 0, 0});
     dim3 grid((unsigned)(N * a.blocks_per_n)), block(256);
-    static const char* emf = sbg_env("SBG_TORGB_MFMA");          // experiment switch: 0 = the streaming kernel for every shape
-    if ((HW & 15) == 0 && (C == 128 || C == 256) && sbg_aligned16(x) && sbg_aligned16(y) && !(emf && atoi(emf) == 0)) {
+    if ((HW & 15) == 0 && (C == 128 || C == 256) && sbg_aligned16(x) && sbg_aligned16(y)) {
         if (dtype == SBG_BF16) {
             if (C == 128) SBG_LAUNCH((torgb_fwd_mfma_kernel<bf16_s, 4>), grid, block, 0, stream, a);
             else SBG_LAUNCH((torgb_fwd_mfma_kernel<bf16_s, 8>), grid, block, 0, stream, a);

@@ -276,7 +276,7 @@ template <> struct FirMfma<f16_s> {
     static __device__ __forceinline__ float from_bits(unsigned short b) { return f16_bits_to_f32(b); }
 };
 
-template <class T, int RPW>      // RPW = output rows per wave: 2 (8 x 32 tile, 68 KB of LDS, 2 workgroups per CU) or 1 (4 x 32 tile, 43 KB, 3 per CU)
+template <class T, int RPW>      // RPW = output rows per wave; built for 2 (8 x 32 tile, 68 KB of LDS, 2 workgroups per CU; 1 and 4 measured slower: DESIGN.md)
 __global__ __launch_bounds__(256, RPW == 1 ? 3 : (RPW == 2 ? 2 : 1)) void upfirdn2d_fir_mfma_kernel(UpfirdnArgs p, unsigned x_bytes, int tiles_x, int tiles_y, int cblocks)
 {
     constexpr int TY = 4 * RPW, TX = 32, FH = 4, FW = 4;
@@ -705,14 +705,9 @@ enum FirVariant { FIR_V_NONE = 0, FIR_V_SLIDE = 1, FIR_V_TILE = 2, FIR_V_SLIDE_E
 template <class T>
 static int launch_fir_mfma(const UpfirdnArgs& a, hipStream_t stream)
 {
-    static const char* e = sbg_env("SBG_FIR_RPW");        // experiment switch: tile kernels (1 = 4 x 32 tiles, 2 = 8 x 32, 4 = 16 x 32) instead of the sliding window
-    if (a.tail == 2) return (a.outH >= 16 && launch_fir_slide<T>(a, stream)) ? FIR_V_SLIDE : FIR_V_NONE;      // the backward tail exists in the sliding-window kernel only
-    if (!e && a.outH >= 16) return launch_fir_slide<T>(a, stream) ? FIR_V_SLIDE : FIR_V_NONE;
-    bool ok;
-    if (e && atoi(e) == 1)      ok = launch_fir_mfma_rpw<T, 1>(a, stream);
-    else if (e && atoi(e) == 4) ok = launch_fir_mfma_rpw<T, 4>(a, stream);
-    else                        ok = launch_fir_mfma_rpw<T, 2>(a, stream);
-    return ok ? FIR_V_TILE : FIR_V_NONE;
+    if (a.outH >= 16) return launch_fir_slide<T>(a, stream) ? FIR_V_SLIDE : FIR_V_NONE;
+    if (a.tail == 2) return FIR_V_NONE;      // the backward tail exists in the sliding-window kernel only
+    return launch_fir_mfma_rpw<T, 2>(a, stream) ? FIR_V_TILE : FIR_V_NONE;
 }
 
 template <class T> static int try_fir_mfma(const UpfirdnArgs& a, hipStream_t stream) { return launch_fir_mfma<T>(a, stream); }
@@ -727,14 +722,13 @@ static int launch_upfirdn(const UpfirdnArgs& a0, bool vec8, bool exact16, hipStr
                       es * ((double)a.N * a.C * a.inH * a.inW + (double)a.N * a.C * a.outH * a.outW),
                       {a.N, a.C, a.inH, a.inW, a.outH, a.outW, a.upx * 16 + a.downx});      // dims[6] gains the variant digit below
     const bool mfma_ok = vec8 && exact16 && sizeof(T) == 2 && a.upx == 1 && a.upy == 1 && a.downx == 1 && a.downy == 1 && a.fw == 4 && a.fh == 4 && (a.C % 64) == 0
-                         && a.outW >= 16 && a.outH >= 8 && sbg_env("SBG_FIR_NO_MFMA") == nullptr;
+                         && a.outW >= 16 && a.outH >= 8;
     // A few columns beyond a multiple of the 32-column strips (the 2 res + 1 wide outputs of the discriminator's low-pass in front of a strided
     // convolution: 257 = 8 strips + 1) would cost a whole strip of matrix-core work (9 strips for 257 columns: 11 % idle, 33 columns: 48 %): the
     // strips take the multiple of 32 and the register-blocked kernel the remaining columns, as a launch over the shifted sub-rectangle.
     const int rem = a.outW % 32;
-    static const char* no_edge = sbg_env("SBG_FIR_NO_EDGE");
     const int code = a.upx * 16 + a.downx;
-    if (mfma_ok && !a.tail && !no_edge && rem >= 1 && rem <= 4 && a.outW > 32) {
+    if (mfma_ok && !a.tail && rem >= 1 && rem <= 4 && a.outW > 32) {
         UpfirdnArgs m = a, e = a;
         m.outW = a.outW - rem;
         e.outW = rem; e.padx0 = a.padx0 - m.outW; e.y = (void*)((T*)a.y + (int64_t)m.outW * a.osx);
@@ -784,13 +778,13 @@ extern "C" int sbg_upfirdn2d_tail_supported(const sbg_upfirdn2d_params* q)
     const int C = q->inSize[2];
     return (q->dtype == SBG_BF16 || q->dtype == SBG_F16) && q->filter_exact16 && q->upx == 1 && q->upy == 1 && q->downx == 1 && q->downy == 1
            && q->filterSize[0] == 4 && q->filterSize[1] == 4 && (C % 64) == 0 && q->outSize[0] >= 16 && q->outSize[1] >= 8
-           && q->inStride[2] == 1 && q->outStride[2] == 1 && sbg_env("SBG_FIR_NO_MFMA") == nullptr;
+           && q->inStride[2] == 1 && q->outStride[2] == 1;
 }
 
 // Rows of `dact_partial` (= workgroups of the sliding-window launch) for a launch with a backward tail, or -1 when that kernel does not take it.
 extern "C" int64_t sbg_upfirdn2d_dact_rows(const sbg_upfirdn2d_params* q)
 {
-    if (!q || !sbg_upfirdn2d_tail_supported(q) || q->outSize[1] < 16 || sbg_env("SBG_FIR_RPW") != nullptr) return -1;
+    if (!q || !sbg_upfirdn2d_tail_supported(q) || q->outSize[1] < 16) return -1;
     if (q->inStride[0] < 0 || q->inStride[1] < 0 || q->inStride[3] < 0) return -1;
     const int64_t x_bytes = 2 * ((int64_t)(q->inSize[3] - 1) * q->inStride[3] + (int64_t)(q->inSize[1] - 1) * q->inStride[1] + (int64_t)(q->inSize[0] - 1) * q->inStride[0] + q->inSize[2]);
     if (x_bytes >= (int64_t)SBG_FIR_OOB) return -1;

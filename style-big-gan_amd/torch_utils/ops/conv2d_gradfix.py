@@ -10,7 +10,7 @@ implicit-GEMM kernels ``sbg_conv2d_igemm`` / ``sbg_conv2d_wgrad`` (csrc/conv_ige
 Layout / precision: activations are processed channel-minor (``torch.channels_last``; other layouts are converted),
 bf16 / f16 tensors take one MFMA pass with fp32 accumulation; fp32 tensors are split into three bf16 parts (hi + mid + lo =
 24 mantissa bits) and take six MFMA passes accumulated in fp32 (every product term above 2^-24; still ~2.7x the throughput of
-the fp32-input MFMA, which runs at 1/16 of the bf16 rate on gfx950).  ``fp32_mfma_passes = 3`` selects a cheaper hi/lo split.
+the fp32-input MFMA, which runs at 1/16 of the bf16 rate on gfx950).
 """
 import contextlib
 
@@ -24,8 +24,6 @@ from ... import _lib
 
 enabled = False                     # kept for API parity; the HIP path is always used on a ROCm device
 weight_gradients_disabled = False   # forcefully disable computation of gradients with respect to the weights
-import os as _os0
-fp32_mfma_passes = int(_os0.environ.get('SBG_FP32_PASSES', '6'))     # fp32 tensors: 6 = bf16 hi/mid/lo split (~fp32 accuracy), 3 = hi/lo split (rel. error ~1e-5 per product); experiment switch
 
 
 @contextlib.contextmanager
@@ -79,13 +77,9 @@ def _operand_passes(a, b):
     if a.dtype in (torch.bfloat16, torch.float16):
         return [(a, b)]
     if a.dtype == torch.float32:
-        if fp32_mfma_passes >= 6:
-            a0, a1, a2 = _split_bf16(a, 3)
-            b0, b1, b2 = _split_bf16(b, 3)
-            return [(a2, b0), (a0, b2), (a1, b1), (a1, b0), (a0, b1), (a0, b0)]
-        a0, a1 = _split_bf16(a, 2)
-        b0, b1 = _split_bf16(b, 2)
-        return [(a1, b0), (a0, b1), (a0, b0)]
+        a0, a1, a2 = _split_bf16(a, 3)
+        b0, b1, b2 = _split_bf16(b, 3)
+        return [(a2, b0), (a0, b2), (a1, b1), (a1, b0), (a0, b1), (a0, b0)]
     raise RuntimeError(f"conv2d: unsupported dtype {a.dtype}")
 
 
@@ -115,9 +109,8 @@ class Epilogue:
         p.act, p.alpha, p.gain, p.clamp = self.act, self.alpha, self.gain, self.clamp
 
 
-import os as _os
-_KSPLIT_MAX_TILES = int(_os.environ.get('SBG_KSPLIT_MAX_TILES', '128'))     # experiment switches for the K split of few-tile launches
-_KSPLIT_TARGET = int(_os.environ.get('SBG_KSPLIT_TARGET', '256'))
+_KSPLIT_MAX_TILES = 128    # K split: a launch of fewer output tiles than this ...
+_KSPLIT_TARGET = 256       # ... spreads its reduction over about this many workgroups
 
 # fp32 operands up to this many elements run as ONE launch over the concatenated hi / mid / lo parts (each operand built by one pass of
 # sbg_split_bf16_cat: 4 B read + 12 B written per element).  The alternative -- six launches that read-modify-write the fp32 output five times,
@@ -128,7 +121,6 @@ CONCAT_NUMEL = 1 << 28
 
 
 _ORDER6 = ((2, 0, 1, 1, 0, 0), (0, 2, 1, 0, 1, 0))      # part indices of (a, b) in the six products of _operand_passes, smallest terms first
-_ORDER3 = ((1, 0, 0), (0, 1, 0))
 
 
 def _split_cat(t, dim, order, dense=False):
@@ -162,8 +154,7 @@ def _mfma_operands(a, b, a_cat_dim, b_cat_dim, b_dense=False):
     """[(a_k, b_k)]: the matrix-core launches whose sum is the product of a and b (see _operand_passes); small fp32 operands become ONE launch
     over concatenated hi / mid / lo parts, each operand built by one kernel (`b_dense`: b is a weight view wanted contiguous)"""
     if (a.dtype == torch.float32 and b.dtype == torch.float32 and a.device.type == "cuda" and a.numel() <= CONCAT_NUMEL and a.numel() > 0 and b.numel() > 0):
-        oa, ob = _ORDER6 if fp32_mfma_passes >= 6 else _ORDER3
-        return [(_split_cat(a, a_cat_dim, oa), _split_cat(b, b_cat_dim, ob, dense=b_dense))]
+        return [(_split_cat(a, a_cat_dim, _ORDER6[0]), _split_cat(b, b_cat_dim, _ORDER6[1], dense=b_dense))]
     return _fold_passes(_operand_passes(a, b), a_cat_dim, b_cat_dim)
 
 
