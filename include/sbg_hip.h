@@ -386,6 +386,30 @@ int sbg_filter1d_batch(const float* x, const float* taps, float* y, int M, int H
                        int planes_per_filter, int flip, sbg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Perceptual path length sampler arithmetic (metrics/perceptual_path_length.py of the reference), all fp32, dense rows.
+ * Each writes the [2B, ...] synthesis / detector batch in one launch: rows 0..B-1 at t[b], rows B..2B-1 at t[b] + eps (fp32 add).
+ *   sbg_ppl_slerp_endpoints: out[r] = slerp(z0[b], z1[b], t_r) for z0, z1 [B, D] -- `slerp` (:23-32): both inputs normalised, the
+ *                            angle from acos of their dot product, the orthogonalised second axis normalised, the result renormalised;
+ *                            one wave per row, every norm and dot product a wave reduction.  Replaces `slerp(z0, z1, t)` and
+ *                            `slerp(z0, z1, t + eps)` (:64-65) and their `torch.cat`.
+ *   sbg_ppl_lerp_endpoints:  out[r] = torch.lerp(w0[b], w1[b], t_r) over [B, L = num_ws * w_dim] with torch's two-branch formula
+ *                            (|weight| < 0.5 ? s + w (e - s) : e - (e - s)(1 - w)) -- `w0.lerp(w1, t)` / `w0.lerp(w1, t + eps)` (:59-60). */
+int sbg_ppl_slerp_endpoints(const float* z0, const float* z1, const float* t, float eps, float* out, int B, int D, sbg_stream_t stream);
+int sbg_ppl_lerp_endpoints(const float* w0, const float* w1, const float* t, float eps, float* out, int B, int64_t L, sbg_stream_t stream);
+/* Synthesis output -> detector input (:77-89): img fp32 [N, C, H, W] with element strides (any memory format) -> out fp32 dense
+ * [N, C == 1 ? 3 : C, S, S]: the optional centre crop (rows [3c, 7c), columns [2c, 6c), c = H / 8; needs H == W), the area mean over
+ * factor x factor boxes (`reshape(...).mean([3, 5])`, skipped for factor 1), then (x + 1) * 127.5 and the grey -> RGB repeat.
+ * Mean and scale round separately, in the reference's order.  The window must split into whole boxes. */
+int sbg_ppl_prep_images(const float* img, float* out, int N, int C, int H, int W, int64_t sn, int64_t sc, int64_t sh, int64_t sw,
+                        int crop, int factor, sbg_stream_t stream);
+/* Differential LPIPS distance (:92-93, `(lpips_t0 - lpips_t1).square().sum(1) / epsilon ** 2`): feats fp32 [2B, F] dense ->
+ * dist[b] = (sum_f (feats[b, f] - feats[B + b, f])^2) / eps2, eps2 = the fp32 value of epsilon^2, one division at the end.
+ * Two launches: per-(row, chunk) partial sums into `workspace` (sbg_ppl_dist_workspace(B, F) bytes), then a fixed-order sum per
+ * row.  No float atomics: the result is the same on every run. */
+int64_t sbg_ppl_dist_workspace(int B, int64_t F);
+int sbg_ppl_dist(const float* feats, float* dist, void* workspace, int B, int64_t F, float eps2, sbg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * In-process launch timing (measurement only; bench.py's roofline figures come from here).
  * While enabled, every kernel launch of this library is bracketed by two hipEvents recorded on the launch stream
  * and logged with its algorithmic flops / bytes.  sbg_prof_fetch() synchronises the logged events, writes up to `max`
@@ -394,7 +418,7 @@ int sbg_filter1d_batch(const float* x, const float* taps, float* y, int M, int H
 enum sbg_kernel_kind {
     SBG_K_BIAS_ACT = 1, SBG_K_UPFIRDN2D = 2, SBG_K_CONV_IGEMM = 3, SBG_K_CONV_WGRAD = 4, SBG_K_WGRAD_REDUCE = 5,
     SBG_K_SCALE_NC = 6, SBG_K_DOT_HW = 7, SBG_K_SN_POWER = 9, SBG_K_ATTENTION = 10, SBG_K_GRID_SAMPLE = 11, SBG_K_FILTER1D = 12, SBG_K_COLOR = 13, SBG_K_WEIGHT_PREP = 14, SBG_K_TORGB = 15, SBG_K_FROMRGB = 16,
-    SBG_K_GROUPED_GEMM = 17
+    SBG_K_GROUPED_GEMM = 17, SBG_K_PPL = 18     /* SBG_K_PPL: dims[0] = variant: 0 slerp / 1 lerp endpoints, 2 image prep, 3 distance */
 };
 typedef struct sbg_prof_record {
     int    kind;            /* enum sbg_kernel_kind */

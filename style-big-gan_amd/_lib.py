@@ -104,7 +104,8 @@ class ProfRecord(ctypes.Structure):
 
 
 KERNEL_KINDS = {1: "bias_act", 2: "upfirdn2d", 3: "conv_igemm", 4: "conv_wgrad", 5: "wgrad_reduce", 6: "scale_nc", 7: "dot_hw", 9: "sn_power", 10: "attention",
-                11: "grid_sample", 12: "filter1d", 13: "color", 14: "weight_prep", 15: "torgb", 16: "fromrgb", 17: "grouped_gemm"}
+                11: "grid_sample", 12: "filter1d", 13: "color", 14: "weight_prep", 15: "torgb", 16: "fromrgb", 17: "grouped_gemm", 18: "ppl"}
+PPL_VARIANTS = {0: "slerp", 1: "lerp", 2: "prep", 3: "dist"}        # dims[0] of a "ppl" launch record
 
 _lib = None
 _lock = threading.Lock()
@@ -167,6 +168,11 @@ SYMBOLS = [
     ("sbg_grid_sample2d_bwd_overwrites", _c.c_int, [_c.POINTER(GridSampleParams)]),
     ("sbg_color_transform", _c.c_int, [_c.c_void_p] * 3 + [_c.c_int, _c.c_int64, _c.c_void_p]),
     ("sbg_filter1d_batch", _c.c_int, [_c.c_void_p] * 3 + [_c.c_int] * 8 + [_c.c_void_p]),
+    ("sbg_ppl_slerp_endpoints", _c.c_int, [_c.c_void_p] * 3 + [_c.c_float, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p]),
+    ("sbg_ppl_lerp_endpoints", _c.c_int, [_c.c_void_p] * 3 + [_c.c_float, _c.c_void_p, _c.c_int, _c.c_int64, _c.c_void_p]),
+    ("sbg_ppl_prep_images", _c.c_int, [_c.c_void_p] * 2 + [_c.c_int] * 4 + [_c.c_int64] * 4 + [_c.c_int, _c.c_int, _c.c_void_p]),
+    ("sbg_ppl_dist_workspace", _c.c_int64, [_c.c_int, _c.c_int64]),
+    ("sbg_ppl_dist", _c.c_int, [_c.c_void_p] * 3 + [_c.c_int, _c.c_int64, _c.c_float, _c.c_void_p]),
     ("sbg_prof_enable", _c.c_int, [_c.c_int]),
     ("sbg_prof_fetch", _c.c_int, [_c.POINTER(ProfRecord), _c.c_int]),
 ]

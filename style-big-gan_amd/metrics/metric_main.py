@@ -1,8 +1,8 @@
 """Metric registry and reporting.  Interface of the reference's ``stylegan2ada/metrics/metric_main.py``: ``register_metric``,
 ``is_valid_metric``, ``list_valid_metrics``, ``calc_metric(metric, dataset_name, **MetricOptions kwargs)`` (:39-61: compute, broadcast
 rank 0's numbers, wrap with timing metadata) and ``report_metric(result_dict, run_dir, snapshot_pkl)`` (:65-76: one JSON line to stdout
-and to ``metric-<name>.jsonl``).  Metric names and their sample counts are the reference's (:81-150); the perceptual-path-length family
-needs an LPIPS network and is not registered."""
+and to ``metric-<name>.jsonl``).  Metric names and their sample counts are the reference's (:81-150), the perceptual-path-length family
+(:101, :133-150) included: its LPIPS network is the local ``vgg16.pt`` detector (or a callable stand-in), see perceptual_path_length.py."""
 import json
 import os
 import time
@@ -10,7 +10,7 @@ import time
 import torch
 
 from ..utils import EasyDict
-from . import metric_utils, scores
+from . import metric_utils, perceptual_path_length, scores
 
 _metric_dict = dict()       # name -> fn(opts, dataset_name)
 
@@ -106,3 +106,34 @@ def pr50k3(opts, dataset_name='image_folder'):
     _full_dataset(opts, keep_flips=True)
     precision, recall = scores.compute_pr(opts, dataset_name=dataset_name, max_real=50000, num_gen=50000, nhood_size=3, row_batch_size=10000, col_batch_size=10000)
     return dict(pr50k3_precision=precision, pr50k3_recall=recall)
+
+
+# -- perceptual path length (reference :101, :133-150): 50k samples, epsilon 1e-4, pairs in batches of 2
+def _ppl(opts, dataset_name, space, sampling, crop):
+    return perceptual_path_length.compute_ppl(opts, num_samples=50000, epsilon=1e-4, space=space, sampling=sampling, crop=crop, batch_size=2,
+                                              dataset_name=dataset_name)
+
+
+@register_metric
+def ppl2_wend(opts, dataset_name='image_folder'):
+    return dict(ppl2_wend=_ppl(opts, dataset_name, space='w', sampling='end', crop=False))
+
+
+@register_metric
+def ppl_zfull(opts, dataset_name='image_folder'):
+    return dict(ppl_zfull=_ppl(opts, dataset_name, space='z', sampling='full', crop=True))
+
+
+@register_metric
+def ppl_wfull(opts, dataset_name='image_folder'):
+    return dict(ppl_wfull=_ppl(opts, dataset_name, space='w', sampling='full', crop=True))
+
+
+@register_metric
+def ppl_zend(opts, dataset_name='image_folder'):
+    return dict(ppl_zend=_ppl(opts, dataset_name, space='z', sampling='end', crop=True))
+
+
+@register_metric
+def ppl_wend(opts, dataset_name='image_folder'):
+    return dict(ppl_wend=_ppl(opts, dataset_name, space='w', sampling='end', crop=True))

@@ -436,7 +436,26 @@ class BaseTrainer:
             import warnings
             warnings.warn(f"log.metrics={self.metrics} ignored: data.dataset=synthetic has no data set to score against")
             self.metrics = []
+        self._check_ppl_metrics(gen.generator)
         return self
+
+    def _check_ppl_metrics(self, generator):
+        """the perceptual-path-length metrics need the VGG16 LPIPS detector and a generator with `mapping` / `synthesis` (reference
+        perceptual_path_length.py:57-70): refuse at setup what would fail at the first snapshot"""
+        ppl = [m for m in self.metrics if m.startswith(("ppl_", "ppl2_"))]
+        if not ppl:
+            return
+        from ..metrics import metric_utils, perceptual_path_length
+        det = self.metric_detector
+        if os.path.isdir(det):
+            if not os.path.isfile(os.path.join(det, perceptual_path_length.VGG16)):
+                raise ValueError(f"log.metrics={ppl} needs the LPIPS detector {perceptual_path_length.VGG16}: log.metric_detector={det} does not hold it")
+        elif metric_utils.get_feature_detector_name(det) != metric_utils.get_feature_detector_name(perceptual_path_length.VGG16):
+            raise ValueError(f"log.metrics={ppl} needs the LPIPS detector {perceptual_path_length.VGG16}; log.metric_detector={det} is another "
+                             "detector (pass a directory holding vgg16.pt)")
+        from .generators import Generator
+        if not issubclass(generators[generator], Generator):
+            raise ValueError(f"log.metrics={ppl} needs a generator with mapping and synthesis networks; gen.generator={generator} has neither")
 
     @staticmethod
     def _augment_arguments(config):
