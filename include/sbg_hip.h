@@ -410,6 +410,30 @@ int64_t sbg_ppl_dist_workspace(int B, int64_t F);
 int sbg_ppl_dist(const float* feats, float* dist, void* workspace, int B, int64_t F, float eps2, sbg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Latent projector arithmetic (stylegan2ada/projector.py of the reference, `project()` :25-131), all fp32.  No float atomics; every
+ * sum has a fixed order, so two runs on the same inputs give the same bits.  No allocation or synchronisation inside: workspaces
+ * come from the caller (sizes from the *_workspace queries, -1 for an unsupported input).
+ * The noise entries take the whole set of noise buffers as a host table: bufs[b] -> dense, 16-byte aligned fp32 [res[b], res[b]],
+ * res[b] a power of two in [4, 1024], 1 <= nbuf <= 32; any other set is an error.  Levels of a buffer: level 0 is the buffer, level
+ * k + 1 = avg_pool2d(level k, 2), down to the first side <= 8 (the reference's loop, :104-113).
+ *   sbg_proj_noise_reg:      means[2l], means[2l + 1] = mean(P * roll(P, 1, W)), mean(P * roll(P, 1, H)) of level l of the flat
+ *                            (buffer, level) list; reg[0] = sum of every mean^2 in that order.  The pooled levels stay in
+ *                            `workspace` for the backward.  3 launches.
+ *   sbg_proj_noise_reg_bwd:  grads[b] = g[0] * sum_k G_k[y >> k, x >> k] / 4^k with G_k[i, j] = 2 (m_x (P[i, j-1] + P[i, j+1]) +
+ *                            m_y (P[i-1, j] + P[i+1, j])) / n^2 (indices wrap); reads the forward's means and workspace.  1 launch.
+ *   sbg_proj_noise_normalize: in place, buf -= mean(buf); buf *= rsqrt(mean(buf^2)) (:125-129).  2 launches.
+ * sbg_proj_sqdist: dist[0] = sum_f (t[f] - s[f])^2 (the LPIPS term, :98), two stages.  sbg_proj_sqdist_bwd: ds = 2 g[0] (s - t). */
+int64_t sbg_proj_noise_reg_workspace(const int* res, int nbuf);
+int sbg_proj_noise_reg(const float* const* bufs, const int* res, int nbuf, float* means, float* reg, void* workspace, sbg_stream_t stream);
+int sbg_proj_noise_reg_bwd(const float* const* bufs, float* const* grads, const int* res, int nbuf, const float* means, const float* g,
+                           const void* workspace, sbg_stream_t stream);
+int64_t sbg_proj_noise_normalize_workspace(const int* res, int nbuf);
+int sbg_proj_noise_normalize(float* const* bufs, const int* res, int nbuf, void* workspace, sbg_stream_t stream);
+int64_t sbg_proj_sqdist_workspace(int64_t F);
+int sbg_proj_sqdist(const float* t, const float* s, float* dist, void* workspace, int64_t F, sbg_stream_t stream);
+int sbg_proj_sqdist_bwd(const float* t, const float* s, const float* g, float* ds, int64_t F, sbg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * In-process launch timing (measurement only; bench.py's roofline figures come from here).
  * While enabled, every kernel launch of this library is bracketed by two hipEvents recorded on the launch stream
  * and logged with its algorithmic flops / bytes.  sbg_prof_fetch() synchronises the logged events, writes up to `max`
@@ -418,7 +442,8 @@ int sbg_ppl_dist(const float* feats, float* dist, void* workspace, int B, int64_
 enum sbg_kernel_kind {
     SBG_K_BIAS_ACT = 1, SBG_K_UPFIRDN2D = 2, SBG_K_CONV_IGEMM = 3, SBG_K_CONV_WGRAD = 4, SBG_K_WGRAD_REDUCE = 5,
     SBG_K_SCALE_NC = 6, SBG_K_DOT_HW = 7, SBG_K_SN_POWER = 9, SBG_K_ATTENTION = 10, SBG_K_GRID_SAMPLE = 11, SBG_K_FILTER1D = 12, SBG_K_COLOR = 13, SBG_K_WEIGHT_PREP = 14, SBG_K_TORGB = 15, SBG_K_FROMRGB = 16,
-    SBG_K_GROUPED_GEMM = 17, SBG_K_PPL = 18     /* SBG_K_PPL: dims[0] = variant: 0 slerp / 1 lerp endpoints, 2 image prep, 3 distance */
+    SBG_K_GROUPED_GEMM = 17, SBG_K_PPL = 18,    /* SBG_K_PPL: dims[0] = variant: 0 slerp / 1 lerp endpoints, 2 image prep, 3 distance */
+    SBG_K_PROJECTOR = 19        /* one record per launch; dims[0] = variant: 0 reg / 1 reg_bwd / 2 normalize / 3 sqdist / 4 sqdist_bwd, dims[1] = stage */
 };
 typedef struct sbg_prof_record {
     int    kind;            /* enum sbg_kernel_kind */

@@ -104,8 +104,10 @@ class ProfRecord(ctypes.Structure):
 
 
 KERNEL_KINDS = {1: "bias_act", 2: "upfirdn2d", 3: "conv_igemm", 4: "conv_wgrad", 5: "wgrad_reduce", 6: "scale_nc", 7: "dot_hw", 9: "sn_power", 10: "attention",
-                11: "grid_sample", 12: "filter1d", 13: "color", 14: "weight_prep", 15: "torgb", 16: "fromrgb", 17: "grouped_gemm", 18: "ppl"}
+                11: "grid_sample", 12: "filter1d", 13: "color", 14: "weight_prep", 15: "torgb", 16: "fromrgb", 17: "grouped_gemm", 18: "ppl",
+                19: "projector"}
 PPL_VARIANTS = {0: "slerp", 1: "lerp", 2: "prep", 3: "dist"}        # dims[0] of a "ppl" launch record
+PROJ_VARIANTS = {0: "reg", 1: "reg_bwd", 2: "normalize", 3: "sqdist", 4: "sqdist_bwd"}      # dims[0] of a "projector" launch record
 
 _lib = None
 _lock = threading.Lock()
@@ -173,6 +175,14 @@ SYMBOLS = [
     ("sbg_ppl_prep_images", _c.c_int, [_c.c_void_p] * 2 + [_c.c_int] * 4 + [_c.c_int64] * 4 + [_c.c_int, _c.c_int, _c.c_void_p]),
     ("sbg_ppl_dist_workspace", _c.c_int64, [_c.c_int, _c.c_int64]),
     ("sbg_ppl_dist", _c.c_int, [_c.c_void_p] * 3 + [_c.c_int, _c.c_int64, _c.c_float, _c.c_void_p]),
+    ("sbg_proj_noise_reg_workspace", _c.c_int64, [_c.c_void_p, _c.c_int]),
+    ("sbg_proj_noise_reg", _c.c_int, [_c.c_void_p] * 2 + [_c.c_int] + [_c.c_void_p] * 4),
+    ("sbg_proj_noise_reg_bwd", _c.c_int, [_c.c_void_p] * 3 + [_c.c_int] + [_c.c_void_p] * 4),
+    ("sbg_proj_noise_normalize_workspace", _c.c_int64, [_c.c_void_p, _c.c_int]),
+    ("sbg_proj_noise_normalize", _c.c_int, [_c.c_void_p] * 2 + [_c.c_int] + [_c.c_void_p] * 2),
+    ("sbg_proj_sqdist_workspace", _c.c_int64, [_c.c_int64]),
+    ("sbg_proj_sqdist", _c.c_int, [_c.c_void_p] * 4 + [_c.c_int64, _c.c_void_p]),
+    ("sbg_proj_sqdist_bwd", _c.c_int, [_c.c_void_p] * 4 + [_c.c_int64, _c.c_void_p]),
     ("sbg_prof_enable", _c.c_int, [_c.c_int]),
     ("sbg_prof_fetch", _c.c_int, [_c.POINTER(ProfRecord), _c.c_int]),
 ]
