@@ -445,6 +445,14 @@ enum sbg_kernel_kind {
     SBG_K_GROUPED_GEMM = 17, SBG_K_PPL = 18,    /* SBG_K_PPL: dims[0] = variant: 0 slerp / 1 lerp endpoints, 2 image prep, 3 distance */
     SBG_K_PROJECTOR = 19        /* one record per launch; dims[0] = variant: 0 reg / 1 reg_bwd / 2 normalize / 3 sqdist / 4 sqdist_bwd, dims[1] = stage */
 };
+/* Kernel-variant codes in the records of the streaming kernels (which kernel served the launch):
+ *   bias_act     dims[4] = 1 vec8 / 2 scalar,  dims[5] = bias mode (0 none, 1 channel-minor vector, 2 one per 8-vector, 3 generic)
+ *   scale_nc     dims[4] = 1 vec8 / 2 scalar
+ *   dot_hw       dims[4] = 1 generic / 2 lane per channel vector / 3 serial channel vectors,  dims[5] = pixel splits
+ *                (dims[3] = layout, 3 dot_hw_scale, 2 modconv_bwd, 4 modconv_bwd_prescaled, 5 moments_hw: dims[4] = 1 vec8 / 2 scalar)
+ *   weight_prep  pack (dims[3] = 0): dims[4] = 1 transposing LDS tiles / 2 one lane per (row, column)
+ *   torgb        forward (dims[4] = 0): dims[5] = 1 matrix cores / 2 streaming, 3 outputs / 3 streaming, 4 outputs
+ *   fromrgb      backward (dims[4] = 1): dims[5] = image channels unrolled (3, or 4 for any), dims[6] = 1 with the image gradient */
 typedef struct sbg_prof_record {
     int    kind;            /* enum sbg_kernel_kind */
     int    dims[7];         /* kernel specific shape key (see each kernel's source) */

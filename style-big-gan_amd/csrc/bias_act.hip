@@ -141,7 +141,7 @@ static int launch_bias_act(const BiasActArgs& p, bool vec, hipStream_t stream)
 {
     const int es = sizeof(T) == 4 ? 4 : 2;
     const int streams = 2 + (p.xref ? 1 : 0) + (p.yref ? 1 : 0) + (p.dy ? 1 : 0);
-    SbgProfScope prof(stream, SBG_K_BIAS_ACT, 0.0, (double)p.sizeX * es * streams, {(int)p.sizeX, p.grad, A, es});
+    SbgProfScope prof(stream, SBG_K_BIAS_ACT, 0.0, (double)p.sizeX * es * streams, {(int)p.sizeX, p.grad, A, es, vec ? 1 : 2, p.bmode});
     if (vec) {
         unsigned grid = sbg_stream_grid((p.sizeX >> 3) + 1, 256);
         SBG_LAUNCH((bias_act_vec8<T, A>), dim3(grid), dim3(256), 0, stream, p);

@@ -112,16 +112,15 @@ __global__ void __launch_bounds__(256) fromrgb_bwd_kernel(FromArgs p)
 #pragma unroll
         for (int c = 0; c < MAX_CI; c++) dw[c][j] = 0.0f;
     }
-    // the saved output is 16-bit: a value clamped to +-clamp was stored as round(clamp), so the rail test uses the rounded bound
-    float clamp_r = p.clamp;
-    if (p.clamp >= 0.0f) { T tmp; Elem<T>::st(&tmp, p.clamp); clamp_r = Elem<T>::ld(&tmp); }
+    // the rail test compares the saved 16-bit output with the fp32 clamp, as the reference does (bias_act.cu:141): where round(clamp) < clamp
+    // the clamped elements pass their gradient, where round(clamp) > clamp a value between the two does not
     const float* ib = p.img + (int64_t)n * p.Ci * p.HW;
     const T* dyb = (const T*)p.dy + (int64_t)n * p.HW * p.Co;
     const T* ysb = (const T*)p.ysaved + (int64_t)n * p.HW * p.Co;
     float* dib = DIMG ? p.dimg + (int64_t)n * p.Ci * p.HW : nullptr;
     // slope of clamp(act(x) * gain) on either side of zero (piecewise linear activations; bias_act.cu:141 conventions), zero on the rails
     const float gpos = p.gain, gneg = p.act == SBG_ACT_LRELU ? p.gain * p.alpha : (p.act == SBG_ACT_RELU ? 0.0f : p.gain);
-    const float rail = p.clamp >= 0.0f ? clamp_r : __builtin_inff();
+    const float rail = p.clamp >= 0.0f ? p.clamp : __builtin_inff();
     for (int64_t chunk = (int64_t)blk * 256; chunk < p.HW; chunk += (int64_t)p.blocks_per_n * 256) {
         {
             const int64_t pix = chunk + threadIdx.x;
@@ -251,7 +250,7 @@ extern "C" int sbg_fromrgb_bwd(const float* img, const float* w, const void* dy,
     a.N = N; a.Ci = Ci; a.Co = Co; a.HW = HW; a.act = act; a.alpha = alpha; a.gain = gain; a.clamp = clamp;
     a.blocks_per_n = blocks_for(N, HW);
     hipStream_t stream = (hipStream_t)stream_;
-    SbgProfScope prof(stream, SBG_K_FROMRGB, 4.0 * N * Co * (double)Ci * HW, (double)N * HW * (4.0 * Co + 8.0 * Ci), {N, Ci, Co, (int)HW, 1, 0, 0});
+    SbgProfScope prof(stream, SBG_K_FROMRGB, 4.0 * N * Co * (double)Ci * HW, (double)N * HW * (4.0 * Co + 8.0 * Ci), {N, Ci, Co, (int)HW, 1, Ci == 3 ? 3 : MAX_CI, dimg ? 1 : 0});
     dim3 grid((unsigned)(N * a.blocks_per_n)), block(256);
     const int lds = 4 * (Co >> 3) * (MAX_CI * 8 + 8 + 1) * (int)sizeof(float);      // <= 42 KB (Co = 512)
 #define SBG_FROMRGB_BWD(T_) do { \

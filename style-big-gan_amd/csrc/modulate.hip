@@ -259,12 +259,16 @@ __global__ __launch_bounds__(256) void modconv_bwd_kernel(ModBwdArgs p)
 
 static bool dot_fast(int layout, int C) { return layout == 1 && (C % 8) == 0; }
 
+// launch-record code of the dot_hw_cminor8 form a channel count takes (DOT_FORM_*: dims[4] of a dot_hw record, dims[5] = pixel splits)
+enum { DOT_FORM_GENERIC = 1, DOT_FORM_LANE_VEC = 2, DOT_FORM_SERIAL = 3 };
+static int dot_cminor8_form(int C) { const int cv = C >> 3; return (cv <= 256 && (256 % cv) == 0) ? DOT_FORM_LANE_VEC : DOT_FORM_SERIAL; }
+
 template <class T>
 static int run_scale(const ScaleArgs& a0, int layout, bool vec, hipStream_t s)
 {
     ScaleArgs a = a0;
     const double es = sizeof(T) == 4 ? 4 : 2;
-    SbgProfScope prof(s, SBG_K_SCALE_NC, 0.0, 2.0 * es * a.N * (double)a.C * a.HW, {a.N, a.C, (int)a.HW, layout});
+    SbgProfScope prof(s, SBG_K_SCALE_NC, 0.0, 2.0 * es * a.N * (double)a.C * a.HW, {a.N, a.C, (int)a.HW, layout, vec ? 1 : 2});
     if (vec) {
         a.total = (int64_t)a.N * a.HW * (a.C >> 3);
         SBG_LAUNCH((scale_nc_cminor8<T>), dim3(sbg_stream_grid(a.total, 256)), dim3(256), 0, s, a);
@@ -280,7 +284,7 @@ template <class T>
 static int run_dot(const DotArgs& a, int layout, bool fast, hipStream_t s)
 {
     const double es = sizeof(T) == 4 ? 4 : 2;
-    SbgProfScope prof(s, SBG_K_DOT_HW, 0.0, (a.v ? 2.0 : 1.0) * es * a.N * (double)a.C * a.HW, {a.N, a.C, (int)a.HW, layout});
+    SbgProfScope prof(s, SBG_K_DOT_HW, 0.0, (a.v ? 2.0 : 1.0) * es * a.N * (double)a.C * a.HW, {a.N, a.C, (int)a.HW, layout, fast ? dot_cminor8_form(a.C) : DOT_FORM_GENERIC, a.nsplit});
     if (fast) SBG_LAUNCH((dot_hw_cminor8<T>), dim3(a.N, a.nsplit), dim3(256), 0, s, a);
     else      SBG_LAUNCH((dot_hw_generic<T>), dim3((unsigned)((int64_t)a.N * a.C)), dim3(256), 0, s, a, layout);
     SBG_HIP_LAUNCH_CHECK();
@@ -391,6 +395,7 @@ extern "C" int sbg_moments_hw(const void* x, float* r, int dtype, int N, int C, 
     const int64_t NC = (int64_t)N * C;
     const int vec = sbg_aligned16(x) && (HW % 8) == 0;
     hipStream_t s = (hipStream_t)stream;
+    SbgProfScope prof(s, SBG_K_DOT_HW, 0.0, (double)sbg_dtype_size(dtype) * NC * HW, {N, C, (int)HW, 5, vec ? 1 : 2});
     if (dtype == SBG_F32)      SBG_LAUNCH((moments_hw_planar<float>), dim3((unsigned)NC), dim3(256), 0, s, (const float*)x, r, NC, HW, vec);
     else if (dtype == SBG_F16) SBG_LAUNCH((moments_hw_planar<f16_s>), dim3((unsigned)NC), dim3(256), 0, s, (const f16_s*)x, r, NC, HW, vec);
     else                       SBG_LAUNCH((moments_hw_planar<bf16_s>), dim3((unsigned)NC), dim3(256), 0, s, (const bf16_s*)x, r, NC, HW, vec);
@@ -418,7 +423,7 @@ extern "C" int sbg_dot_hw_scale(const void* u, const void* v, const float* scale
     p.pix_per_split = (HW + p.nsplit - 1) / p.nsplit;
     hipStream_t s = (hipStream_t)stream;
     const double es = dtype == SBG_F32 ? 4 : 2;
-    SbgProfScope prof(s, SBG_K_DOT_HW, 0.0, 3.0 * es * N * (double)C * HW, {N, C, (int)HW, 3});
+    SbgProfScope prof(s, SBG_K_DOT_HW, 0.0, 3.0 * es * N * (double)C * HW, {N, C, (int)HW, 3, DOT_FORM_LANE_VEC, p.nsplit});
     if (dtype == SBG_F32)      SBG_LAUNCH((dot_hw_cminor8<float>), dim3(N, p.nsplit), dim3(256), 0, s, p);
     else if (dtype == SBG_F16) SBG_LAUNCH((dot_hw_cminor8<f16_s>), dim3(N, p.nsplit), dim3(256), 0, s, p);
     else                       SBG_LAUNCH((dot_hw_cminor8<bf16_s>), dim3(N, p.nsplit), dim3(256), 0, s, p);
@@ -470,7 +475,7 @@ static int modconv_bwd_impl(const void* dy, const void* y, const float* prescale
     p.alpha = act == SBG_ACT_LRELU ? alpha : (act == SBG_ACT_RELU ? 0.f : 1.f); p.gain = gain; p.clamp = clamp;
     hipStream_t s = (hipStream_t)stream;
     const double es = dtype == SBG_F32 ? 4 : 2;
-    SbgProfScope prof(s, SBG_K_DOT_HW, 0.0, 3.0 * es * N * (double)C * HW, {N, C, (int)HW, prescale ? 4 : 2});
+    SbgProfScope prof(s, SBG_K_DOT_HW, 0.0, 3.0 * es * N * (double)C * HW, {N, C, (int)HW, prescale ? 4 : 2, DOT_FORM_LANE_VEC, p.nsplit});
     if (prescale) {
         if (dtype == SBG_F32)      SBG_LAUNCH((modconv_bwd_kernel<float, true>), dim3(N, p.nsplit), dim3(256), 0, s, p);
         else if (dtype == SBG_F16) SBG_LAUNCH((modconv_bwd_kernel<f16_s, true>), dim3(N, p.nsplit), dim3(256), 0, s, p);

@@ -93,8 +93,13 @@ __global__ void __launch_bounds__(256) torgb_fwd_kernel(RgbArgs p)
 // of pixels 4 fg .. 4 fg + 3 as one 16-B store.  C = 32 NKB = 128 / 256 (at 512 the 192 weight registers leave no room: the streaming kernel stays,
 // its launches are the small 4x4 .. 64x64 layers), HW a multiple of 16.
 // Measured ([64, C, R, R], same box): 128 @256^2 369 -> 253 us (3.05 -> 4.44 TB/s), 256 @128^2 207 -> 143 us (2.66 -> 3.83).
+// SCALE: the remainders are split at 2^SCALE and 2^(2 SCALE) times their size and accumulate apart.  bf16 has fp32's exponent range: its parts
+// stay normal unscaled (SCALE 0, one accumulator), and three 8-bit parts hold every fp32 weight exactly.  f16 parts below 2^-14 are subnormal
+// (quantum 2^-24): unscaled, the second and third parts of a weight below ~2^-3 lose up to 2^-25 absolute.  Scaled by 2^11 and 2^22 they stay
+// in the head's binade, and the split is exact for 2^-14 <= |w| < 2^15.
 template <class T> struct RgbMfma;
 template <> struct RgbMfma<bf16_s> {
+    static constexpr int SCALE = 0;
     static __device__ __forceinline__ unsigned short cvt(float v) { return f32_to_bf16_bits(v); }
     static __device__ __forceinline__ float back(unsigned short b) { return bf16_bits_to_f32(b); }
     static __device__ __forceinline__ float4_t run(short8_t a, short8_t b, float4_t c) {
@@ -102,6 +107,7 @@ template <> struct RgbMfma<bf16_s> {
     }
 };
 template <> struct RgbMfma<f16_s> {
+    static constexpr int SCALE = 11;
     static __device__ __forceinline__ unsigned short cvt(float v) { return f32_to_f16_bits(v); }
     static __device__ __forceinline__ float back(unsigned short b) { return f16_bits_to_f32(b); }
     static __device__ __forceinline__ float4_t run(short8_t a, short8_t b, float4_t c) {
@@ -114,6 +120,8 @@ __global__ void __launch_bounds__(256) torgb_fwd_mfma_kernel(RgbArgs p)
 {
     const int n = blockIdx.x / p.blocks_per_n, blk = blockIdx.x % p.blocks_per_n;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, fr = lane & 15, fg = lane >> 4;
+    constexpr int S = RgbMfma<T>::SCALE;
+    constexpr float up = (float)(1 << S), down = 1.0f / (float)(1 << S);
     short8_t bh[NKB], bm[NKB], bl[NKB];
 #pragma unroll
     for (int kb = 0; kb < NKB; kb++)
@@ -121,10 +129,10 @@ __global__ void __launch_bounds__(256) torgb_fwd_mfma_kernel(RgbArgs p)
         for (int j = 0; j < 8; j++) {
             const float w = fr < p.O ? p.wmod[((int64_t)n * p.O + fr) * p.C + kb * 32 + fg * 8 + j] : 0.0f;
             const unsigned short h = RgbMfma<T>::cvt(w);
-            const float r1 = w - RgbMfma<T>::back(h);
+            const float r1 = (w - RgbMfma<T>::back(h)) * up;
             const unsigned short m = RgbMfma<T>::cvt(r1);
             bh[kb][j] = (short)h; bm[kb][j] = (short)m;
-            bl[kb][j] = (short)RgbMfma<T>::cvt(r1 - RgbMfma<T>::back(m));
+            bl[kb][j] = (short)RgbMfma<T>::cvt((r1 - RgbMfma<T>::back(m)) * up);
         }
     const float bias = (p.bias && fr < p.O) ? p.bias[fr] : 0.0f;
     const T* xb = (const T*)p.x + (int64_t)n * p.HW * p.C;
@@ -138,11 +146,23 @@ __global__ void __launch_bounds__(256) torgb_fwd_mfma_kernel(RgbArgs p)
 #pragma unroll
         for (int kb = 0; kb < NKB; kb++) a[kb] = *reinterpret_cast<const short8_t*>(px + kb * 32);
         float4_t acc = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (S == 0) {
 #pragma unroll
-        for (int kb = 0; kb < NKB; kb++) {
-            acc = RgbMfma<T>::run(a[kb], bl[kb], acc);      // smallest parts first
-            acc = RgbMfma<T>::run(a[kb], bm[kb], acc);
-            acc = RgbMfma<T>::run(a[kb], bh[kb], acc);
+            for (int kb = 0; kb < NKB; kb++) {
+                acc = RgbMfma<T>::run(a[kb], bl[kb], acc);      // smallest parts first
+                acc = RgbMfma<T>::run(a[kb], bm[kb], acc);
+                acc = RgbMfma<T>::run(a[kb], bh[kb], acc);
+            }
+        } else {
+            float4_t acm = {0.f, 0.f, 0.f, 0.f}, acl = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int kb = 0; kb < NKB; kb++) {
+                acl = RgbMfma<T>::run(a[kb], bl[kb], acl);
+                acm = RgbMfma<T>::run(a[kb], bm[kb], acm);
+                acc = RgbMfma<T>::run(a[kb], bh[kb], acc);
+            }
+#pragma unroll
+            for (int e = 0; e < 4; e++) acc[e] += (acl[e] * down + acm[e]) * down;      // smallest parts first
         }
         if (fr < p.O) {
             float4_t r;
@@ -300,6 +320,7 @@ extern "C" int sbg_torgb_fwd(const void* x, const float* wmod, const float* bias
     SbgProfScope prof(stream, SBG_K_TORGB, 2.0 * N * O * (double)C * HW, (double)N * HW * (2.0 * C + 4.0 * O), {N, C, O, (int)HW, 0, 0, 0});
     dim3 grid((unsigned)(N * a.blocks_per_n)), block(256);
     if ((HW & 15) == 0 && (C == 128 || C == 256) && sbg_aligned16(x) && sbg_aligned16(y)) {
+        prof.set_dim(5, 1);
         if (dtype == SBG_BF16) {
             if (C == 128) SBG_LAUNCH((torgb_fwd_mfma_kernel<bf16_s, 4>), grid, block, 0, stream, a);
             else SBG_LAUNCH((torgb_fwd_mfma_kernel<bf16_s, 8>), grid, block, 0, stream, a);
@@ -310,6 +331,7 @@ extern "C" int sbg_torgb_fwd(const void* x, const float* wmod, const float* bias
         SBG_HIP_LAUNCH_CHECK();
         return 0;
     }
+    prof.set_dim(5, O <= 3 ? 2 : 3);
     if (O <= 3) {
         if (dtype == SBG_BF16) SBG_LAUNCH((torgb_fwd_kernel<bf16_s, 3>), grid, block, 0, stream, a);
         else                   SBG_LAUNCH((torgb_fwd_kernel<f16_s, 3>), grid, block, 0, stream, a);

@@ -105,9 +105,10 @@ extern "C" int sbg_pack_weight(const float* w, void* out, int out_dtype, int A, 
     a.sA = sA; a.sB = sB; a.sKH = sKH; a.sKW = sKW; a.gain = gain;
     hipStream_t stream = (hipStream_t)stream_;
     const int64_t total = (int64_t)A * Bp;
-    SbgProfScope prof(stream, SBG_K_WEIGHT_PREP, 0.0, (double)A * B * KH * KW * (4.0 + sbg_dtype_size(out_dtype)), {A, B, KH * KW, 0, 0, 0, 0});
+    const bool transposing = !w2 && sA == 1 && sB >= 64 && A >= 32 && B >= 32 && KH * KW <= 65535;      // see pack_weight_t_kernel
+    SbgProfScope prof(stream, SBG_K_WEIGHT_PREP, 0.0, (double)A * B * KH * KW * (4.0 + sbg_dtype_size(out_dtype)), {A, B, KH * KW, 0, transposing ? 1 : 2, 0, 0});
     dim3 grid(sbg_stream_grid(total, 256)), block(256);
-    if (!w2 && sA == 1 && sB >= 64 && A >= 32 && B >= 32 && KH * KW <= 65535) {       // transposing form (see pack_weight_t_kernel)
+    if (transposing) {
         const dim3 tgrid((unsigned)((A + 31) / 32), (unsigned)((Bp + 31) / 32), (unsigned)(KH * KW));
         if (out_dtype == SBG_BF16)      SBG_LAUNCH(pack_weight_t_kernel<bf16_s>, tgrid, block, 0, stream, a);
         else if (out_dtype == SBG_F16)  SBG_LAUNCH(pack_weight_t_kernel<f16_s>, tgrid, block, 0, stream, a);
