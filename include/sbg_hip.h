@@ -434,6 +434,35 @@ int sbg_proj_sqdist(const float* t, const float* s, float* dist, void* workspace
 int sbg_proj_sqdist_bwd(const float* t, const float* s, const float* g, float* ds, int64_t F, sbg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Image export: the float -> uint8 step and the grid layout of the reference's image writers, and the latent table of its style
+ * matrix.  One launch each, no workspace.
+ *
+ * sbg_img_quantize_tile: img fp32 [N, C, H, W], C = 1 or 3, with element strides >= 0 (any memory format, slices) -> bytes in the
+ * caller's HWC canvas uint8 [gh * H, gw * W, C].  Image n fills cell k = cell0 + n, rows [k / gw * H, +H), columns [k % gw * W, +W);
+ * cell0 + N <= gw * gh, cells outside that run are not touched, so several calls fill one canvas.  Every float is read once and
+ * every byte written once.  `rule` selects the quantisation:
+ *   SBG_QUANT_GRID   `save_image_grid` (train_parts/trainers.py:102-106): v = (x - lo) * scale as two rounded fp32 operations,
+ *                    round half to even, clip to [0, 255].  scale = 255 / (hi - lo), computed by the caller in double and rounded
+ *                    to float (what numpy does with the Python scalar).
+ *   SBG_QUANT_CLAMP  stylegan2ada/generate.py:98,120 and style_mixing.py:79,88: v = x * 127.5 + 128 as a rounded multiply and a
+ *                    rounded add (no fused multiply-add), clamp to [0, 255], truncate.  lo and scale are ignored.
+ * The two differ on ties.  Non-finite values, which the reference leaves undefined: a NaN (in x or in v) writes 0, +inf and -inf
+ * clamp like any other value outside the range.
+ * W % 4 == 0 with 16-byte aligned rows (planar, or channel-minor with C = 3) takes four pixels per work-item: 16-byte loads,
+ * 4-byte stores; anything else takes one pixel per work-item.
+ *
+ * sbg_ws_truncate_mix: W fp32 [S, L, D] dense, w_avg fp32 [D] -> out fp32 [R * Cn, L, D] dense,
+ *   out[r * Cn + c, l] = T[mask[l] ? cols[c] : rows[r], l],  T = w_avg + (W - w_avg) * psi
+ * evaluated in that order as three rounded fp32 operations (style_mixing.py:74; not torch.lerp).  rows [R], cols [Cn] and mask [L]
+ * are int32 arrays on the device; an index outside [0, S) is never dereferenced: its rows of `out` are filled with NaN.  With
+ * rows = 0..S-1, Cn = 1 and a zero mask the result is T itself. */
+enum sbg_quant_rule { SBG_QUANT_GRID = 0, SBG_QUANT_CLAMP = 1 };
+int sbg_img_quantize_tile(const float* img, uint8_t* canvas, int N, int C, int H, int W, int64_t sn, int64_t sc, int64_t sh, int64_t sw,
+                          int gw, int gh, int cell0, int rule, float lo, float scale, sbg_stream_t stream);
+int sbg_ws_truncate_mix(const float* W, const float* w_avg, float psi, const int* rows, const int* cols, const int* mask, float* out,
+                        int S, int L, int D, int R, int Cn, sbg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * In-process launch timing (measurement only; bench.py's roofline figures come from here).
  * While enabled, every kernel launch of this library is bracketed by two hipEvents recorded on the launch stream
  * and logged with its algorithmic flops / bytes.  sbg_prof_fetch() synchronises the logged events, writes up to `max`
@@ -443,7 +472,9 @@ enum sbg_kernel_kind {
     SBG_K_BIAS_ACT = 1, SBG_K_UPFIRDN2D = 2, SBG_K_CONV_IGEMM = 3, SBG_K_CONV_WGRAD = 4, SBG_K_WGRAD_REDUCE = 5,
     SBG_K_SCALE_NC = 6, SBG_K_DOT_HW = 7, SBG_K_SN_POWER = 9, SBG_K_ATTENTION = 10, SBG_K_GRID_SAMPLE = 11, SBG_K_FILTER1D = 12, SBG_K_COLOR = 13, SBG_K_WEIGHT_PREP = 14, SBG_K_TORGB = 15, SBG_K_FROMRGB = 16,
     SBG_K_GROUPED_GEMM = 17, SBG_K_PPL = 18,    /* SBG_K_PPL: dims[0] = variant: 0 slerp / 1 lerp endpoints, 2 image prep, 3 distance */
-    SBG_K_PROJECTOR = 19        /* one record per launch; dims[0] = variant: 0 reg / 1 reg_bwd / 2 normalize / 3 sqdist / 4 sqdist_bwd, dims[1] = stage */
+    SBG_K_PROJECTOR = 19,       /* one record per launch; dims[0] = variant: 0 reg / 1 reg_bwd / 2 normalize / 3 sqdist / 4 sqdist_bwd, dims[1] = stage */
+    SBG_K_IMAGE_EXPORT = 20     /* dims[0] = variant: 0 quantize_tile (N, C, H, W, rule, dims[6] = 1 four planar pixels / 2 four channel-minor
+                                 * pixels / 3 one pixel per work-item), 1 truncate_mix (R * Cn, L, D, dims[4] = 1 vec4 / 2 scalar) */
 };
 /* Kernel-variant codes in the records of the streaming kernels (which kernel served the launch):
  *   bias_act     dims[4] = 1 vec8 / 2 scalar,  dims[5] = bias mode (0 none, 1 channel-minor vector, 2 one per 8-vector, 3 generic)

@@ -7,7 +7,7 @@ std::string& sbg_err_slot()
     return slot;
 }
 
-extern "C" int sbg_version(void) { return 5; }
+extern "C" int sbg_version(void) { return 6; }
 
 bool sbg_launch_geometry_ok(dim3 grid, dim3 block, size_t lds_bytes, const char* kernel, const char* file, int line)
 {

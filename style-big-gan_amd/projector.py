@@ -16,13 +16,13 @@ work and same result ([num_steps, num_ws, w_dim]).  Differences:
 import argparse
 import copy
 import os
-import re
 from time import perf_counter
 
 import numpy as np
 import torch
 import torch.nn.functional as F
 
+from .snapshot_io import build_generator, config_overrides, generator_common_kwargs, snapshot_generator_state     # noqa: F401
 from .torch_utils.ops import projector as proj_ops
 
 LPIPS_KWARGS = dict(resize_images=False, return_lpips=True)
@@ -174,38 +174,6 @@ def load_target(path, resolution):
     return target_pil, np.array(target_pil, dtype=np.uint8)
 
 
-def generator_common_kwargs(state):
-    """c_dim, img_resolution and img_channels of a generator, read from its state dict (the CLI has no data set to ask)"""
-    res = [int(m.group(1)) for k in state for m in [re.match(r'synthesis\.b(\d+)\.', k)] if m]
-    if not res:
-        raise RuntimeError('projector: the snapshot holds no mapping/synthesis generator')
-    img_resolution = max(res)
-    torgb = state.get(f'synthesis.b{img_resolution}.torgb.weight')
-    embed = state.get('mapping.embed.weight')
-    return dict(c_dim=int(embed.shape[1]) if embed is not None else 0, img_resolution=img_resolution,
-                img_channels=int(torgb.shape[0]) if torgb is not None else 3)
-
-
-def build_generator(config, state, device):
-    """G through the `generators` registry with the config's gens_args, weights from `state` (strict)"""
-    from .train_parts.generators import generators
-    from .train_parts.trainers import BaseTrainer
-    name = config.gen.generator
-    kw = BaseTrainer._model_kwargs(config.gens_args[name], generator_common_kwargs(state))
-    G = generators[name](**kw)
-    G.load_state_dict(state, strict=True)
-    return G.eval().requires_grad_(False).to(device)
-
-
-def snapshot_generator_state(path):
-    """G_ema of a network-snapshot-*.pt, or G when the run kept no average"""
-    snap = torch.load(path, map_location='cpu', weights_only=True)
-    key = 'G_ema' if snap.get('G_ema') is not None else 'G'
-    if key not in snap:
-        raise RuntimeError(f'projector: {path} holds neither G_ema nor G')
-    return snap[key]
-
-
 def parse_args(argv=None):
     """-> (config overrides as `key=value` strings, the projector's options)"""
     ap = argparse.ArgumentParser(prog='python -m style_big_gan_amd.projector', description=__doc__.split('\n')[0])
@@ -217,10 +185,7 @@ def parse_args(argv=None):
     ap.add_argument('--detector', required=True, help='local vgg16.pt (TorchScript LPIPS detector)')
     ap.add_argument('--save-video', action='store_true', help='save an mp4 of the optimisation (needs imageio)')
     args, rest = ap.parse_known_args(argv)
-    bad = [r for r in rest if '=' not in r or r.startswith('-')]
-    if bad:
-        ap.error(f'unrecognised arguments: {" ".join(bad)}')
-    return rest, args
+    return config_overrides(ap, rest), args
 
 
 def run_projection(argv=None):

@@ -32,6 +32,58 @@ trainers = utils.ClassRegistry()
 merge_rounds = os.environ.get('SBG_MERGE_ROUNDS', '1') != '0'      # accumulation rounds of a phase in one pass (StepEngine._rounds_in_one_pass)
 
 
+def setup_snapshot_image_grid(training_set, random_seed=0):
+    """-> ((gw, gh), uint8 images [gw * gh, C, H, W], labels [gw * gh, label_dim]): the samples of the snapshot grid (reference :63-98).
+    The grid covers about 7680 x 4320 pixels, at least 7 x 4 and at most 32 x 32 cells.  Without labels: a random subset of the
+    data set in shuffled order.  With labels: one class per grid row, classes in sorted order, each class's samples shuffled and
+    handed out gw at a time."""
+    rnd = np.random.RandomState(random_seed)
+    gw = int(np.clip(7680 // training_set.image_shape[2], 7, 32))
+    gh = int(np.clip(4320 // training_set.image_shape[1], 4, 32))
+    if not training_set.has_labels:
+        all_indices = list(range(len(training_set)))
+        rnd.shuffle(all_indices)
+        grid_indices = [all_indices[i % len(all_indices)] for i in range(gw * gh)]
+    else:
+        label_groups = dict()       # label => [idx, ...]
+        for idx in range(len(training_set)):
+            label = tuple(training_set.get_details(idx).raw_label.flat[::-1])
+            label_groups.setdefault(label, []).append(idx)
+        label_order = sorted(label_groups.keys())
+        for label in label_order:
+            rnd.shuffle(label_groups[label])
+        grid_indices = []
+        for y in range(gh):
+            label = label_order[y % len(label_order)]
+            indices = label_groups[label]
+            grid_indices += [indices[x % len(indices)] for x in range(gw)]
+            label_groups[label] = [indices[(i + gw) % len(indices)] for i in range(len(indices))]
+    images, labels = zip(*[training_set[i] for i in grid_indices])
+    return (gw, gh), np.stack(images), np.stack(labels)
+
+
+def write_grid_png(canvas, fname):
+    """uint8 HWC canvas -> PNG: mode 'L' for one channel, 'RGB' for three (reference :114-118)"""
+    import PIL.Image
+    canvas = np.ascontiguousarray(canvas)
+    assert canvas.ndim == 3 and canvas.shape[2] in [1, 3]
+    if canvas.shape[2] == 1:
+        PIL.Image.fromarray(canvas[:, :, 0], 'L').save(fname)
+    else:
+        PIL.Image.fromarray(canvas, 'RGB').save(fname)
+
+
+def save_image_grid(img, fname, drange, grid_size):
+    """images [gw * gh, C, H, W] (array or tensor, any real dtype) -> PNG of the gw x gh grid (reference :102-118): cast to float32,
+    (x - lo) * (255 / (hi - lo)), round half to even, clip.  A device tensor is quantised and tiled by the HIP kernel, so one byte per
+    value crosses to the host; anything on the host takes the reference's numpy expression."""
+    from ..torch_utils.ops import image_export
+    img = img if isinstance(img, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(img))
+    gw, gh = grid_size
+    assert img.shape[0] == gw * gh
+    write_grid_png(image_export.tile(img.to(torch.float32), (gw, gh), 'grid', drange).cpu().numpy(), fname)
+
+
 def lazy_reg_opt_kwargs(opt_kwargs, interval):
     """lr and betas of a phase that also carries a regulariser applied every `interval` iterations (reference :619-623)"""
     mb_ratio = interval / (interval + 1)
@@ -334,7 +386,31 @@ class SyntheticDataset:
         self.resolution, self.num_channels, self.label_dim = resolution, num_channels, num_classes
         self.image_shape = [num_channels, resolution, resolution]
         self.has_labels = num_classes > 0
+        self.seed = int(seed)
         self._gen = torch.Generator().manual_seed(seed)
+
+    # What the snapshot image grid reads (setup_snapshot_image_grid): a nominal size and per-index samples.  Sample `idx` is drawn from
+    # a generator of its own, so indexing never moves the stream `batch` draws from.
+    nominal_size = 4096
+
+    def __len__(self):
+        return self.nominal_size
+
+    def _raw_label(self, idx):
+        g = torch.Generator().manual_seed((self.seed * 1000003 + int(idx)) * 2 + 1)
+        return int(torch.randint(0, self.label_dim, [1], generator=g)) if self.has_labels else 0
+
+    def get_details(self, idx):
+        return EasyDict(raw_idx=int(idx), xflip=False, raw_label=np.asarray(self._raw_label(idx), dtype=np.int64))
+
+    def __getitem__(self, idx):
+        """-> (uint8 image [C, H, W], float32 one-hot label [label_dim]) as numpy arrays, like the real data sets"""
+        g = torch.Generator().manual_seed((self.seed * 1000003 + int(idx)) * 2)
+        img = torch.randint(0, 256, self.image_shape, generator=g, dtype=torch.uint8).numpy()
+        label = np.zeros([self.label_dim], dtype=np.float32)
+        if self.has_labels:
+            label[self._raw_label(idx)] = 1
+        return img, label
 
     def batch(self, n, device):
         img = torch.randint(0, 256, [n] + self.image_shape, generator=self._gen, dtype=torch.uint8).to(device)
@@ -355,6 +431,7 @@ class BaseTrainer:
     def __init__(self):
         self.rank = 0
         self.config = None
+        self.grid_size = self.grid_z = self.grid_c = None       # the snapshot image grid, set by the first save_image_snapshot
 
     # -- argument assembly / validation (reference :155-395) -----------------------------------------------------------
     def setup_arguments(self, config):
@@ -379,6 +456,7 @@ class BaseTrainer:
                              "reference .pkl snapshots are pickled modules; neither is loaded here -- pass a .pt written by save_snapshot)")
         self.run_dir = os.path.join(str(config.log.output), str(config.exp.name)) if config.exp.get("name", utils.MISSING) != utils.MISSING else None
         self.snapshot_iterations = None     # iterations between snapshots; None = only on request
+        self.image_snapshot_iterations = None       # iterations between image snapshots (fakes<kimg>.png); None = only on request
         from ..metrics import metric_main
         self.metrics = [str(m) for m in config.log.get("metrics", [])]      # reference :215-217
         bad = [m for m in self.metrics if not metric_main.is_valid_metric(m)]
@@ -613,7 +691,43 @@ class BaseTrainer:
         return self.engine.phases
 
     def export_sample_images(self):
-        pass
+        """reals.png and fakes_init.png at the start of a run (reference :677-696), when image snapshots are switched on"""
+        if self.image_snapshot_iterations:
+            self.save_image_snapshot()
+
+    def save_image_snapshot(self, run_dir=None):
+        """The run's sample images (reference :677-696, :807-815).  The first call picks the grid's real samples, writes reals.png, draws
+        the grid's latents `grid_z` (labels `grid_c` from the picked samples) and writes fakes_init.png; every later call writes
+        fakes<kimg:06d>.png from the same latents.  Images come from G_ema (G in eval mode when the run keeps no average) with
+        noise_mode='const', in `batch_gpu` chunks; on the device each chunk is quantised and tiled straight into the uint8 canvas.  Rank 0
+        writes; -> the file written (None on other ranks)."""
+        run_dir = run_dir or self.run_dir
+        assert run_dir is not None, "save_image_snapshot needs exp.name / log.output or an explicit run_dir"
+        if self.rank != 0:
+            return None
+        from ..torch_utils.ops import image_export
+        eng = self.engine
+        os.makedirs(run_dir, exist_ok=True)
+        first = self.grid_size is None
+        if first:
+            print('Exporting sample images...')
+            self.grid_size, images, labels = setup_snapshot_image_grid(training_set=self.dataset)
+            save_image_grid(images, os.path.join(run_dir, 'reals.png'), drange=[0, 255], grid_size=self.grid_size)
+            self.grid_z = torch.randn([labels.shape[0], eng.z_dim], device=eng.device).split(self.batch_gpu)
+            self.grid_c = torch.from_numpy(labels).to(eng.device).split(self.batch_gpu)
+        path = os.path.join(run_dir, 'fakes_init.png' if first else f'fakes{eng.cur_nimg // 1000:06d}.png')
+        G = eng.G_ema if eng.G_ema is not None else eng.G
+        was_training = G.training
+        G.eval()
+        canvas, cell = None, 0
+        with torch.no_grad():
+            for z, c in zip(self.grid_z, self.grid_c):
+                img = G(z, c, noise_mode='const').to(torch.float32)
+                canvas = image_export.tile(img, self.grid_size, 'grid', [-1, 1], canvas=canvas, cell0=cell)
+                cell += z.shape[0]
+        G.train(was_training)
+        write_grid_png(canvas.cpu().numpy(), path)
+        return path
 
     def training_loop(self, max_iterations=None):
         eng = self.engine
@@ -627,6 +741,8 @@ class BaseTrainer:
                 path = self.save_snapshot()
                 if self.metrics:            # every configured metric after each snapshot, on all ranks (reference :834-836)
                     self.evaluate_metrics(snapshot_path=path)
+            if self.image_snapshot_iterations and it % self.image_snapshot_iterations == 0:
+                self.save_image_snapshot()
             if max_iterations is None and total >= 0 and eng.cur_nimg >= total:
                 break
         self.stats.update()
