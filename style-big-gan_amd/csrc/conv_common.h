@@ -1,8 +1,16 @@
-// conv_common.h -- types shared by the implicit-GEMM convolution kernels (conv_igemm.hip, conv_k64.hip).
+// conv_common.h -- what the convolution kernels (conv_k64.hip, conv_up2.hip, conv_igemm.hip, conv_thin.hip; conv_wgrad.hip for the first
+// two items) share on the host side: the LDS-DMA sentinel, the MFMA wrappers, the kernel argument block, the host launch layer
+// (conv_is_plain, conv_prof_bytes, conv_launch) and the entry points of the per-file dispatchers.  The device-side pieces are in conv_device.h.
 #pragma once
 #include "sbg_common.h"
+#include <cstdlib>
+
+// Byte offset that is out of range for every buffer descriptor the kernels build (tensors < 2 GiB): an LDS-DMA load from it writes zeros.
+#define SBG_OOB_OFFSET 0x80000000u
 
 namespace sbgconv {
+
+typedef __attribute__((address_space(3))) void* lds_void_ptr;
 
 struct bf16_mfma { static constexpr int dtype = SBG_BF16; };
 struct f16_mfma  { static constexpr int dtype = SBG_F16;  };
@@ -42,6 +50,38 @@ struct ConvArgs {
     int lds_params;   // halo kernel: a loader wave stages each tile's epilogue parameters (noise / bias / demodulation coefficients) in LDS
 };
 
+// no fused epilogue: the accumulators are stored as they are.  (The macro form is for conv_thin_kernel alone, which compiles to different
+// instructions when the test goes through a function.)
+#define SBG_CONV_IS_PLAIN(a) (((a).act <= SBG_ACT_LINEAR) && (a).gain == 1.f && (a).clamp < 0.f && !(a).bias && !(a).noise && !(a).oscale)
+static __host__ __device__ __forceinline__ bool conv_is_plain(const ConvArgs& a) { return SBG_CONV_IS_PLAIN(a); }
+// the same for the caller's parameter block, where act 0 and gain 0 stand for "not set"
+static inline bool conv_is_plain(const sbg_conv_params& q)
+{
+    return (q.act == 0 || q.act == SBG_ACT_LINEAR) && (q.gain == 1.f || q.gain == 0.f) && q.clamp < 0.f && !q.bias && !q.noise && !q.oscale;
+}
+
+// bytes a launch moves, as the profiler counts them: the input once, the weights once, `outpix` output pixels (read back when accumulating)
+static inline double conv_prof_bytes(const ConvArgs& a, double outpix)
+{
+    const double ys = a.ydtype == SBG_F32 ? 4.0 : 2.0;
+    return 2.0 * a.N * a.IH * a.IW * (double)a.Cin + 2.0 * a.ntaps * a.Cout * (double)a.Cin + ys * outpix * (double)a.Cout * (a.accumulate ? 2 : 1);
+}
+
+// One launch of a convolution kernel: grid bound, dynamic-LDS limit (raised once per kernel), profiler scope, launch, error check.
+// dims = the profiler's shape key; its last entry is the code that names the kernel (bench.py, profiles/summarize.py, tests read it).
+template <auto Kern, class... Args>
+static int conv_launch(int64_t nblk, unsigned grid_y, unsigned block, int lds, hipStream_t stream, double flops, double bytes,
+                       std::initializer_list<int> dims, const Args&... args)
+{
+    if (nblk > INT32_MAX || nblk < 1) return sbg_fail(SBG_ERR_INVALID, "conv2d_igemm: grid too large");
+    if (lds > 64 * 1024 && !SBG_RAISE_LDS_ONCE(Kern, lds))
+        return sbg_fail(SBG_ERR_LAUNCH, "conv2d_igemm: cannot raise the dynamic LDS limit to %d bytes", lds);
+    SbgProfScope prof(stream, SBG_K_CONV_IGEMM, flops, bytes, dims);
+    SBG_LAUNCH(Kern, dim3((unsigned)nblk, grid_y), dim3(block), lds, stream, args...);
+    SBG_HIP_LAUNCH_CHECK();
+    return SBG_OK;
+}
+
 } // namespace sbgconv
 
 // conv_k64.hip: K-step-64 LDS-DMA kernels (gather and halo-staged).  Returns SBG_OK / an error, or -1 when the launch does not
@@ -50,6 +90,9 @@ int sbg_conv_k64_dispatch(sbgconv::ConvArgs& a, bool bf16, int64_t x_bytes, int6
 // conv_thin.hip: few-channel convolutions (Cin, Cout <= 64, one of them <= 32) as a streaming kernel with the reduction axis packed
 // over (tap, channel).  Returns SBG_OK / an error, or -1 when the launch is not a thin one.
 int sbg_conv_thin_dispatch(sbgconv::ConvArgs& a, bool bf16, hipStream_t stream);
+// conv_up2.hip: puts the taps of a 4 / 2 / 2 / 1-tap stride-2 transposed convolution in canonical order (inside every phase by (dy, dx)), all of them
+// or none; false when the launch is not of that form.  Called before any kernel is offered the launch, so every kernel sums a phase in one order.
+bool sbg_conv_up2_canonical_taps(sbgconv::ConvArgs& a, int64_t x_bytes, int64_t w_bytes);
 // conv_up2.hip: all four phases of a stride-2 3x3 transposed convolution from one staged input halo.  Returns SBG_OK / an error, or -1 when the
 // launch is not of that form; on SBG_OK `border` describes the remaining last row / column rectangles as an ordinary phased launch.
 int sbg_conv_up2_dispatch(sbgconv::ConvArgs& a, bool bf16, int64_t x_bytes, int64_t w_bytes, sbg_conv_params* border, const sbg_conv_params* q, hipStream_t stream);

@@ -19,200 +19,13 @@
 // `buffer_load_dwordx4 ... lds` (lane -> row = lane >> 3, slot = lane & 7).  The k-slot -> slot XOR swizzle
 // slot = kslot ^ (row & 7) is applied on the SOURCE address and on the fragment reads: ds_read_b128 of 16 consecutive
 // rows is conflict-free at any row alignment (SQ_LDS_BANK_CONFLICT = 0 measured), which the shifted halo windows need.
-#include "conv_common.h"
-#include <cstdlib>
+#include "conv_device.h"
 #include <type_traits>
-#include <utility>
 
 using namespace sbgconv;
 
 namespace {
 
-typedef __attribute__((address_space(3))) void* lds_void_ptr;
-#define SBG_OOB_OFFSET 0x80000000u      // >= num_records of every descriptor built below (tensors < 2 GiB): reads as zeros
-
-// LDS row R of the weight tile holds output channel c0 + chmap(R): inside a 32-row block, MFMA row m of the even / odd
-// 16-row tile maps to channel 8 (m / 4) + 4 (tile & 1) + (m % 4), so accumulator tiles (2h, 2h + 1) of a lane hold
-// channels 32 h + 8 fg + {0..3} and {4..7}.
-static __device__ __forceinline__ int chmap(int R) { return (R & ~31) + 8 * ((R & 15) >> 2) + 4 * ((R >> 4) & 1) + (R & 3); }
-
-template <int... Is, class F>
-static __device__ __forceinline__ void static_for_impl(std::integer_sequence<int, Is...>, F&& f) { (f(std::integral_constant<int, Is>{}), ...); }
-template <int N, class F>
-static __device__ __forceinline__ void static_for(F&& f) { static_for_impl(std::make_integer_sequence<int, N>{}, f); }   // compile-time unrolled loop
-
-template <int N> static __device__ __forceinline__ void wait_vmcnt_const() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
-
-// Straight-line fast path of the epilogue (layout of the accumulators: see conv_epilogue8 below): the output dtype and "no epilogue math" are template parameters, every 8-channel group of the
-// wave is in range and 16-B aligned (checked by the caller), so the loops below carry no per-element guards and no dtype
-// branches: leaky ReLU with alpha 0 / 1 covers ReLU / linear, clamp = med3 with an infinite bound when disabled.
-// `lp`: the tile's epilogue parameters staged in LDS by a loader wave (halo kernel: [noise of the TH x TW tile, row-major | bias of the 128 tile
-// channels | demodulation coefficients of (image, 128 tile channels)], 1 KiB each, fp32) -- the loads below then come from LDS (~100 cycles)
-// instead of L2 / HBM (a round trip of 1-2 us under load, paid by both compute groups at every tile boundary); lp_c = channel offset of this wave
-// inside the tile, lp_pix(j) = the pixel's index inside the tile.
-typedef __attribute__((address_space(3))) const float lds_cfloat;
-typedef __attribute__((address_space(3))) const float4_t lds_cfloat4;
-struct LdsParams { lds_cfloat* base; int c; int tw; };
-template <int TC, int TP, int YDT, bool PLAIN, bool NUNI, bool LP = false, class PixFn>
-static __device__ __forceinline__ void conv_epilogue_fast(const ConvArgs& p, float4_t (&acc)[TC][TP], int cbase, int fg, PixFn pix, int64_t ybase,
-                                                          const LdsParams* lp = nullptr, int y0 = 0, int x0 = 0)
-{
-    // NUNI: every pixel of the wave lies in one image (halo kernel), so the demodulation coefficients are per-h constants.
-    // Every parameter load (noise per pixel, bias and demodulation coefficients per channel group) is issued up front and UNCONDITIONALLY -- an
-    // absent term reads a valid dummy address (the first 16 bytes of x) and is replaced by a select -- so the wave waits for ONE round trip.
-    // (With `if (p.noise) nz = p.noise[...]` per pixel the compiler emitted load, s_waitcnt vmcnt(0), branch join four times over, plus two
-    // more waits for bias and coefficients: six exposed L2 / HBM latencies per tile, more than the arithmetic.)
-    constexpr int TH2 = TC / 2;
-    const float alpha = (p.act == SBG_ACT_LRELU) ? p.alpha : (p.act == SBG_ACT_RELU ? 0.f : 1.f);
-    const float lsel = alpha <= 1.f ? __builtin_inff() : -__builtin_inff();      // leaky ReLU = med3(u, alpha u, +inf) = max for alpha <= 1, min (-inf) above
-    const float cl = p.clamp >= 0.f ? p.clamp : __builtin_inff();
-    const float gain = p.gain;
-    const float* const dummy = reinterpret_cast<const float*>(p.x);
-    const bool has_nz = !PLAIN && p.noise != nullptr, has_b = !PLAIN && p.bias != nullptr, has_s = !PLAIN && p.oscale != nullptr;
-    int64_t yoff[TP]; float nz[TP]; bool ok[TP]; int nn[TP];
-#pragma unroll
-    for (int j = 0; j < TP; j++) {
-        int n, oy, ox;
-        ok[j] = pix(j, n, oy, ox);                      // (an out-of-range pixel still decodes to valid coordinates)
-        nn[j] = n;
-        yoff[j] = ybase + (int64_t)blockIdx.y * p.y_split_stride + (int64_t)n * p.ys_n + (int64_t)oy * p.ys_h + (int64_t)ox * p.ys_w + cbase + 8 * fg;
-        nz[j] = 0.f;
-        if (!PLAIN) {
-            if constexpr (LP) nz[j] = lp->base[(oy - y0) * lp->tw + (ox - x0)];
-            else              nz[j] = *(has_nz ? p.noise + ((int64_t)n * p.noise_sn + (int64_t)oy * p.OW + ox) : dummy);
-        }
-    }
-    float4_t b_lo[TH2], b_hi[TH2], s_lo[TH2], s_hi[TH2];
-#pragma unroll
-    for (int h = 0; h < TH2; h++) {
-        b_lo[h] = b_hi[h] = float4_t{0.f, 0.f, 0.f, 0.f};
-        s_lo[h] = s_hi[h] = float4_t{1.f, 1.f, 1.f, 1.f};
-        if (!PLAIN) {
-            if constexpr (LP) {
-                lds_cfloat* b = lp->base + 256 + lp->c + 32 * h + 8 * fg;
-                b_lo[h] = *(lds_cfloat4*)b; b_hi[h] = *(lds_cfloat4*)(b + 4);
-                if (NUNI) { s_lo[h] = *(lds_cfloat4*)(b + 256); s_hi[h] = *(lds_cfloat4*)(b + 260); }
-            } else {
-            const float* b = has_b ? p.bias + cbase + 32 * h + 8 * fg : dummy;
-            b_lo[h] = *reinterpret_cast<const float4_t*>(b); b_hi[h] = *reinterpret_cast<const float4_t*>(has_b ? b + 4 : dummy);
-            if (NUNI) {
-                const float* sc = has_s ? p.oscale + (int64_t)nn[0] * p.Cout + cbase + 32 * h + 8 * fg : dummy;
-                s_lo[h] = *reinterpret_cast<const float4_t*>(sc); s_hi[h] = *reinterpret_cast<const float4_t*>(has_s ? sc + 4 : dummy);
-            }
-            }
-        }
-    }
-    if (!PLAIN) {
-#pragma unroll
-        for (int j = 0; j < TP; j++) nz[j] = has_nz ? nz[j] : 0.f;
-#pragma unroll
-        for (int h = 0; h < TH2; h++) {
-            if (!has_b) { b_lo[h] = float4_t{0.f, 0.f, 0.f, 0.f}; b_hi[h] = b_lo[h]; }
-            if (!NUNI || !has_s) { s_lo[h] = float4_t{1.f, 1.f, 1.f, 1.f}; s_hi[h] = s_lo[h]; }
-        }
-    }
-#pragma unroll
-    for (int h = 0; h < TH2; h++) {
-#pragma unroll
-        for (int j = 0; j < TP; j++) {
-            if (!ok[j]) continue;
-            float4_t lo = acc[2 * h][j], hi = acc[2 * h + 1][j];
-            if (!PLAIN) {
-                float4_t sl = s_lo[h], sh = s_hi[h];
-                if (!NUNI && has_s) {
-                    const float* sc = p.oscale + (int64_t)nn[j] * p.Cout + cbase + 32 * h + 8 * fg;
-                    sl = *reinterpret_cast<const float4_t*>(sc); sh = *reinterpret_cast<const float4_t*>(sc + 4);
-                }
-                lo = lo * sl + (nz[j] + b_lo[h]);
-                hi = hi * sh + (nz[j] + b_hi[h]);
-                const float4_t tl = lo * alpha, th = hi * alpha;       // vector forms: v_pk_mul_f32
-#pragma unroll
-                for (int e = 0; e < 4; e++) { lo[e] = __builtin_amdgcn_fmed3f(lo[e], tl[e], lsel); hi[e] = __builtin_amdgcn_fmed3f(hi[e], th[e], lsel); }
-                lo = lo * gain; hi = hi * gain;
-#pragma unroll
-                for (int e = 0; e < 4; e++) { lo[e] = __builtin_amdgcn_fmed3f(lo[e], -cl, cl); hi[e] = __builtin_amdgcn_fmed3f(hi[e], -cl, cl); }
-            }
-            if (YDT == SBG_F32) {
-                float* dst = (float*)p.y + yoff[j] + 32 * h;
-                if (p.accumulate) { lo += *reinterpret_cast<float4_t*>(dst); hi += *reinterpret_cast<float4_t*>(dst + 4); }
-                *reinterpret_cast<float4_t*>(dst) = lo;
-                *reinterpret_cast<float4_t*>(dst + 4) = hi;
-            } else {
-                short8_t o;
-#pragma unroll
-                for (int e = 0; e < 4; e++) { o[e] = (short)f32_to_bf16_bits(lo[e]); o[4 + e] = (short)f32_to_bf16_bits(hi[e]); }
-                *reinterpret_cast<short8_t*>((unsigned short*)p.y + yoff[j] + 32 * h) = o;
-            }
-        }
-    }
-}
-
-
-// Epilogue: lane (fr, fg) holds, for the pixel of fragment column fr in segment j, channels cbase + 32 h + 8 fg + e with
-// e = 0..3 in acc[2h][j] and e = 4..7 in acc[2h + 1][j].  pix(j, n, oy, ox) -> in range?
-template <int TC, int TP, bool NUNI = false, class PixFn>
-static __device__ __forceinline__ void conv_epilogue8(const ConvArgs& p, float4_t (&acc)[TC][TP], int cbase, int fg, PixFn pix, int64_t ybase = 0,
-                                                      const LdsParams* lp = nullptr, int y0 = 0, int x0 = 0)
-{
-    constexpr int TH2 = TC / 2;
-    const bool plain = (p.act <= SBG_ACT_LINEAR) && p.gain == 1.f && p.clamp < 0.f && !p.bias && !p.noise && !p.oscale;
-    // fast path: the wave's whole channel range is valid, rows and per-channel vectors 16-B aligned, bf16 / fp32 output
-    const bool fast = (cbase + 16 * TC <= p.Cout) && ((p.Cout & 7) == 0) && ((((uintptr_t)p.y) & 15) == 0) && (((p.ys_n | p.ys_h | p.ys_w) & 7) == 0)
-                      && ((((uintptr_t)p.oscale) & 15) == 0) && ((((uintptr_t)p.bias) & 15) == 0) && p.ydtype != SBG_F16;
-    if (fast) {
-        if (p.ydtype == SBG_BF16) {
-            if (plain) conv_epilogue_fast<TC, TP, SBG_BF16, true, NUNI>(p, acc, cbase, fg, pix, ybase);
-            else if (lp) conv_epilogue_fast<TC, TP, SBG_BF16, false, NUNI, true>(p, acc, cbase, fg, pix, ybase, lp, y0, x0);
-            else       conv_epilogue_fast<TC, TP, SBG_BF16, false, NUNI>(p, acc, cbase, fg, pix, ybase);
-        } else {
-            if (plain) conv_epilogue_fast<TC, TP, SBG_F32, true, NUNI>(p, acc, cbase, fg, pix, ybase);
-            else if (lp) conv_epilogue_fast<TC, TP, SBG_F32, false, NUNI, true>(p, acc, cbase, fg, pix, ybase, lp, y0, x0);
-            else       conv_epilogue_fast<TC, TP, SBG_F32, false, NUNI>(p, acc, cbase, fg, pix, ybase);
-        }
-        return;
-    }
-    float bias8[TH2][8];
-#pragma unroll
-    for (int h = 0; h < TH2; h++) {
-        const int co = cbase + 32 * h + 8 * fg;
-#pragma unroll
-        for (int e = 0; e < 8; e++) bias8[h][e] = (p.bias && co + e < p.Cout) ? p.bias[co + e] : 0.f;
-    }
-#pragma unroll
-    for (int j = 0; j < TP; j++) {
-        int n, oy, ox;
-        if (!pix(j, n, oy, ox)) continue;
-        const int64_t yoff = ybase + (int64_t)blockIdx.y * p.y_split_stride + (int64_t)n * p.ys_n + (int64_t)oy * p.ys_h + (int64_t)ox * p.ys_w;
-        const float nz = (!plain && p.noise) ? p.noise[(int64_t)n * p.noise_sn + (int64_t)oy * p.OW + ox] : 0.f;
-#pragma unroll
-        for (int h = 0; h < TH2; h++) {
-            const int co = cbase + 32 * h + 8 * fg;
-            if (co >= p.Cout) continue;
-            float v[8];
-#pragma unroll
-            for (int e = 0; e < 4; e++) { v[e] = acc[2 * h][j][e]; v[4 + e] = acc[2 * h + 1][j][e]; }
-#pragma unroll 1
-            for (int e = 0; e < 8; e++) {            // rolled: this path serves odd channel counts (ToRGB, tails), not the flops
-                if (co + e >= p.Cout) break;
-                float u = v[e];
-                if (!plain) {
-                    if (p.oscale) u *= p.oscale[(int64_t)n * p.Cout + co + e];
-                    u += nz + bias8[h][e];
-                    if (p.act == SBG_ACT_LRELU) u = (u > 0.f) ? u : u * p.alpha;
-                    else if (p.act == SBG_ACT_RELU) u = (u > 0.f) ? u : 0.f;
-                    u *= p.gain;
-                    if (p.clamp >= 0.f) u = (u > -p.clamp && u < p.clamp) ? u : (u >= 0.f ? p.clamp : -p.clamp);
-                }
-                if (p.ydtype == SBG_F32) {
-                    float* dst = (float*)p.y + yoff + co + e;
-                    *dst = p.accumulate ? *dst + u : u;
-                } else {
-                    ((unsigned short*)p.y)[yoff + co + e] = (p.ydtype == SBG_BF16) ? f32_to_bf16_bits(u) : f32_to_f16_bits(u);
-                }
-            }
-        }
-    }
-}
 
 // Gather (im2col-on-the-fly) kernel: any tap list and stride; one 128 (or 64) x 256 (or 128) tile per workgroup, 8 waves.
 template <class MF, int BC, int BP, int WGC, int WGP>
@@ -234,19 +47,14 @@ __global__ __launch_bounds__(512, 2) void conv_k64_kernel(ConvArgs p, unsigned x
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const bool grpY = wave >= 4;
-    int bid = blockIdx.x;
-    {   // XCD-aware tile order: workgroups b and b + 8 share an XCD (L2); give each XCD a contiguous run of tiles
-        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, k = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-    }
+    const int bid = xcd_tile_order(blockIdx.x, gridDim.x);
     const int c0 = (bid % p.ctiles) * BC, p0 = (bid / p.ctiles) * BP;     // one tile per workgroup
 
     __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, (int)x_bytes, 0x00020000);
     __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, (int)w_bytes, 0x00020000);
 
-    // ---- DMA lane coordinates: lane -> (row = 8 piece + (lane >> 3), slot = lane & 7), source k-slot = slot ^ (row & 7)
-    const int lrow = lane >> 3;
-    const int src_k = ((lane & 7) ^ lrow) * 8;          // channel offset inside the 64-channel slice
+    const int lrow = dma_lrow(lane);
+    const int src_k = dma_src_k(lane, lrow);      // DMA lane coordinates
     unsigned a_base[IA];                                // byte offset of (channel row, src_k) in a weight slab, or out of range
 #pragma unroll
     for (int i = 0; i < IA; i++) {
@@ -280,7 +88,7 @@ __global__ __launch_bounds__(512, 2) void conv_k64_kernel(ConvArgs p, unsigned x
     const int wci = wave / WGP, wpi = wave % WGP;
     const int wc = wci * WC, wp = wpi * WP;
     const int fr = lane & 15, fg = lane >> 4;
-    const int frag_off = fr * 128 + ((fg ^ (fr & 7)) << 4);          // k-sub 0; k-sub 1 = ^ 64
+    const int foff = frag_off(fr, fg);
     float4_t acc[TC][TP];
 #pragma unroll
     for (int i = 0; i < TC; i++)
@@ -293,7 +101,7 @@ __global__ __launch_bounds__(512, 2) void conv_k64_kernel(ConvArgs p, unsigned x
 #pragma unroll
         for (int ks = 0; ks < 2; ks++)
 #pragma unroll
-            for (int i = 0; i < TC; i++) fa[ks][i] = *reinterpret_cast<const short8_t*>(sa + i * 16 * 128 + (frag_off ^ (ks * 64)));
+            for (int i = 0; i < TC; i++) fa[ks][i] = *reinterpret_cast<const short8_t*>(sa + i * 16 * 128 + (foff ^ (ks * 64)));
     };
     auto mma = [&]() {
 #pragma unroll
@@ -354,7 +162,7 @@ __global__ __launch_bounds__(512, 2) void conv_k64_kernel(ConvArgs p, unsigned x
 #pragma unroll
             for (int ks = 0; ks < 2; ks++)
 #pragma unroll
-                for (int j = 0; j < TP; j++) fb[ks][j] = *reinterpret_cast<const short8_t*>(sb + j * 16 * 128 + (frag_off ^ (ks * 64)));
+                for (int j = 0; j < TP; j++) fb[ks][j] = *reinterpret_cast<const short8_t*>(sb + j * 16 * 128 + (foff ^ (ks * 64)));
         };
         constexpr int C = IA + IB;                       // DMA instructions per wave per step
         static_assert(LEAD == 2, "gather pipeline: two steps of loads in flight");
@@ -433,11 +241,7 @@ __global__ __launch_bounds__(768, 3) void conv_halo_ld_kernel(ConvArgs p, unsign
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int bid = blockIdx.x;
-    {   // XCD-aware tile order: workgroups b and b + 8 share an XCD (L2); give each XCD a contiguous run of tiles
-        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, k = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-    }
+    const int bid = xcd_tile_order(blockIdx.x, gridDim.x);
     const int tiles_x = p.OW / TW, tiles_y = p.OH / TH;
     const int ntiles = p.ptiles * p.ctiles, G = gridDim.x;
     const int my_tiles = (ntiles - bid + G - 1) / G;                  // tiles bid, bid + G, ...  (the grid never exceeds ntiles)
@@ -462,8 +266,8 @@ __global__ __launch_bounds__(768, 3) void conv_halo_ld_kernel(ConvArgs p, unsign
         t_.tn += gstep.tn + carry;
         return t_;
     };
-    const int lrow = lane >> 3;
-    const int src_k = ((lane & 7) ^ lrow) * 8;          // DMA lane -> (row = 8 piece + lrow, slot = lane & 7), source k-slot = slot ^ (row & 7)
+    const int lrow = dma_lrow(lane);
+    const int src_k = dma_src_k(lane, lrow);      // DMA lane coordinates
 
     if (wave >= 10) {
         // ---------------------------------------------------------------- halo loader (waves 10, 11) ----------------------
@@ -528,7 +332,7 @@ __global__ __launch_bounds__(768, 3) void conv_halo_ld_kernel(ConvArgs p, unsign
         TileC tc = decode(tile);
         {
             const int hbase = halo_base(tc, 0); const unsigned emask = edge_mask(tc);
-            static_for<HPL>([&](auto it_) { issue_halo(it_, hbase, emask, src_k < p.Cin, 0); });
+            sbg_static_for<HPL>([&](auto it_) { issue_halo(it_, hbase, emask, src_k < p.Cin, 0); });
         }
         // The 22 pieces of the next slice go out TWO per half-step (behind each of the slice's first eleven barriers), not as one burst behind
         // the first: an LDS-DMA instruction costs its wave ~100+ cycles beside the compute waves' fragment reads, every wave of the workgroup
@@ -546,7 +350,7 @@ __global__ __launch_bounds__(768, 3) void conv_halo_ld_kernel(ConvArgs p, unsign
             }
             const int hbase = halo_base(tc, chunk); const unsigned emask = edge_mask(tc);
             const bool kok = chunk * 64 + src_k < p.Cin;
-            static_for<17>([&](auto it_) {
+            sbg_static_for<17>([&](auto it_) {
                 constexpr int i = decltype(it_)::value;
                 if (more) {
                     if constexpr (per * i < HPL)     issue_halo(std::integral_constant<int, (per * i < HPL ? per * i : 0)>{}, hbase, emask, kok, (c + 1) & 1);
@@ -639,7 +443,7 @@ __global__ __launch_bounds__(768, 3) void conv_halo_ld_kernel(ConvArgs p, unsign
     const int wci = wave >> 2, wpi = wave & 3;           // waves 0-3 and 4-7 each cover both channel halves? no: wave = wci * 4 + wpi
     const int wc = wci * WC;
     const int fr = lane & 15, fg = lane >> 4;
-    const int frag_off = fr * 128 + ((fg ^ (fr & 7)) << 4);          // k-sub 0; k-sub 1 = ^ 64
+    const int foff = frag_off(fr, fg);
     const int tl = lane < p.ntaps ? lane : 0;
     const int tbl_shift = p.tap_dy[tl] * PW + p.tap_dx[tl];
     float4_t acc[TC][TP];
@@ -677,7 +481,7 @@ __global__ __launch_bounds__(768, 3) void conv_halo_ld_kernel(ConvArgs p, unsign
     if (grpY) __builtin_amdgcn_s_barrier();              // 0
     for (int c = 0; c < nslices; c++) {
         const unsigned char* hb = sH + par * HALO_BYTES;
-        static_for<NT>([&](auto tap_tag) {
+        sbg_static_for<NT>([&](auto tap_tag) {
             constexpr int t = decltype(tap_tag)::value;
             const int shift = __builtin_amdgcn_readlane(tbl_shift, t);
             const unsigned char* sa = smem + stage * STAGE + wc * 128;
@@ -686,7 +490,7 @@ __global__ __launch_bounds__(768, 3) void conv_halo_ld_kernel(ConvArgs p, unsign
 #pragma unroll
             for (int ks = 0; ks < 2; ks++)
 #pragma unroll
-                for (int i = 0; i < TC; i++) fa[ks][i] = *reinterpret_cast<const short8_t*>(sa + i * 16 * 128 + (frag_off ^ (ks * 64)));
+                for (int i = 0; i < TC; i++) fa[ks][i] = *reinterpret_cast<const short8_t*>(sa + i * 16 * 128 + (foff ^ (ks * 64)));
 #pragma unroll
             for (int j = 0; j < TP; j++) {
                 const int pp = seg_pp[j] + shift;
@@ -697,12 +501,7 @@ __global__ __launch_bounds__(768, 3) void conv_halo_ld_kernel(ConvArgs p, unsign
             __builtin_amdgcn_s_waitcnt(0xC07F);          // lgkmcnt(0): fragments are in registers, this wave no longer reads the stage
             __builtin_amdgcn_s_barrier();                // B_b
             __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int ks = 0; ks < 2; ks++)
-#pragma unroll
-                for (int i = 0; i < TC; i++)
-#pragma unroll
-                    for (int j = 0; j < TP; j++) acc[i][j] = Mfma<MF>::run(fa[ks][i], fb[ks][j], acc[i][j]);
+            mma_step<MF>(acc, fa, fb);
             __builtin_amdgcn_sched_barrier(0);
             stage = (stage + 1) & (NSTAGE - 1);
         });
@@ -743,11 +542,7 @@ __global__ __launch_bounds__(768, 3) void conv_gather_ld_kernel(ConvArgs p, unsi
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int bid = blockIdx.x;
-    {   // XCD-aware tile order: workgroups b and b + 8 share an XCD (L2); give each XCD a contiguous run of tiles
-        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = bid & 7, k = bid >> 3;
-        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-    }
+    const int bid = xcd_tile_order(blockIdx.x, gridDim.x);
     const int ntiles = p.ptiles * p.ctiles, G = gridDim.x;
     const int my_tiles = (ntiles - bid + G - 1) / G;                  // tiles bid, bid + G, ...  (the grid never exceeds ntiles)
     const int kchunks = (p.Cin + 63) >> 6;
@@ -758,8 +553,8 @@ __global__ __launch_bounds__(768, 3) void conv_gather_ld_kernel(ConvArgs p, unsi
     auto tile_phase = [&](int tile) { const int r = tile / p.ctiles; return (r % p.nphase + (r / p.nphase) / p.ph_rot_div) % p.nphase; };
     int S = 0;
     for (int t_ = bid; t_ < ntiles; t_ += G) S += p.ph_ntaps[tile_phase(t_)] * kchunks;
-    const int lrow = lane >> 3;
-    const int src_k = ((lane & 7) ^ lrow) * 8;          // DMA lane -> (row = 8 piece + lrow, slot = lane & 7), source k-slot = slot ^ (row & 7)
+    const int lrow = dma_lrow(lane);
+    const int src_k = dma_src_k(lane, lrow);      // DMA lane coordinates
     const int tl = lane < p.ntaps ? lane : 0;
 
     if (wave >= 8) {
@@ -861,7 +656,7 @@ __global__ __launch_bounds__(768, 3) void conv_gather_ld_kernel(ConvArgs p, unsi
     const int wci = wave >> 2, wpi = wave & 3;
     const int wc = wci * WC, wp = wpi * WP;
     const int fr = lane & 15, fg = lane >> 4;
-    const int frag_off = fr * 128 + ((fg ^ (fr & 7)) << 4);          // k-sub 0; k-sub 1 = ^ 64
+    const int foff = frag_off(fr, fg);
     float4_t acc[TC][TP];
 #pragma unroll
     for (int i = 0; i < TC; i++)
@@ -895,20 +690,15 @@ __global__ __launch_bounds__(768, 3) void conv_gather_ld_kernel(ConvArgs p, unsi
 #pragma unroll
         for (int ks = 0; ks < 2; ks++)
 #pragma unroll
-            for (int i = 0; i < TC; i++) fa[ks][i] = *reinterpret_cast<const short8_t*>(sa + i * 16 * 128 + (frag_off ^ (ks * 64)));
+            for (int i = 0; i < TC; i++) fa[ks][i] = *reinterpret_cast<const short8_t*>(sa + i * 16 * 128 + (foff ^ (ks * 64)));
 #pragma unroll
         for (int ks = 0; ks < 2; ks++)
 #pragma unroll
-            for (int j = 0; j < TP; j++) fb[ks][j] = *reinterpret_cast<const short8_t*>(sb + j * 16 * 128 + (frag_off ^ (ks * 64)));
+            for (int j = 0; j < TP; j++) fb[ks][j] = *reinterpret_cast<const short8_t*>(sb + j * 16 * 128 + (foff ^ (ks * 64)));
         __builtin_amdgcn_s_waitcnt(0xC07F);              // lgkmcnt(0): fragments are in registers, this wave no longer reads the stage
         __builtin_amdgcn_s_barrier();                    // B_b
         __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int ks = 0; ks < 2; ks++)
-#pragma unroll
-            for (int i = 0; i < TC; i++)
-#pragma unroll
-                for (int j = 0; j < TP; j++) acc[i][j] = Mfma<MF>::run(fa[ks][i], fb[ks][j], acc[i][j]);
+        mma_step<MF>(acc, fa, fb);
         __builtin_amdgcn_sched_barrier(0);
         stage = stage == NSTAGE - 1 ? 0 : stage + 1;
         if (--left == 0) { pend = true; done_tile = tile; tile += G; if (tile < ntiles) left = p.ph_ntaps[tile_phase(tile)] * kchunks; }
@@ -929,27 +719,14 @@ static int launch_gather_ld(ConvArgs& a, unsigned x_bytes, unsigned w_bytes, hip
     for (int i = 0; i < a.nphase; i++) if (a.ph_P[i] > pmax) pmax = a.ph_P[i];
     a.ptiles = ((pmax + 255) / 256) * a.nphase;      // every phase gets the pixel tiles of the largest one (the others' last tile may be empty)
     int64_t nblk = (int64_t)a.ptiles * a.ctiles;
-    if (nblk > INT32_MAX) return sbg_fail(SBG_ERR_INVALID, "conv2d_igemm: grid too large");
-    static int ncu = 0;
-    if (ncu == 0) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        ncu = n;
-    }
-    if (nblk > ncu) nblk = ncu;     // persistent: one workgroup per CU, each walks tiles b, b + grid, ...
+    if (nblk > INT32_MAX) return sbg_fail(SBG_ERR_INVALID, "conv2d_igemm: grid too large");      // (the kernel counts tiles in an int)
+    if (nblk > sbg_cu_count()) nblk = sbg_cu_count();     // persistent: one workgroup per CU, each walks tiles b, b + grid, ...
     a.ph_rot_div = (int)(nblk / ((int64_t)a.ctiles * a.nphase)); if (a.ph_rot_div < 1) a.ph_rot_div = 1;
-    auto kern = conv_gather_ld_kernel<MF>;
-    if (!SBG_RAISE_LDS_ONCE(kern, lds))
-        return sbg_fail(SBG_ERR_LAUNCH, "conv2d_igemm: cannot raise the dynamic LDS limit to %d bytes", lds);
-    const double ys = a.ydtype == SBG_F32 ? 4.0 : 2.0;
     double macs = 0.0, outpix = 0.0;
     for (int i = 0; i < a.nphase; i++) { macs += (double)a.ph_P[i] * a.ph_ntaps[i]; outpix += a.ph_P[i]; }
-    SbgProfScope prof(stream, SBG_K_CONV_IGEMM, 2.0 * macs * a.Cout * (double)a.Cin,
-                      2.0 * a.N * a.IH * a.IW * (double)a.Cin + 2.0 * a.ntaps * a.Cout * (double)a.Cin + ys * outpix * (double)a.Cout * (a.accumulate ? 2 : 1),
-                      {(int)outpix, a.Cout, a.Cin, a.ntaps, a.stride, a.OH, 4128256 + (a.nphase > 1 ? 1000000 * a.nphase : 0)});
-    SBG_LAUNCH(kern, dim3((unsigned)nblk), dim3(768), lds, stream, a, x_bytes, w_bytes);
-    SBG_HIP_LAUNCH_CHECK();
-    return SBG_OK;
+    return conv_launch<conv_gather_ld_kernel<MF>>(nblk, 1, 768, lds, stream, 2.0 * macs * a.Cout * (double)a.Cin, conv_prof_bytes(a, outpix),
+                                                  {(int)outpix, a.Cout, a.Cin, a.ntaps, a.stride, a.OH, 4128256 + (a.nphase > 1 ? 1000000 * a.nphase : 0)},
+                                                  a, x_bytes, w_bytes);
 }
 
 template <class MF, int TH, int TW>
@@ -958,7 +735,7 @@ static int launch_halo_ld(ConvArgs& a, unsigned x_bytes, unsigned w_bytes, hipSt
     constexpr int HPIECES = ((TH + 2) * (TW + 2) + 7) / 8;
     constexpr int lds = 4 * 128 * 128 + 2 * HPIECES * 1024 + 2 * 3072;
     {   // the epilogue parameters go through LDS when the epilogue's 16-B fast path applies and the noise rows are 16-B aligned
-        const bool plain = (a.act <= SBG_ACT_LINEAR) && a.gain == 1.f && a.clamp < 0.f && !a.bias && !a.noise && !a.oscale;
+        const bool plain = conv_is_plain(a);
         const bool fast = ((a.Cout & 7) == 0) && ((((uintptr_t)a.y) & 15) == 0) && (((a.ys_n | a.ys_h | a.ys_w) & 7) == 0)
                           && ((((uintptr_t)a.oscale) & 15) == 0) && ((((uintptr_t)a.bias) & 15) == 0) && a.ydtype != SBG_F16;
         const bool nz_ok = !a.noise || (((((uintptr_t)a.noise) & 15) == 0) && (a.noise_sn & 3) == 0 && (a.OW & 3) == 0
@@ -969,24 +746,10 @@ static int launch_halo_ld(ConvArgs& a, unsigned x_bytes, unsigned w_bytes, hipSt
     a.ctiles = (a.Cout + 127) / 128;
     a.ptiles = a.N * (a.OH / TH) * (a.OW / TW);
     int64_t nblk = (int64_t)a.ptiles * a.ctiles;
-    if (nblk > INT32_MAX) return sbg_fail(SBG_ERR_INVALID, "conv2d_igemm: grid too large");
-    static int ncu = 0;
-    if (ncu == 0) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        ncu = n;
-    }
-    if (nblk > ncu) nblk = ncu;     // persistent: one workgroup per CU (the LDS footprint admits no more), each walks tiles b, b + grid, ...
-    auto kern = conv_halo_ld_kernel<MF, TH, TW>;
-    if (!SBG_RAISE_LDS_ONCE(kern, lds))
-        return sbg_fail(SBG_ERR_LAUNCH, "conv2d_igemm: cannot raise the dynamic LDS limit to %d bytes", lds);
-    const double ys = a.ydtype == SBG_F32 ? 4.0 : 2.0;
-    SbgProfScope prof(stream, SBG_K_CONV_IGEMM, 2.0 * a.P * a.Cout * (double)a.Cin * a.ntaps,
-                      2.0 * a.N * a.IH * a.IW * (double)a.Cin + 2.0 * a.ntaps * a.Cout * (double)a.Cin + ys * a.P * (double)a.Cout * (a.accumulate ? 2 : 1),
-                      {a.P, a.Cout, a.Cin, a.ntaps, a.stride, a.OH, 3128256});
-    SBG_LAUNCH(kern, dim3((unsigned)nblk), dim3(768), lds, stream, a, x_bytes, w_bytes);
-    SBG_HIP_LAUNCH_CHECK();
-    return SBG_OK;
+    if (nblk > INT32_MAX) return sbg_fail(SBG_ERR_INVALID, "conv2d_igemm: grid too large");      // (the kernel counts tiles in an int)
+    if (nblk > sbg_cu_count()) nblk = sbg_cu_count();     // persistent: one workgroup per CU (the LDS footprint admits no more), each walks tiles b, b + grid, ...
+    return conv_launch<conv_halo_ld_kernel<MF, TH, TW>>(nblk, 1, 768, lds, stream, 2.0 * a.P * a.Cout * (double)a.Cin * a.ntaps, conv_prof_bytes(a, a.P),
+                                                        {a.P, a.Cout, a.Cin, a.ntaps, a.stride, a.OH, 3128256}, a, x_bytes, w_bytes);
 }
 
 template <class MF, int BC, int BP, int WGC, int WGP>
@@ -997,17 +760,9 @@ static int launch_k64(ConvArgs& a, unsigned x_bytes, unsigned w_bytes, hipStream
     a.ctiles = (a.Cout + BC - 1) / BC;
     a.ptiles = (a.P + BP - 1) / BP;
     const int64_t nblk = (int64_t)a.ptiles * a.ctiles;
-    if (nblk > INT32_MAX) return sbg_fail(SBG_ERR_INVALID, "conv2d_igemm: grid too large");
-    auto kern = conv_k64_kernel<MF, BC, BP, WGC, WGP>;
-    if (!SBG_RAISE_LDS_ONCE(kern, lds))
-        return sbg_fail(SBG_ERR_LAUNCH, "conv2d_igemm: cannot raise the dynamic LDS limit to %d bytes", lds);
-    const double ys = a.ydtype == SBG_F32 ? 4.0 : 2.0;
-    SbgProfScope prof(stream, SBG_K_CONV_IGEMM, 2.0 * a.P * a.Cout * (double)a.Cin * a.ntaps,
-                      2.0 * a.N * a.IH * a.IW * (double)a.Cin + 2.0 * a.ntaps * a.Cout * (double)a.Cin + ys * a.P * (double)a.Cout * (a.accumulate ? 2 : 1),
-                      {a.P, a.Cout, a.Cin, a.ntaps, a.stride, a.OH, 1000000 + BC * 1000 + BP});
-    SBG_LAUNCH(kern, dim3((unsigned)nblk, (unsigned)(a.ksplit > 1 ? a.ksplit : 1)), dim3(512), lds, stream, a, x_bytes, w_bytes);
-    SBG_HIP_LAUNCH_CHECK();
-    return SBG_OK;
+    return conv_launch<conv_k64_kernel<MF, BC, BP, WGC, WGP>>(nblk, (unsigned)(a.ksplit > 1 ? a.ksplit : 1), 512, lds, stream,
+                                                              2.0 * a.P * a.Cout * (double)a.Cin * a.ntaps, conv_prof_bytes(a, a.P),
+                                                              {a.P, a.Cout, a.Cin, a.ntaps, a.stride, a.OH, 1000000 + BC * 1000 + BP}, a, x_bytes, w_bytes);
 }
 
 // y[i] (+)= sum_k ws[k][i] in a fixed order; 16 lanes share an output element (slabs k, k + 16, ...), then a shuffle tree.
@@ -1043,16 +798,7 @@ __global__ __launch_bounds__(256) void conv_ksplit_reduce_epi_kernel(const float
         const int img = (int)(pix / hw), pp = (int)(pix - (int64_t)img * hw);
         const float nz = p.noise ? p.noise[(int64_t)img * p.noise_sn + pp] : 0.f;
 #pragma unroll
-        for (int e = 0; e < 8; e++) {
-            float u = acc[e];
-            if (p.oscale) u *= p.oscale[(int64_t)img * p.Cout + co + e];
-            u += nz + (p.bias ? p.bias[co + e] : 0.f);
-            if (p.act == SBG_ACT_LRELU) u = (u > 0.f) ? u : u * p.alpha;
-            else if (p.act == SBG_ACT_RELU) u = (u > 0.f) ? u : 0.f;
-            u *= p.gain;
-            if (p.clamp >= 0.f) u = (u > -p.clamp && u < p.clamp) ? u : (u >= 0.f ? p.clamp : -p.clamp);
-            acc[e] = u;
-        }
+        for (int e = 0; e < 8; e++) acc[e] = tail(p, acc[e], (int64_t)img * p.Cout + co + e, nz + (p.bias ? p.bias[co + e] : 0.f));
         if (p.ydtype == SBG_F32)       Vec8<float>::st((float*)p.y + i, acc);
         else if (p.ydtype == SBG_BF16) Vec8<bf16_s>::st((bf16_s*)p.y + i, acc);
         else                           Vec8<f16_s>::st((f16_s*)p.y + i, acc);
@@ -1106,8 +852,7 @@ int sbg_conv_k64_dispatch(ConvArgs& a, bool bf16, int64_t x_bytes, int64_t w_byt
     const unsigned xb = (unsigned)x_bytes, wb = (unsigned)w_bytes;
     const int64_t y_numel = (int64_t)a.P * a.Cout;
     const bool dense_y = a.ys_w == a.Cout && a.ys_h == (int64_t)a.OW * a.Cout && a.ys_n == (int64_t)a.OH * a.OW * a.Cout;
-    const bool plain = (a.act <= SBG_ACT_LINEAR) && a.gain == 1.f && a.clamp < 0.f && !a.bias && !a.noise && !a.oscale;
-    const bool simple = a.ydtype == SBG_F32 && plain;                      // plain fp32 sum (may accumulate); otherwise the epilogue rides in the reduction
+    const bool simple = a.ydtype == SBG_F32 && conv_is_plain(a);                      // plain fp32 sum (may accumulate); otherwise the epilogue rides in the reduction
     const bool epi_ok = !a.accumulate && (a.Cout & 7) == 0 && (((uintptr_t)a.y) & 15) == 0;
     const int k = (workspace && dense_y && (simple || epi_ok)) ? plan_ksplit(a, ksplit) : 1;
     if (k > 1) {

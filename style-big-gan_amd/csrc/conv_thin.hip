@@ -119,7 +119,7 @@ __global__ __launch_bounds__(256) void conv_thin_kernel(ConvArgs p, int pitch)  
     }
 
     // ---- epilogue: lane holds output channels 16 i + 4 fg + {0..3} of pixel (fragment j, column fi)
-    const bool plain = (p.act <= SBG_ACT_LINEAR) && p.gain == 1.f && p.clamp < 0.f && !p.bias && !p.noise && !p.oscale;
+    const bool plain = SBG_CONV_IS_PLAIN(p);
     const float alpha = (p.act == SBG_ACT_LRELU) ? p.alpha : (p.act == SBG_ACT_RELU ? 0.f : 1.f);
     const float cl = p.clamp >= 0.f ? p.clamp : __builtin_inff();
     const bool vec_ok = ((p.Cout & 3) == 0) && (((p.ys_n | p.ys_h | p.ys_w | yoff) & 3) == 0) && ((((uintptr_t)p.y) & 15) == 0);
@@ -169,19 +169,21 @@ __global__ __launch_bounds__(256) void conv_thin_kernel(ConvArgs p, int pitch)  
 }
 
 template <class MF, int TC, int TP>
-static int launch_thin(const ConvArgs& a, int maxP, int pitch, int lds, hipStream_t stream)
+static int launch_thin(const ConvArgs& a, int pitch, int lds, hipStream_t stream)
 {
-    auto kern = conv_thin_kernel<MF, TC, TP>;
-    if (lds > 64 * 1024 && !SBG_RAISE_LDS_ONCE(kern, lds))
-        return sbg_fail(SBG_ERR_LAUNCH, "conv2d_igemm: cannot raise the dynamic LDS limit to %d bytes", lds);
     int maxOH = a.OH, maxOW = a.OW;
-    if (a.nphase > 1) { maxOH = maxOW = 0; for (int i = 0; i < a.nphase; i++) { if (a.ph_OH[i] > maxOH) maxOH = a.ph_OH[i]; if (a.ph_OW[i] > maxOW) maxOW = a.ph_OW[i]; } }
+    double macs = (double)a.P * a.ntaps, outpix = a.P;
+    if (a.nphase > 1) {
+        maxOH = maxOW = 0; macs = outpix = 0.0;
+        for (int i = 0; i < a.nphase; i++) {
+            if (a.ph_OH[i] > maxOH) maxOH = a.ph_OH[i];
+            if (a.ph_OW[i] > maxOW) maxOW = a.ph_OW[i];
+            macs += (double)a.ph_P[i] * a.ph_ntaps[i]; outpix += a.ph_P[i];
+        }
+    }
     const int64_t nblk = (int64_t)a.N * ((maxOH + 4 * TP - 1) / (4 * TP)) * ((maxOW + 15) / 16);     // a phase with a smaller grid leaves its surplus workgroups idle
-    if (nblk > INT32_MAX || nblk < 1) return sbg_fail(SBG_ERR_INVALID, "conv2d_igemm: grid too large");
-    const dim3 grid((unsigned)nblk, (unsigned)(a.nphase > 1 ? a.nphase : 1));
-    SBG_LAUNCH(kern, grid, dim3(256), lds, stream, a, pitch);
-    SBG_HIP_LAUNCH_CHECK();
-    return SBG_OK;
+    return conv_launch<conv_thin_kernel<MF, TC, TP>>(nblk, (unsigned)(a.nphase > 1 ? a.nphase : 1), 256, lds, stream, 2.0 * macs * a.Cout * (double)a.Cin,
+                                                     conv_prof_bytes(a, outpix), {(int)outpix, a.Cout, a.Cin, a.ntaps, a.stride, a.OH, 6000000 + TC * 16}, a, pitch);
 }
 
 } // namespace
@@ -207,20 +209,13 @@ int sbg_conv_thin_dispatch(ConvArgs& a, bool bf16, hipStream_t stream)
     const int tc = (a.Cout + 15) >> 4;
     const int TCs = tc <= 1 ? 1 : (tc <= 2 ? 2 : 4);
     const int lds = 16 * TCs * pitch * 2;
-    const double ys = a.ydtype == SBG_F32 ? 4.0 : 2.0;
-    double macs = 0.0, outpix = 0.0;
-    if (a.nphase > 1) { for (int i = 0; i < a.nphase; i++) { macs += (double)a.ph_P[i] * a.ph_ntaps[i]; outpix += a.ph_P[i]; } }
-    else { macs = (double)a.P * a.ntaps; outpix = a.P; }
-    SbgProfScope prof(stream, SBG_K_CONV_IGEMM, 2.0 * macs * a.Cout * (double)a.Cin,
-                      2.0 * a.N * a.IH * a.IW * (double)a.Cin + 2.0 * a.ntaps * a.Cout * (double)a.Cin + ys * outpix * (double)a.Cout * (a.accumulate ? 2 : 1),
-                      {(int)outpix, a.Cout, a.Cin, a.ntaps, a.stride, a.OH, 6000000 + TCs * 16});
     // four pixel fragments per wave (eight, sharing the A fragment read and the tap decode over twice the pixels, measured no better: DESIGN.md)
     if (bf16) {
-        if (TCs == 1) return launch_thin<bf16_mfma, 1, 4>(a, maxP, pitch, lds, stream);
-        if (TCs == 2) return launch_thin<bf16_mfma, 2, 4>(a, maxP, pitch, lds, stream);
-        return launch_thin<bf16_mfma, 4, 4>(a, maxP, pitch, lds, stream);
+        if (TCs == 1) return launch_thin<bf16_mfma, 1, 4>(a, pitch, lds, stream);
+        if (TCs == 2) return launch_thin<bf16_mfma, 2, 4>(a, pitch, lds, stream);
+        return launch_thin<bf16_mfma, 4, 4>(a, pitch, lds, stream);
     }
-    if (TCs == 1) return launch_thin<f16_mfma, 1, 4>(a, maxP, pitch, lds, stream);
-    if (TCs == 2) return launch_thin<f16_mfma, 2, 4>(a, maxP, pitch, lds, stream);
-    return launch_thin<f16_mfma, 4, 4>(a, maxP, pitch, lds, stream);
+    if (TCs == 1) return launch_thin<f16_mfma, 1, 4>(a, pitch, lds, stream);
+    if (TCs == 2) return launch_thin<f16_mfma, 2, 4>(a, pitch, lds, stream);
+    return launch_thin<f16_mfma, 4, 4>(a, pitch, lds, stream);
 }

@@ -19,33 +19,13 @@
 // the weights of step s were the last thing step s - 3 issued, so they (and every halo piece before them) have landed once at most
 // cnt(s - 2) + cnt(s - 1) loads are outstanding.
 //
-// Accumulator layout and channel permutation of the weight rows are those of conv_k64.hip, so its epilogue is reused per phase.
-#include "conv_common.h"
-#include "lds_asm.h"
-#include <cstdlib>
-#include <utility>
+// Accumulator layout and channel permutation of the weight rows are those of conv_k64.hip (conv_device.h); the store is this file's own
+// (store_phase: no fused tail, bounds tests of the phase grids).
+#include "conv_device.h"
 
 using namespace sbgconv;
 
-// from conv_k64.hip (same translation-unit-local helpers, restated: 30 lines are cheaper than a shared header with the epilogue's templates)
 namespace {
-
-typedef __attribute__((address_space(3))) void* lds_void_ptr;
-#define SBG_OOB_OFFSET 0x80000000u
-
-static __device__ __forceinline__ int chmap(int R) { return (R & ~31) + 8 * ((R & 15) >> 2) + 4 * ((R >> 4) & 1) + (R & 3); }
-
-template <int OFF>
-static __device__ __forceinline__ void lds_read128_issue(short8_t& d, unsigned addr)
-{
-    static_assert(OFF >= 0 && OFF < 65536, "16-bit offset field");
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF) : "memory");
-}
-template <int N>
-static __device__ __forceinline__ void lds_wait6(short8_t& a0, short8_t& a1, short8_t& b0, short8_t& b1, short8_t& b2, short8_t& b3)
-{
-    asm volatile("s_waitcnt lgkmcnt(%6)" : "+v"(a0), "+v"(a1), "+v"(b0), "+v"(b1), "+v"(b2), "+v"(b3) : "n"(N) : "memory");
-}
 
 // store of one phase: lane (fr, fg) holds, for the pixel of fragment column fr in segment j, channels cbase + 8 fg + e with e = 0..3 in
 // acc[0][j] and e = 4..7 in acc[1][j] (conv_k64.hip's layout with TC = 2)
@@ -99,8 +79,8 @@ __global__ __launch_bounds__(512) void conv_up2_kernel(ConvArgs p, unsigned x_by
 
     __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, (int)x_bytes, 0x00020000);
     __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, (int)w_bytes, 0x00020000);
-    const int lrow = lane >> 3;
-    const int src_k = ((lane & 7) ^ lrow) * 8;          // DMA lane -> (row = 8 piece + lrow, slot = lane & 7), source k-slot = slot ^ (row & 7)
+    const int lrow = dma_lrow(lane);
+    const int src_k = dma_src_k(lane, lrow);            // DMA lane coordinates
 
     // ---- weight rows of this wave: piece `wave` (rows 8 wave + lrow) of every tap tile; per tap the slab offset
     unsigned wrow;                                       // byte offset of (channel row, src_k) inside a slab, or out of range
@@ -182,7 +162,7 @@ __global__ __launch_bounds__(512) void conv_up2_kernel(ConvArgs p, unsigned x_by
             constexpr int k = decltype(kt)::value;
             // cnt(k) = 4 for k < 3, else 2;  allowed outstanding = cnt(k - 2) + cnt(k - 1) (indices mod 5)
             constexpr int allowed = (k == 0) ? 4 : (k == 1) ? 6 : (k == 2) ? 8 : (k == 3) ? 8 : 6;
-            asm volatile("s_waitcnt vmcnt(%0)" :: "n"(allowed) : "memory");
+            wait_vmcnt_const<allowed>();
             __builtin_amdgcn_s_barrier();
             // ---- loads: [halo pieces of slice c + 1 -> the other buffer] [weights of step s + 3 -> the slot step s - 1 used].  `late`: one
             // DMA instruction behind each group of eight MFMAs instead of all four in front of the step's first fragment read (experiment)
@@ -238,7 +218,7 @@ __global__ __launch_bounds__(512) void conv_up2_kernel(ConvArgs p, unsigned x_by
             slot = (slot + 1) & (NRING - 1);
         });
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the spare loads of the last steps: nothing of this workgroup's LDS may be written after it ends
+    wait_vmcnt_const<0>();                               // the spare loads of the last steps: nothing of this workgroup's LDS may be written after it ends
 
     // ---- epilogue: phase ph -> output pixels (oy, ox) of its grid, offset ph_yoff, strides already those of the phase grid
 #pragma unroll
@@ -252,45 +232,61 @@ static int launch_up2(const ConvArgs& a, unsigned x_bytes, unsigned w_bytes, int
     constexpr int lds = 2 * 38 * 1024 + 4 * 16384 + 1024;
     const int tiles_y = Hm / 8, tiles_x = Wm / 32;
     const int64_t nblk = (int64_t)a.N * tiles_y * tiles_x * a.ctiles;
-    if (nblk > INT32_MAX || nblk < 1) return sbg_fail(SBG_ERR_INVALID, "conv2d_igemm: grid too large");
     const double ys = a.ydtype == SBG_F32 ? 4.0 : 2.0, pix = (double)a.N * Hm * Wm;
-    SbgProfScope prof(stream, SBG_K_CONV_IGEMM, 2.0 * 9.0 * pix * a.Cout * (double)a.Cin,
-                      2.0 * a.N * a.IH * a.IW * (double)a.Cin + 2.0 * 9 * a.Cout * (double)a.Cin + ys * 4.0 * pix * (double)a.Cout,
-                      {(int)(4.0 * pix), a.Cout, a.Cin, 9, 2, Hm, 9064256});      // 9xxxxxx = conv_up2_kernel (profiles/summarize.py)
-#define SBG_UP2_LAUNCH(YDT) do { auto kern = conv_up2_kernel<MF, YDT>; \
-        if (!SBG_RAISE_LDS_ONCE(kern, lds)) return sbg_fail(SBG_ERR_LAUNCH, "conv2d_igemm: cannot raise the dynamic LDS limit to %d bytes", lds); \
-        SBG_LAUNCH(kern, dim3((unsigned)nblk), dim3(512), lds, stream, a, x_bytes, w_bytes, tiles_y, tiles_x, dymin, dxmin); } while (0)
-    if (a.ydtype == SBG_F32) SBG_UP2_LAUNCH(SBG_F32); else if (a.ydtype == SBG_BF16) SBG_UP2_LAUNCH(SBG_BF16); else SBG_UP2_LAUNCH(SBG_F16);
+    const double flops = 2.0 * 9.0 * pix * a.Cout * (double)a.Cin;
+    const double bytes = 2.0 * a.N * a.IH * a.IW * (double)a.Cin + 2.0 * 9 * a.Cout * (double)a.Cin + ys * 4.0 * pix * (double)a.Cout;
+#define SBG_UP2_LAUNCH(YDT) conv_launch<conv_up2_kernel<MF, YDT>>(nblk, 1, 512, lds, stream, flops, bytes, {(int)(4.0 * pix), a.Cout, a.Cin, 9, 2, Hm, 9064256}, \
+                                                                  a, x_bytes, w_bytes, tiles_y, tiles_x, dymin, dxmin)      // 9xxxxxx = conv_up2_kernel (profiles/summarize.py)
+    if (a.ydtype == SBG_F32) return SBG_UP2_LAUNCH(SBG_F32);
+    if (a.ydtype == SBG_BF16) return SBG_UP2_LAUNCH(SBG_BF16);
+    return SBG_UP2_LAUNCH(SBG_F16);
 #undef SBG_UP2_LAUNCH
-    SBG_HIP_LAUNCH_CHECK();
-    return SBG_OK;
 }
 
 } // namespace
 
-// Returns SBG_OK / an error, or -1 when the launch is not a 4 / 2 / 2 / 1-tap stride-2 transposed convolution this kernel covers.  On
+// Is the launch a 4 / 2 / 2 / 1-tap stride-2 transposed convolution whose nine taps lie in one 2 x 2 window, in tensors this file's kernel can address?
+static bool up2_form(const ConvArgs& a, int64_t x_bytes, int64_t w_bytes, int& dymin, int& dxmin)
+{
+    if (a.nphase != 4 || a.stride != 1 || a.ksplit > 1 || a.accumulate) return false;
+    if (a.ph_ntaps[0] != 4 || a.ph_ntaps[1] != 2 || a.ph_ntaps[2] != 2 || a.ph_ntaps[3] != 1) return false;
+    if ((a.Cout % 8) != 0 || (a.Cin % 8) != 0 || a.Cout < 64 || a.Cin < 64) return false;
+    if (x_bytes >= (int64_t)SBG_OOB_OFFSET || w_bytes >= (int64_t)SBG_OOB_OFFSET) return false;
+    if ((((uintptr_t)a.y) & 15) != 0 || ((a.ys_n | a.ys_h | a.ys_w) & 7) != 0) return false;
+    dymin = a.tap_dy[0]; dxmin = a.tap_dx[0];
+    for (int t = 0; t < 9; t++) { if (a.tap_dy[t] < dymin) dymin = a.tap_dy[t]; if (a.tap_dx[t] < dxmin) dxmin = a.tap_dx[t]; }
+    for (int t = 0; t < 9; t++) if (a.tap_dy[t] - dymin > 1 || a.tap_dx[t] - dxmin > 1) return false;
+    for (int i = 0; i < 4; i++) if (a.ph_tap0[i] != (i == 0 ? 0 : i == 1 ? 4 : i == 2 ? 6 : 8)) return false;
+    return true;
+}
+
+// Canonical tap order of such a launch: inside every phase by (dy, dx).  The entry point calls this BEFORE it offers the launch to any kernel, and
+// it either orders the whole table or leaves it alone: the order in which a phase's taps are accumulated (and so the rounding of the sum) is then
+// the same whichever kernel takes the launch -- sbg_conv_up2_dispatch below, which relies on it, or the multi-phase gather kernel of conv_k64.hip
+// when that one declines (grids under 8 x 32).  Returns whether the launch is of the form.
+bool sbg_conv_up2_canonical_taps(ConvArgs& a, int64_t x_bytes, int64_t w_bytes)
+{
+    int dymin, dxmin;
+    if (!up2_form(a, x_bytes, w_bytes, dymin, dxmin)) return false;
+    for (int i = 0; i < 4; i++)
+        for (int u = a.ph_tap0[i]; u < a.ph_tap0[i] + a.ph_ntaps[i]; u++)
+            for (int v = u + 1; v < a.ph_tap0[i] + a.ph_ntaps[i]; v++)
+                if (a.tap_dy[v] < a.tap_dy[u] || (a.tap_dy[v] == a.tap_dy[u] && a.tap_dx[v] < a.tap_dx[u])) {
+                    std::swap(a.tap_dy[u], a.tap_dy[v]); std::swap(a.tap_dx[u], a.tap_dx[v]); std::swap(a.tap_slab[u], a.tap_slab[v]);
+                }
+    return true;
+}
+
+// Returns SBG_OK / an error, or -1 when the launch is not a 4 / 2 / 2 / 1-tap stride-2 transposed convolution this kernel covers (it reads the
+// tap table and never reorders it: a launch whose taps are not in canonical order is declined).  On
 // success the region [0, Hm) x [0, Wm) of every phase grid has been written; `border` receives the (up to four) rectangles that remain --
 // the last row of the phases that have Hm + 1 rows, the last column of those with Wm + 1 columns -- as phases of an ordinary launch.
 int sbg_conv_up2_dispatch(ConvArgs& a, bool bf16, int64_t x_bytes, int64_t w_bytes, sbg_conv_params* border, const sbg_conv_params* q, hipStream_t stream)
 {
-    if (a.nphase != 4 || a.stride != 1 || a.ksplit > 1 || a.accumulate) return -1;
-    if (a.ph_ntaps[0] != 4 || a.ph_ntaps[1] != 2 || a.ph_ntaps[2] != 2 || a.ph_ntaps[3] != 1) return -1;
-    if ((a.Cout % 8) != 0 || (a.Cin % 8) != 0 || a.Cout < 64 || a.Cin < 64) return -1;
-    if (x_bytes >= (int64_t)SBG_OOB_OFFSET || w_bytes >= (int64_t)SBG_OOB_OFFSET) return -1;
-    if ((((uintptr_t)a.y) & 15) != 0 || ((a.ys_n | a.ys_h | a.ys_w) & 7) != 0) return -1;
-    int dymin = a.tap_dy[0], dxmin = a.tap_dx[0];
-    for (int t = 0; t < 9; t++) { if (a.tap_dy[t] < dymin) dymin = a.tap_dy[t]; if (a.tap_dx[t] < dxmin) dxmin = a.tap_dx[t]; }
-    for (int t = 0; t < 9; t++) if (a.tap_dy[t] - dymin > 1 || a.tap_dx[t] - dxmin > 1) return -1;
-    {   // canonical tap order: inside every phase by (dy, dx); the window shifts must then read 0 1 2 3 | 1 3 | 2 3 | 3 (the kernel hard-codes them)
+    int dymin, dxmin;
+    if (!up2_form(a, x_bytes, w_bytes, dymin, dxmin)) return -1;
+    {   // the window shifts must read 0 1 2 3 | 1 3 | 2 3 | 3 (the kernel hard-codes them)
         static const int want[9] = {0, 1, 2, 3, 1, 3, 2, 3, 3};
-        for (int i = 0; i < 4; i++) {
-            if (a.ph_tap0[i] != (i == 0 ? 0 : i == 1 ? 4 : i == 2 ? 6 : 8)) return -1;
-            for (int u = a.ph_tap0[i]; u < a.ph_tap0[i] + a.ph_ntaps[i]; u++)
-                for (int v = u + 1; v < a.ph_tap0[i] + a.ph_ntaps[i]; v++)
-                    if (a.tap_dy[v] < a.tap_dy[u] || (a.tap_dy[v] == a.tap_dy[u] && a.tap_dx[v] < a.tap_dx[u])) {
-                        std::swap(a.tap_dy[u], a.tap_dy[v]); std::swap(a.tap_dx[u], a.tap_dx[v]); std::swap(a.tap_slab[u], a.tap_slab[v]);
-                    }
-        }
         for (int t = 0; t < 9; t++) if ((a.tap_dy[t] - dymin) * 2 + (a.tap_dx[t] - dxmin) != want[t]) return -1;
     }
     int Hm = a.ph_OH[0], Wm = a.ph_OW[0];

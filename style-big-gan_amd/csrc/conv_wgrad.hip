@@ -16,9 +16,8 @@
 // registers), walking its share of the pixel axis in 32-pixel chunks: the a-tile is staged once per chunk and re-used by
 // every tap, only the gathered b-tiles change.  The pixel axis is split over gridDim.z workgroups that write fp32
 // partial slabs; a second kernel sums the slabs in a fixed order (bitwise reproducible, no float atomics).
-#include "sbg_common.h"
+#include "conv_common.h"
 #include "lds_asm.h"
-#include <cstdlib>
 
 namespace {
 
@@ -226,8 +225,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradArgs p)
 // LDS rows are 128 B (64 channels) and cannot be padded under LDS-DMA, so the 16-B chunk pairs of row R are XOR-swizzled by
 // (R >> 1) & 3 on the source side and in the transposing reads: any 8 consecutive rows then cover 8 distinct 32-B bank slots.
 
-typedef __attribute__((address_space(3))) void* lds_void_ptr;
-#define SBG_OOB_OFFSET 0x80000000u
+using sbgconv::lds_void_ptr;      // (and SBG_OOB_OFFSET: conv_common.h)
 
 template <class MF, int S, int BCA, int NSTAGE>
 __global__ __launch_bounds__(512) void conv_wgrad_rows_kernel(WgradArgs p, unsigned a_bytes, unsigned b_bytes)

@@ -128,6 +128,9 @@ static inline unsigned sbg_stream_grid(int64_t work_items, int block)
     return (unsigned)(need < cap ? need : cap);
 }
 
+// Compute units of the current device, queried once (256 when the query fails): the grid of the persistent kernels.
+int sbg_cu_count();
+
 // ------------------------------------------------------------------------------------------------
 // Launch timing (see sbg_prof_* in include/sbg_hip.h).  Usage: { SbgProfScope prof(stream, kind, flops, bytes, dims); launch; }
 bool sbg_prof_on();

@@ -21,6 +21,16 @@ bool sbg_launch_geometry_ok(dim3 grid, dim3 block, size_t lds_bytes, const char*
     return ok;
 }
 
+int sbg_cu_count()
+{
+    static const int ncu = [] {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+        return n;
+    }();
+    return ncu;
+}
+
 extern "C" const char* sbg_last_error(void) { return sbg_err_slot().c_str(); }
 
 // ------------------------------------------------------------------------------------------------
