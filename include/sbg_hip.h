@@ -479,6 +479,10 @@ enum sbg_kernel_kind {
 /* Kernel-variant codes in the records of the streaming kernels (which kernel served the launch):
  *   bias_act     dims[4] = 1 vec8 / 2 scalar,  dims[5] = bias mode (0 none, 1 channel-minor vector, 2 one per 8-vector, 3 generic)
  *   scale_nc     dims[4] = 1 vec8 / 2 scalar
+ *   upfirdn2d    dims[6] = 10000 * variant + 16 * upx + downx: 1 sliding-window matrix-core FIR / 3 the same plus the register-blocked kernel
+ *                on 1..4 edge columns / 5 register-blocked 4x4 / 6 register-blocked, any size up to 8x8 / 7 generic, 8 channels per lane /
+ *                8 generic, scalar.  2 and 4 (the tile matrix-core kernel alone / with edge columns) are retired and not reused: logs
+ *                recorded before its removal carry them; those launches (8..15 output rows) now log 1 and 3
  *   dot_hw       dims[4] = 1 generic / 2 lane per channel vector / 3 serial channel vectors,  dims[5] = pixel splits
  *                (dims[3] = layout, 3 dot_hw_scale, 2 modconv_bwd, 4 modconv_bwd_prescaled, 5 moments_hw: dims[4] = 1 vec8 / 2 scalar)
  *   weight_prep  pack (dims[3] = 0): dims[4] = 1 transposing LDS tiles / 2 one lane per (row, column)

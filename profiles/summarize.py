@@ -14,6 +14,7 @@ import collections, csv, glob, json, os, shutil, sys
 
 out, tag = sys.argv[1], sys.argv[2]
 here = os.path.dirname(os.path.abspath(__file__))
+# (substring match, first hit wins; kernels that no longer exist -- upfirdn2d_fir_mfma_kernel, upfirdn2d_fir_fixed_kernel -- stay so that old traces still summarise)
 FAMILIES = ('conv_thin_kernel', 'conv_up2_kernel', 'conv_halo8_kernel', 'upfirdn2d_fir_slide_kernel', 'conv_halo_ld_kernel', 'conv_gather_ld_kernel', 'conv_k64_kernel', 'conv_ksplit_reduce', 'upfirdn2d_fir_mfma_kernel',
             'upfirdn2d_fir_fixed_kernel', 'modconv_bwd_kernel', 'conv_igemm_kernel', 'conv_wgrad_rows_kernel', 'conv_wgrad_halo_kernel',
             'conv_wgrad_kernel', 'wgrad_reduce_kernel', 'upfirdn2d_fir_kernel', 'upfirdn2d_kernel', 'attention_bwd', 'attention_fwd', 'mbstd', 'bias_act', 'scale_nc', 'dot_hw')

@@ -12,6 +12,11 @@
 //    effective footprint is re-used out of L1/L2 (each input line is touched by <= fh*fw/(up*up) neighbouring lanes).
 //  * planar (NCHW) activations: one lane = one output pixel of one channel, lanes walk x (coalesced along rows).
 //  * the filter lives in LDS (<= 1024 taps) and is read with wave-uniform addresses (broadcast, conflict-free).
+// Three kernels, most general first, and one dispatch (launch_upfirdn):
+//   upfirdn2d_kernel<T,VEC>            any configuration; 8 channels per lane on channel-minor tensors, else one element
+//   upfirdn2d_fir_kernel<T,FH,FW>      up == down == 1, channel-minor: register-blocked patch per lane; 4 x 4 at compile time or any size up to 8 x 8
+//   upfirdn2d_fir_slide_kernel<T,BT>   the 4 x 4 low-pass on the matrix cores with the fused forward / backward tails; fir_mfma_accepts() is the one
+//                                      statement of which launches it takes, asked by the dispatch, both probe entry points and the entry point's checks
 #include "sbg_common.h"
 #include "lds_asm.h"
 #include <cstdlib>
@@ -109,20 +114,39 @@ __global__ __launch_bounds__(256) void upfirdn2d_kernel(UpfirdnArgs p)
 // convolution, and their gradients), channel-minor, 8 channels per lane.  Each lane produces a TY x TX patch of output
 // pixels from a (TY + fh - 1) x (TX + fw - 1) input window held in registers: for the 4x4 filter that is 35 16-B loads per 8
 // outputs (4.4 per output instead of 16; an 8-wide patch measured slower), every load 256-B-contiguous across the 16 lanes that share a pixel.
+// FH x FW is the filter size at compile time (4 x 4: the [1, 3, 3, 1] low-pass of every up / down layer) -- the window loops unroll, the
+// taps live in registers and the tap-range tests fold away -- or 0 x 0 for any size up to FIR_MAXF read from p.fh / p.fw, taps in LDS.
+// The bounds tests stay branches around each load, which also keeps the loads in program order (bounded live set).
 #define FIR_TX 4
 #define FIR_TY 2
 #define FIR_MAXF 8
-template <class T>
+template <class T, int FH, int FW>
 __global__ __launch_bounds__(256) void upfirdn2d_fir_kernel(UpfirdnArgs p, int xblocks, int yblocks)
 {
+    constexpr bool FIXED = FH > 0;
+    constexpr int UNROLL_Y = FIXED ? FIR_TY + FH - 1 : 1, UNROLL_X = FIXED ? FIR_TX + FW - 1 : 1;        // 1 = leave the run-time loops rolled
+    const int fh = FIXED ? FH : p.fh, fw = FIXED ? FW : p.fw;
+    // taps in visiting order, gain folded in: [ky][kx] multiplies the window pixel (.. + ky, .. + kx)
     __shared__ float sf[FIR_MAXF * FIR_MAXF];
-    const int ntaps = p.fw * p.fh;
-    for (int t = threadIdx.x; t < ntaps; t += blockDim.x) {
-        int ky = t / p.fw, kx = t - ky * p.fw;
-        int fy = p.flip ? ky : p.fh - 1 - ky, fx = p.flip ? kx : p.fw - 1 - kx;
-        sf[t] = p.f[fy * p.fsy + fx * p.fsx] * p.gain;
+    float fv[FIXED ? FH : 1][FIXED ? FW : 1];
+    if constexpr (FIXED) {
+#pragma unroll
+        for (int ky = 0; ky < FH; ky++)
+#pragma unroll
+            for (int kx = 0; kx < FW; kx++) {
+                const int fy = p.flip ? ky : FH - 1 - ky, fx = p.flip ? kx : FW - 1 - kx;
+                fv[ky][kx] = p.f[fy * p.fsy + fx * p.fsx] * p.gain;
+            }
+    } else {
+        const int ntaps = p.fw * p.fh;
+        for (int t = threadIdx.x; t < ntaps; t += blockDim.x) {
+            int ky = t / p.fw, kx = t - ky * p.fw;
+            int fy = p.flip ? ky : p.fh - 1 - ky, fx = p.flip ? kx : p.fw - 1 - kx;
+            sf[t] = p.f[fy * p.fsy + fx * p.fsx] * p.gain;
+        }
+        __syncthreads();
     }
-    __syncthreads();
+    auto tap = [&](int ky, int kx) { if constexpr (FIXED) return fv[ky][kx]; else return sf[ky * fw + kx]; };
     const T* px = (const T*)p.x; T* py = (T*)p.y;
     const int cvecs = p.C >> 3;
     const int64_t step = (int64_t)gridDim.x * blockDim.x;
@@ -140,10 +164,12 @@ __global__ __launch_bounds__(256) void upfirdn2d_fir_kernel(UpfirdnArgs p, int x
 #pragma unroll
                 for (int e = 0; e < 8; e++) acc[a][b][e] = 0.f;
         const T* xin = px + n * p.isn + c;
-        for (int wy = 0; wy < FIR_TY + p.fh - 1; wy++) {           // input window rows
+#pragma unroll UNROLL_Y
+        for (int wy = 0; wy < FIR_TY + fh - 1; wy++) {           // input window rows
             const int iy = oy0 + wy - p.pady0;
             if ((unsigned)iy >= (unsigned)p.inH) continue;
-            for (int wx = 0; wx < FIR_TX + p.fw - 1; wx++) {
+#pragma unroll UNROLL_X
+            for (int wx = 0; wx < FIR_TX + fw - 1; wx++) {
                 const int ix = ox0 + wx - p.padx0;
                 if ((unsigned)ix >= (unsigned)p.inW) continue;
                 float v[8];
@@ -151,83 +177,13 @@ __global__ __launch_bounds__(256) void upfirdn2d_fir_kernel(UpfirdnArgs p, int x
 #pragma unroll
                 for (int a = 0; a < FIR_TY; a++) {
                     const int ky = wy - a;
-                    if (ky < 0 || ky >= p.fh) continue;
+                    if (ky < 0 || ky >= fh) continue;
 #pragma unroll
                     for (int b = 0; b < FIR_TX; b++) {
                         const int kx = wx - b;
-                        if (kx < 0 || kx >= p.fw) continue;
-                        const float fv = sf[ky * p.fw + kx];
+                        if (kx < 0 || kx >= fw) continue;
 #pragma unroll
-                        for (int e = 0; e < 8; e++) acc[a][b][e] += v[e] * fv;
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int a = 0; a < FIR_TY; a++) {
-            const int oy = oy0 + a;
-            if (oy >= p.outH) continue;
-#pragma unroll
-            for (int b = 0; b < FIR_TX; b++) {
-                const int ox = ox0 + b;
-                if (ox >= p.outW) continue;
-                Vec8<T>::st(py + n * p.osn + c + oy * p.osy + ox * p.osx, acc[a][b]);
-            }
-        }
-    }
-}
-
-// The register-blocked kernel with the filter size known at compile time (4 x 4: the [1, 3, 3, 1] low-pass of every up / down
-// layer): the window loops unroll, the taps live in registers and the tap-range tests fold away.  The bounds tests stay branches
-// around each load, which also keeps the loads in program order (bounded live set).
-template <class T, int FH, int FW>
-__global__ __launch_bounds__(256) void upfirdn2d_fir_fixed_kernel(UpfirdnArgs p, int xblocks, int yblocks)
-{
-    float fv[FH][FW];                                   // visiting order: fv[ky][kx] multiplies the window pixel (.. + ky, .. + kx)
-#pragma unroll
-    for (int ky = 0; ky < FH; ky++)
-#pragma unroll
-        for (int kx = 0; kx < FW; kx++) {
-            const int fy = p.flip ? ky : FH - 1 - ky, fx = p.flip ? kx : FW - 1 - kx;
-            fv[ky][kx] = p.f[fy * p.fsy + fx * p.fsx] * p.gain;
-        }
-    const T* px = (const T*)p.x; T* py = (T*)p.y;
-    const int cvecs = p.C >> 3;
-    const int64_t step = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < p.total; idx += step) {
-        int64_t r = idx;
-        const int c = (int)(r % cvecs) << 3; r /= cvecs;
-        const int xb = (int)(r % xblocks); r /= xblocks;
-        const int yb = (int)(r % yblocks); const int n = (int)(r / yblocks);
-        const int ox0 = xb * FIR_TX, oy0 = yb * FIR_TY;
-        float acc[FIR_TY][FIR_TX][8];
-#pragma unroll
-        for (int a = 0; a < FIR_TY; a++)
-#pragma unroll
-            for (int b = 0; b < FIR_TX; b++)
-#pragma unroll
-                for (int e = 0; e < 8; e++) acc[a][b][e] = 0.f;
-        const T* xin = px + n * p.isn + c;
-#pragma unroll
-        for (int wy = 0; wy < FIR_TY + FH - 1; wy++) {
-            const int iy = oy0 + wy - p.pady0;
-            if ((unsigned)iy >= (unsigned)p.inH) continue;
-#pragma unroll
-            for (int wx = 0; wx < FIR_TX + FW - 1; wx++) {
-                const int ix = ox0 + wx - p.padx0;
-                if ((unsigned)ix >= (unsigned)p.inW) continue;
-                float v[8];
-                Vec8<T>::ld(xin + iy * p.isy + ix * p.isx, v);
-#pragma unroll
-                for (int a = 0; a < FIR_TY; a++) {
-                    const int ky = wy - a;
-                    if (ky < 0 || ky >= FH) continue;
-#pragma unroll
-                    for (int b = 0; b < FIR_TX; b++) {
-                        const int kx = wx - b;
-                        if (kx < 0 || kx >= FW) continue;
-#pragma unroll
-                        for (int e = 0; e < 8; e++) acc[a][b][e] += v[e] * fv[ky][kx];
+                        for (int e = 0; e < 8; e++) acc[a][b][e] += v[e] * tap(ky, kx);
                     }
                 }
             }
@@ -248,12 +204,12 @@ __global__ __launch_bounds__(256) void upfirdn2d_fir_fixed_kernel(UpfirdnArgs p,
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Matrix-core FIR for the hot case (up == down == 1, 4 x 4 taps, 16-bit channel-minor tensors, C % 64 == 0, taps exactly
-// representable in the tensor dtype).  The register-blocked kernels above are VALU-bound (16 fp32 FMAs + unpacking per output
-// element: 2.5 TB/s); here a row of 16 output pixels x 16 channels is ONE accumulator tile,
+// representable in the tensor dtype: fir_mfma_accepts() below is the whole rule).  The register-blocked kernel above is VALU-bound
+// (16 fp32 FMAs + unpacking per output element: 2.5 TB/s); here a row of 16 output pixels x 16 channels is ONE accumulator tile,
 //     D[c][ox] += sum_ix  In[iy = oy + ky][ix][c] * T_ky[ix][ox],      T_ky[ix][ox] = f[ky][ix - ox]  (Toeplitz, 32 x 16)
-// i.e. four v_mfma_f32_16x16x32 per tile (one per filter row), 0.4 % of the chip's matrix rate, and the VALU only converts
-// and stores.  The input window of an 8 x 32 output tile x 64 channels (11 rows x 40 pixels) is staged once by LDS-DMA in
-// whole 128-B lines; the A operand (channel x 32 consecutive pixels) is read with the transposing ds_read_b64_tr_b16.
+// i.e. four v_mfma_f32_16x16x32 per tile (one per filter row, ky = 0..3 in that order into a cleared fp32 accumulator), 0.4 % of the
+// chip's matrix rate, and the VALU only converts and stores.  The input window of 32 output columns x 64 channels (40 pixels per row) is
+// staged by LDS-DMA in whole 128-B lines; the A operand (channel x 32 consecutive pixels) is read with the transposing ds_read_b64_tr_b16.
 // Zero-padding = out-of-range DMA offsets; LDS pixels 40..47 of each row are only ever multiplied by zero taps and are
 // cleared once so that they stay finite.  `gain` is applied in fp32 on the accumulator.
 typedef __attribute__((address_space(3))) void* fir_lds_ptr;
@@ -276,153 +232,13 @@ template <> struct FirMfma<f16_s> {
     static __device__ __forceinline__ float from_bits(unsigned short b) { return f16_bits_to_f32(b); }
 };
 
-template <class T, int RPW>      // RPW = output rows per wave; built for 2 (8 x 32 tile, 68 KB of LDS, 2 workgroups per CU; 1 and 4 measured slower: DESIGN.md)
-__global__ __launch_bounds__(256, RPW == 1 ? 3 : (RPW == 2 ? 2 : 1)) void upfirdn2d_fir_mfma_kernel(UpfirdnArgs p, unsigned x_bytes, int tiles_x, int tiles_y, int cblocks)
-{
-    constexpr int TY = 4 * RPW, TX = 32, FH = 4, FW = 4;
-    constexpr int WY = TY + FH - 1;                    // 11 window rows
-    constexpr int WXL = 48;                            // LDS row pitch in pixels: the K window of the second 16-pixel segment ends at 16 + 32
-    constexpr int PPR = 5;                             // DMA pieces (8 pixels) per window row: pixels 0..39 (35 needed)
-    extern __shared__ __attribute__((aligned(16))) unsigned char fsm[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int b = blockIdx.x;
-    const int cb0 = b % cblocks; b /= cblocks;
-    const int tx = b % tiles_x; b /= tiles_x;
-    const int ty = b % tiles_y; const int n = b / tiles_y;
-    const int ox0 = tx * TX, oy0 = ty * TY;
-
-    // clear pixels 40..47 of every window row (8 x 128 B each): 11 rows x 64 chunks of 16 B
-    for (int i = tid; i < WY * 64; i += 256) {
-        const int r = i >> 6, c = i & 63;
-        *reinterpret_cast<float4_t*>(fsm + ((r * WXL + 40) * 128) + c * 16) = float4_t{0.f, 0.f, 0.f, 0.f};
-    }
-    // stage the window: piece = 8 pixels x 128 B, lane -> (pixel row = lane / 8, LDS chunk = lane % 8); the 16-B chunk pairs of LDS
-    // row R are XOR-swizzled by (R >> 1) & 3 on the source side and in the transposing reads (as in conv_wgrad.hip)
-    {
-        __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, (int)x_bytes, 0x00020000);
-        const int drow = lane >> 3, dchunk = lane & 7;
-        for (int piece = wave; piece < WY * PPR; piece += 4) {
-            const int r = piece / PPR, j = piece - r * PPR;
-            const int R = r * WXL + j * 8 + drow;
-            const int sc = (((dchunk >> 1) ^ ((R >> 1) & 3)) << 1) | (dchunk & 1);
-            const int iy = oy0 - p.pady0 + r, ix = ox0 - p.padx0 + j * 8 + drow;
-            const unsigned okm = 0u - (unsigned)(((unsigned)iy < (unsigned)p.inH) & ((unsigned)ix < (unsigned)p.inW) & (j * 8 + drow < TX + FW - 1));
-            const unsigned real = (unsigned)(n * (int)p.isn + iy * (int)p.isy + ix * (int)p.isx + cb0 * 64 + sc * 8) * 2u;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, (fir_lds_ptr)(fsm + (r * WXL + j * 8) * 128), 16, (real & okm) | (SBG_FIR_OOB & ~okm), 0, 0, 0);
-        }
-    }
-    // Toeplitz operand, constant per lane: B lane (n = output pixel = lane & 15, k-group g = lane >> 4) element j multiplies the
-    // input pixel kpix(g, j) = j < 4 ? 4g + j : 16 + 4g + (j - 4)  -- the k order of the transposing reads below
-    const int fi = lane & 15, fg = lane >> 4, fq = fi >> 2, fp = fi & 3;
-    short8_t bt[FH];
-#pragma unroll
-    for (int ky = 0; ky < FH; ky++) {
-        const int fy = p.flip ? ky : FH - 1 - ky;
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const int kpix = j < 4 ? 4 * fg + j : 16 + 4 * fg + (j - 4);
-            const int kx = kpix - fi;
-            float v = 0.f;
-            if (kx >= 0 && kx < FW) v = p.f[fy * p.fsy + (p.flip ? kx : FW - 1 - kx) * p.fsx];
-            bt[ky][j] = FirMfma<T>::bits(v);
-        }
-    }
-    // per-lane byte offsets of the transposing A reads (rows = pixels 4g + q and 16 + 4g + q of the K window, 16 channels at `col`)
-    auto frag_off = [&](int Rrel, int col) {
-        const int chunk = (col >> 3) + (fp >> 1);
-        const int sw = (((chunk >> 1) ^ ((Rrel >> 1) & 3)) << 1) | (chunk & 1);
-        return Rrel * 128 + sw * 16 + (fp & 1) * 8;
-    };
-    int offA[4];
-#pragma unroll
-    for (int c = 0; c < 4; c++) offA[c] = frag_off(4 * fg + fq, c * 16);
-
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-
-    float4_t acc[RPW][2][4];                             // [output row of this wave][16-pixel segment][16-channel block]
-#pragma unroll
-    for (int a = 0; a < RPW; a++)
-#pragma unroll
-        for (int sg = 0; sg < 2; sg++)
-#pragma unroll
-            for (int c = 0; c < 4; c++) acc[a][sg][c] = float4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int rl = 0; rl < RPW + FH - 1; rl++) {          // the window rows behind this wave's output rows
-        const unsigned char* rowp = fsm + ((RPW * wave + rl) * WXL) * 128;
-#pragma unroll
-        for (int sg = 0; sg < 2; sg++)
-#pragma unroll
-            for (int c = 0; c < 4; c++) {
-                const unsigned char* q = rowp + sg * 16 * 128 + offA[c];
-                const short4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((fir_lds_s4_ptr)q);
-                const short4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((fir_lds_s4_ptr)(q + 16 * 128));
-                const short8_t fa = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-#pragma unroll
-                for (int a = 0; a < RPW; a++) {
-                    const int ky = rl - a;
-                    if (ky < 0 || ky >= FH) continue;
-                    acc[a][sg][c] = FirMfma<T>::run(fa, bt[ky], acc[a][sg][c]);
-                }
-            }
-    }
-    // D tile: lane holds channels cb*16 + 4 fg + {0..3} of output pixel seg*16 + (lane & 15).  v_permlane16_swap_b32 exchanges the
-    // odd 16-lane rows of one channel block with the even rows of the next, after which lane group fg holds EIGHT consecutive
-    // channels -- block c + (fg & 1), offset 8 (fg >> 1) -- and stores 16 B instead of 2 x 8 B (the store path is issue-bound).
-    T* yb = (T*)p.y + n * p.osn + cb0 * 64 + (fg & 1) * 16 + (fg >> 1) * 8;
-    // fused tail, applied in fp32 before the exchange: this lane's channels are cb0*64 + 16 c + 4 fg + {0..3}
-    float4_t t_scale[4], t_bias[4], t_post[4];
-    const float t_alpha = p.tail ? p.alpha : 1.f, t_gain = p.tail ? p.act_gain : 1.f, t_cl = (p.tail && p.clamp >= 0.f) ? p.clamp : __builtin_inff();
-#pragma unroll
-    for (int c = 0; c < 4; c++) {
-        const int ch = cb0 * 64 + c * 16 + 4 * fg;
-        t_scale[c] = float4_t{p.gain, p.gain, p.gain, p.gain};
-        t_bias[c] = float4_t{0.f, 0.f, 0.f, 0.f};
-        t_post[c] = float4_t{1.f, 1.f, 1.f, 1.f};
-        if (p.tail && p.oscale) t_scale[c] *= *reinterpret_cast<const float4_t*>(p.oscale + (int64_t)n * p.C + ch);
-        if (p.tail && p.bias)   t_bias[c] = *reinterpret_cast<const float4_t*>(p.bias + ch);
-        if (p.tail == 1 && p.post) t_post[c] = *reinterpret_cast<const float4_t*>(p.post + (int64_t)n * p.C + ch);
-    }
-#pragma unroll
-    for (int a = 0; a < RPW; a++) {
-        const int oy = oy0 + RPW * wave + a;
-#pragma unroll
-        for (int sg = 0; sg < 2; sg++) {
-            const int ox = ox0 + sg * 16 + fi;
-            const bool ok = oy < p.outH && ox < p.outW;
-            T* dst = yb + oy * p.osy + ox * p.osx;
-            const float nz = (p.tail && p.noise && ok) ? p.noise[n * p.noise_sn + (int64_t)oy * p.outW + ox] : 0.f;
-#pragma unroll
-            for (int c = 0; c < 4; c++) {
-                float4_t v = acc[a][sg][c] * t_scale[c] + (t_bias[c] + nz);
-#pragma unroll
-                for (int e = 0; e < 4; e++) { float u = v[e]; u = (u > 0.f) ? u : u * t_alpha; v[e] = __builtin_amdgcn_fmed3f(u * t_gain, -t_cl, t_cl) * t_post[c][e]; }
-                acc[a][sg][c] = v;
-            }
-#pragma unroll
-            for (int c = 0; c < 4; c += 2) {
-                const float4_t va = acc[a][sg][c], vb = acc[a][sg][c + 1];
-                const unsigned a0 = (unsigned)(unsigned short)FirMfma<T>::bits(va[0]) | ((unsigned)(unsigned short)FirMfma<T>::bits(va[1]) << 16);
-                const unsigned a1 = (unsigned)(unsigned short)FirMfma<T>::bits(va[2]) | ((unsigned)(unsigned short)FirMfma<T>::bits(va[3]) << 16);
-                const unsigned b0 = (unsigned)(unsigned short)FirMfma<T>::bits(vb[0]) | ((unsigned)(unsigned short)FirMfma<T>::bits(vb[1]) << 16);
-                const unsigned b1 = (unsigned)(unsigned short)FirMfma<T>::bits(vb[2]) | ((unsigned)(unsigned short)FirMfma<T>::bits(vb[3]) << 16);
-                const auto r0 = __builtin_amdgcn_permlane16_swap(a0, b0, false, false);      // all lanes take part (no divergence above)
-                const auto r1 = __builtin_amdgcn_permlane16_swap(a1, b1, false, false);
-                typedef __attribute__((ext_vector_type(4))) unsigned uint4_t;
-                const uint4_t o = {r0[0], r1[0], r0[1], r1[1]};
-                if (ok) *reinterpret_cast<uint4_t*>(dst + c * 16) = o;
-            }
-        }
-    }
-}
-
-// Sliding-window variant of the matrix-core FIR: a workgroup owns a strip of 32 output columns x 64 channels and WALKS DOWN it, four
-// output rows per step.  The window rows live in a 12-row ring in LDS (row r of the strip's window in slot r % 12); a step needs the seven
-// rows [4s, 4s + 7), of which only the last four are new, and those are fetched by LDS-DMA one step ahead while the matrix cores work on the
-// current rows.  The tile kernel above re-reads three of every eleven window rows (and, before the column mask, 40 of 35 columns): 1.72x the
-// input bytes; here the vertical overlap is read once per strip segment and the horizontal one is 35 / 32, and the loads of step s + 1, the
-// MFMAs of step s and the stores of step s - 1 are in flight together (two workgroups per CU: 72 KB of LDS each).
+// The kernel is a sliding window: a workgroup owns a strip of 32 output columns x 64 channels and WALKS DOWN it, four output rows per
+// step (one per wave; rows past the segment are masked DMA offsets and masked stores, so any height runs).  The window rows live in a
+// 12-row ring in LDS (row r of the strip's window in slot r % 12); a step needs the seven rows [4s, 4s + 7), of which only the last four
+// are new, and those are fetched by LDS-DMA one step ahead while the matrix cores work on the current rows.  The vertical overlap is read
+// once per strip segment and the horizontal one is 35 / 32 (a kernel of independent 8 x 32 tiles, retired, re-read three of every eleven
+// window rows: 1.72x the input bytes), and the loads of step s + 1, the MFMAs of step s and the stores of step s - 1 are in flight
+// together (two workgroups per CU: 72 KB of LDS each).
 // Order inside a step: issue the prefetch -> compute from LDS -> wait for the prefetch (the stores of the previous step, issued a whole step
 // ago, have drained by then) -> barrier (every wave is done with the rows the NEXT prefetch overwrites, and sees the new rows) -> store.
 // BT (backward tail): see UpfirdnArgs::dact_y -- the transposed low-pass in the backward of `bias_act -> low-pass` (D's conv0 -> the filter in front of the
@@ -648,70 +464,52 @@ __global__ __launch_bounds__(256, 2) void upfirdn2d_fir_slide_kernel(UpfirdnArgs
     }
 }
 
-// strip / segment geometry of the sliding-window kernel (shared by the launcher and by sbg_upfirdn2d_dact_rows)
-static bool fir_slide_geometry(const UpfirdnArgs& a, int& tiles_x, int& cblocks, int& ysegs, int& seg_rows, int64_t& nblk)
+// Strip / segment geometry of a sliding-window launch, and the extent of its buffer resource.
+struct FirSlidePlan { unsigned x_bytes; int tiles_x, cblocks, ysegs, seg_rows; int64_t nblk; };
+
+// THE rule "the matrix-core FIR takes this launch"; every caller asks here.  On top of it a launch needs the 8-channel vector layout
+// (`vec8` of the entry point: pointer and stride alignment).
+//  FIR_RULE_SHAPE   dtype, filter, sizes and channel-minor layout only: the answer of sbg_upfirdn2d_tail_supported(), which the Python
+//                   layer probes before it has a launch to describe -- it never looked at the operand's extent or the stride signs
+//  FIR_RULE_LAUNCH  the whole rule; *plan (if given) then describes the launch
+enum FirRule { FIR_RULE_SHAPE, FIR_RULE_LAUNCH };
+static bool fir_mfma_accepts(const UpfirdnArgs& a, bool exact16, size_t elem_size, FirRule rule, FirSlidePlan* plan = nullptr)
 {
-    tiles_x = (a.outW + 31) / 32; cblocks = a.C / 64;
-    const int64_t strips = (int64_t)a.N * tiles_x * cblocks;
+    if (elem_size != 2 || !exact16 || a.upx != 1 || a.upy != 1 || a.downx != 1 || a.downy != 1 || a.fw != 4 || a.fh != 4) return false;
+    if ((a.C % 64) != 0 || a.outW < 16 || a.outH < 8 || a.isc != 1 || a.osc != 1) return false;   // smaller images stay with the register-blocked kernel
+    if (rule == FIR_RULE_SHAPE) return true;
+    if (a.tail == 2 && a.outH < 16) return false;       // the backward tail's domain (sbg_upfirdn2d_dact_rows)
+    // the window is fetched through a buffer resource with 32-bit offsets; bit 31 marks the padding
+    const int64_t x_bytes = 2 * ((int64_t)(a.N - 1) * a.isn + (int64_t)(a.inH - 1) * a.isy + (int64_t)(a.inW - 1) * a.isx + a.C);
+    if (x_bytes >= (int64_t)SBG_FIR_OOB || a.isn < 0 || a.isy < 0 || a.isx < 0) return false;
+    FirSlidePlan g;
+    g.x_bytes = (unsigned)x_bytes;
+    g.tiles_x = (a.outW + 31) / 32; g.cblocks = a.C / 64;
+    const int64_t strips = (int64_t)a.N * g.tiles_x * g.cblocks;
     // vertical segments: enough workgroups for two per CU on every CU, but at least 16 output rows per segment (3 overlap rows are re-read per segment)
-    ysegs = 1;
-    while (strips * ysegs < 1024 && a.outH / (ysegs * 2) >= 16) ysegs *= 2;
-    seg_rows = (((a.outH + ysegs - 1) / ysegs) + 3) & ~3;
-    ysegs = (a.outH + seg_rows - 1) / seg_rows;
-    nblk = strips * ysegs;
-    return nblk <= INT32_MAX && nblk > 0;
+    g.ysegs = 1;
+    while (strips * g.ysegs < 1024 && a.outH / (g.ysegs * 2) >= 16) g.ysegs *= 2;
+    g.seg_rows = (((a.outH + g.ysegs - 1) / g.ysegs) + 3) & ~3;
+    g.ysegs = (a.outH + g.seg_rows - 1) / g.seg_rows;
+    g.nblk = strips * g.ysegs;
+    if (g.nblk > INT32_MAX || g.nblk <= 0) return false;
+    if (plan) *plan = g;
+    return true;
 }
 
-template <class T>
-static bool launch_fir_slide(const UpfirdnArgs& a, hipStream_t stream)
+template <class T, bool BT>
+static bool launch_fir_slide(const UpfirdnArgs& a, const FirSlidePlan& g, hipStream_t stream)
 {
     constexpr int lds = 12 * 48 * 128;
-    const int64_t x_bytes = 2 * ((int64_t)(a.N - 1) * a.isn + (int64_t)(a.inH - 1) * a.isy + (int64_t)(a.inW - 1) * a.isx + a.C);
-    if (x_bytes >= (int64_t)SBG_FIR_OOB || a.isn < 0 || a.isy < 0 || a.isx < 0) return false;
-    int tiles_x, cblocks, ysegs, seg_rows; int64_t nblk;
-    if (!fir_slide_geometry(a, tiles_x, cblocks, ysegs, seg_rows, nblk)) return false;
-    if (a.tail == 2) {
-        auto kern = upfirdn2d_fir_slide_kernel<T, true>;
-        if (!SBG_RAISE_LDS_ONCE(kern, lds)) return false;
-        SBG_LAUNCH_OR(return false, kern, dim3((unsigned)nblk), dim3(256), lds, stream, a, (unsigned)x_bytes, tiles_x, cblocks, ysegs, seg_rows);
-    } else {
-        auto kern = upfirdn2d_fir_slide_kernel<T, false>;
-        if (!SBG_RAISE_LDS_ONCE(kern, lds)) return false;
-        SBG_LAUNCH_OR(return false, kern, dim3((unsigned)nblk), dim3(256), lds, stream, a, (unsigned)x_bytes, tiles_x, cblocks, ysegs, seg_rows);
-    }
-    return true;
-}
-
-template <class T, int RPW>
-static bool launch_fir_mfma_rpw(const UpfirdnArgs& a, hipStream_t stream)
-{
-    constexpr int TY = 4 * RPW, lds = (TY + 3) * 48 * 128;
-    const int64_t x_bytes = 2 * ((int64_t)(a.N - 1) * a.isn + (int64_t)(a.inH - 1) * a.isy + (int64_t)(a.inW - 1) * a.isx + a.C);
-    if (x_bytes >= (int64_t)SBG_FIR_OOB || a.isn < 0 || a.isy < 0 || a.isx < 0) return false;
-    const int tiles_x = (a.outW + 31) / 32, tiles_y = (a.outH + TY - 1) / TY, cblocks = a.C / 64;
-    const int64_t nblk = (int64_t)a.N * tiles_y * tiles_x * cblocks;
-    if (nblk > INT32_MAX || nblk <= 0) return false;
-    auto kern = upfirdn2d_fir_mfma_kernel<T, RPW>;
+    auto kern = upfirdn2d_fir_slide_kernel<T, BT>;
     if (!SBG_RAISE_LDS_ONCE(kern, lds)) return false;
-    SBG_LAUNCH_OR(return false, kern, dim3((unsigned)nblk), dim3(256), lds, stream, a, (unsigned)x_bytes, tiles_x, tiles_y, cblocks);
+    SBG_LAUNCH_OR(return false, kern, dim3((unsigned)g.nblk), dim3(256), lds, stream, a, g.x_bytes, g.tiles_x, g.cblocks, g.ysegs, g.seg_rows);
     return true;
 }
 
-// Kernel that served an upfirdn2d launch: the launch log records 10000 * variant + 16 * upx + downx in dims[6].
-enum FirVariant { FIR_V_NONE = 0, FIR_V_SLIDE = 1, FIR_V_TILE = 2, FIR_V_SLIDE_EDGE = 3, FIR_V_TILE_EDGE = 4, FIR_V_FIXED44 = 5, FIR_V_GENERIC = 6,
-                  FIR_V_VEC8 = 7, FIR_V_SCALAR = 8 };
-
-// -> FIR_V_SLIDE / FIR_V_TILE when a matrix-core kernel took the launch, FIR_V_NONE otherwise
-template <class T>
-static int launch_fir_mfma(const UpfirdnArgs& a, hipStream_t stream)
-{
-    if (a.outH >= 16) return launch_fir_slide<T>(a, stream) ? FIR_V_SLIDE : FIR_V_NONE;
-    if (a.tail == 2) return FIR_V_NONE;      // the backward tail exists in the sliding-window kernel only
-    return launch_fir_mfma_rpw<T, 2>(a, stream) ? FIR_V_TILE : FIR_V_NONE;
-}
-
-template <class T> static int try_fir_mfma(const UpfirdnArgs& a, hipStream_t stream) { return launch_fir_mfma<T>(a, stream); }
-template <> int try_fir_mfma<float>(const UpfirdnArgs&, hipStream_t) { return FIR_V_NONE; }
+// Kernel that served an upfirdn2d launch: the launch log records 10000 * variant + 16 * upx + downx in dims[6] (listed in sbg_hip.h).
+// 2 and 4 were the tile kernel's (alone / with edge columns) and stay retired: committed profiles carry them.
+enum FirVariant { FIR_V_NONE = 0, FIR_V_SLIDE = 1, FIR_V_SLIDE_EDGE = 3, FIR_V_FIXED44 = 5, FIR_V_GENERIC = 6, FIR_V_VEC8 = 7, FIR_V_SCALAR = 8 };
 
 template <class T>
 static int launch_upfirdn(const UpfirdnArgs& a0, bool vec8, bool exact16, hipStream_t stream)
@@ -721,27 +519,34 @@ static int launch_upfirdn(const UpfirdnArgs& a0, bool vec8, bool exact16, hipStr
     SbgProfScope prof(stream, SBG_K_UPFIRDN2D, 0.0,
                       es * ((double)a.N * a.C * a.inH * a.inW + (double)a.N * a.C * a.outH * a.outW),
                       {a.N, a.C, a.inH, a.inW, a.outH, a.outW, a.upx * 16 + a.downx});      // dims[6] gains the variant digit below
-    const bool mfma_ok = vec8 && exact16 && sizeof(T) == 2 && a.upx == 1 && a.upy == 1 && a.downx == 1 && a.downy == 1 && a.fw == 4 && a.fh == 4 && (a.C % 64) == 0
-                         && a.outW >= 16 && a.outH >= 8;
+    auto try_fir_mfma = [&](const UpfirdnArgs& b) -> bool {
+        if constexpr (sizeof(T) == 2) {
+            FirSlidePlan g;
+            if (!vec8 || !fir_mfma_accepts(b, exact16, sizeof(T), FIR_RULE_LAUNCH, &g)) return false;
+            return b.tail == 2 ? launch_fir_slide<T, true>(b, g, stream) : launch_fir_slide<T, false>(b, g, stream);
+        } else {
+            return false;
+        }
+    };
     // A few columns beyond a multiple of the 32-column strips (the 2 res + 1 wide outputs of the discriminator's low-pass in front of a strided
     // convolution: 257 = 8 strips + 1) would cost a whole strip of matrix-core work (9 strips for 257 columns: 11 % idle, 33 columns: 48 %): the
     // strips take the multiple of 32 and the register-blocked kernel the remaining columns, as a launch over the shifted sub-rectangle.
     const int rem = a.outW % 32;
     const int code = a.upx * 16 + a.downx;
-    if (mfma_ok && !a.tail && rem >= 1 && rem <= 4 && a.outW > 32) {
+    if (!a.tail && rem >= 1 && rem <= 4 && a.outW > 32) {
         UpfirdnArgs m = a, e = a;
         m.outW = a.outW - rem;
         e.outW = rem; e.padx0 = a.padx0 - m.outW; e.y = (void*)((T*)a.y + (int64_t)m.outW * a.osx);
-        if (const int v = try_fir_mfma<T>(m, stream)) {
+        if (try_fir_mfma(m)) {
             const int xblocks = (e.outW + FIR_TX - 1) / FIR_TX, yblocks = (e.outH + FIR_TY - 1) / FIR_TY;
             e.total = (int64_t)e.N * yblocks * xblocks * (e.C >> 3);
-            SBG_LAUNCH((upfirdn2d_fir_fixed_kernel<T, 4, 4>), dim3(sbg_stream_grid(e.total, 256)), dim3(256), 0, stream, e, xblocks, yblocks);
+            SBG_LAUNCH((upfirdn2d_fir_kernel<T, 4, 4>), dim3(sbg_stream_grid(e.total, 256)), dim3(256), 0, stream, e, xblocks, yblocks);
             SBG_HIP_LAUNCH_CHECK();
-            prof.set_dim(6, 10000 * (v == FIR_V_SLIDE ? FIR_V_SLIDE_EDGE : FIR_V_TILE_EDGE) + code);
+            prof.set_dim(6, 10000 * FIR_V_SLIDE_EDGE + code);
             return SBG_OK;
         }
     }
-    int variant = mfma_ok ? try_fir_mfma<T>(a, stream) : FIR_V_NONE;
+    int variant = try_fir_mfma(a) ? FIR_V_SLIDE : FIR_V_NONE;
     if (variant != FIR_V_NONE) {
         // matrix-core FIR
     } else if (a.tail) {
@@ -751,10 +556,10 @@ static int launch_upfirdn(const UpfirdnArgs& a0, bool vec8, bool exact16, hipStr
         a.total = (int64_t)a.N * yblocks * xblocks * (a.C >> 3);
         if (a.fw == 4 && a.fh == 4) {
             variant = FIR_V_FIXED44;
-            SBG_LAUNCH((upfirdn2d_fir_fixed_kernel<T, 4, 4>), dim3(sbg_stream_grid(a.total, 256)), dim3(256), 0, stream, a, xblocks, yblocks);
+            SBG_LAUNCH((upfirdn2d_fir_kernel<T, 4, 4>), dim3(sbg_stream_grid(a.total, 256)), dim3(256), 0, stream, a, xblocks, yblocks);
         } else {
             variant = FIR_V_GENERIC;
-            SBG_LAUNCH((upfirdn2d_fir_kernel<T>), dim3(sbg_stream_grid(a.total, 256)), dim3(256), 0, stream, a, xblocks, yblocks);
+            SBG_LAUNCH((upfirdn2d_fir_kernel<T, 0, 0>), dim3(sbg_stream_grid(a.total, 256)), dim3(256), 0, stream, a, xblocks, yblocks);
         }
     } else if (vec8) {
         variant = FIR_V_VEC8;
@@ -770,28 +575,48 @@ static int launch_upfirdn(const UpfirdnArgs& a0, bool vec8, bool exact16, hipStr
     return SBG_OK;
 }
 
+// the kernels' view of a parameter block (copies only; the entry point validates)
+static void fill_args(const sbg_upfirdn2d_params* q, UpfirdnArgs& a)
+{
+    a.x = q->x; a.f = q->f; a.y = q->y;
+    a.upx = q->upx; a.upy = q->upy; a.downx = q->downx; a.downy = q->downy; a.padx0 = q->padx0; a.pady0 = q->pady0;
+    a.flip = q->flip ? 1 : 0; a.gain = q->gain;
+    a.inW = q->inSize[0]; a.inH = q->inSize[1]; a.C = q->inSize[2]; a.N = q->inSize[3];
+    a.isx = q->inStride[0]; a.isy = q->inStride[1]; a.isc = q->inStride[2]; a.isn = q->inStride[3];
+    a.fw = q->filterSize[0]; a.fh = q->filterSize[1]; a.fsx = q->filterStride[0]; a.fsy = q->filterStride[1];
+    a.outW = q->outSize[0]; a.outH = q->outSize[1];
+    a.osx = q->outStride[0]; a.osy = q->outStride[1]; a.osc = q->outStride[2]; a.osn = q->outStride[3];
+    a.total = 0;
+    a.oscale = q->oscale; a.noise = q->noise; a.noise_sn = q->noise_stride_n; a.bias = q->bias;
+    a.tail = q->dact_y ? 2 : (q->act != 0 ? 1 : 0);
+    a.alpha = q->act == SBG_ACT_LRELU ? q->alpha : (q->act == SBG_ACT_RELU ? 0.f : 1.f); a.act_gain = q->act_gain; a.clamp = q->clamp;
+    a.post = q->post_scale;
+    // backward tail: slope of clamp(act(.) * gain) at the saved output (same tests as sbg_modconv_bwd)
+    a.dact_y = q->dact_y; a.dact_part = q->dact_y ? q->dact_partial : nullptr;
+    a.dact_gpos = q->dact_y ? q->dact_gain : 1.f;
+    a.dact_gneg = !q->dact_y ? 1.f : (q->dact_act == SBG_ACT_LRELU ? q->dact_gain * q->dact_alpha : (q->dact_act == SBG_ACT_RELU ? 0.f : q->dact_gain));
+    a.dact_rail = (q->dact_y && q->dact_clamp >= 0.f) ? q->dact_clamp : __builtin_inff();
+}
+
 } // namespace
 
 extern "C" int sbg_upfirdn2d_tail_supported(const sbg_upfirdn2d_params* q)
 {
     if (!q) return 0;
-    const int C = q->inSize[2];
-    return (q->dtype == SBG_BF16 || q->dtype == SBG_F16) && q->filter_exact16 && q->upx == 1 && q->upy == 1 && q->downx == 1 && q->downy == 1
-           && q->filterSize[0] == 4 && q->filterSize[1] == 4 && (C % 64) == 0 && q->outSize[0] >= 16 && q->outSize[1] >= 8
-           && q->inStride[2] == 1 && q->outStride[2] == 1;
+    UpfirdnArgs a;
+    fill_args(q, a);
+    return fir_mfma_accepts(a, q->filter_exact16 != 0, q->dtype == SBG_BF16 || q->dtype == SBG_F16 ? 2 : 0, FIR_RULE_SHAPE);
 }
 
 // Rows of `dact_partial` (= workgroups of the sliding-window launch) for a launch with a backward tail, or -1 when that kernel does not take it.
 extern "C" int64_t sbg_upfirdn2d_dact_rows(const sbg_upfirdn2d_params* q)
 {
-    if (!q || !sbg_upfirdn2d_tail_supported(q) || q->outSize[1] < 16) return -1;
-    if (q->inStride[0] < 0 || q->inStride[1] < 0 || q->inStride[3] < 0) return -1;
-    const int64_t x_bytes = 2 * ((int64_t)(q->inSize[3] - 1) * q->inStride[3] + (int64_t)(q->inSize[1] - 1) * q->inStride[1] + (int64_t)(q->inSize[0] - 1) * q->inStride[0] + q->inSize[2]);
-    if (x_bytes >= (int64_t)SBG_FIR_OOB) return -1;
-    UpfirdnArgs a = {};
-    a.outW = q->outSize[0]; a.outH = q->outSize[1]; a.C = q->inSize[2]; a.N = q->inSize[3];
-    int tiles_x, cblocks, ysegs, seg_rows; int64_t nblk;
-    return fir_slide_geometry(a, tiles_x, cblocks, ysegs, seg_rows, nblk) ? nblk : -1;
+    if (!q) return -1;
+    UpfirdnArgs a;
+    fill_args(q, a);
+    a.tail = 2;         // whether or not dact_y is set yet: the caller sizes dact_partial from this answer
+    FirSlidePlan g;
+    return fir_mfma_accepts(a, q->filter_exact16 != 0, q->dtype == SBG_BF16 || q->dtype == SBG_F16 ? 2 : 0, FIR_RULE_LAUNCH, &g) ? g.nblk : -1;
 }
 
 extern "C" int sbg_upfirdn2d(const sbg_upfirdn2d_params* q, sbg_stream_t stream)
@@ -810,30 +635,13 @@ extern "C" int sbg_upfirdn2d(const sbg_upfirdn2d_params* q, sbg_stream_t stream)
     if (out_numel == 0) return SBG_OK;
 
     UpfirdnArgs a;
-    a.x = q->x; a.f = q->f; a.y = q->y;
-    a.upx = q->upx; a.upy = q->upy; a.downx = q->downx; a.downy = q->downy; a.padx0 = q->padx0; a.pady0 = q->pady0;
-    a.flip = q->flip ? 1 : 0; a.gain = q->gain;
-    a.inW = q->inSize[0]; a.inH = q->inSize[1]; a.C = q->inSize[2]; a.N = q->inSize[3];
-    a.isx = q->inStride[0]; a.isy = q->inStride[1]; a.isc = q->inStride[2]; a.isn = q->inStride[3];
-    a.fw = q->filterSize[0]; a.fh = q->filterSize[1]; a.fsx = q->filterStride[0]; a.fsy = q->filterStride[1];
-    a.outW = q->outSize[0]; a.outH = q->outSize[1];
-    a.osx = q->outStride[0]; a.osy = q->outStride[1]; a.osc = q->outStride[2]; a.osn = q->outStride[3];
-    a.total = 0;
-    a.oscale = q->oscale; a.noise = q->noise; a.noise_sn = q->noise_stride_n; a.bias = q->bias;
-    a.tail = (q->act != 0) ? 1 : 0;
-    a.alpha = q->act == SBG_ACT_LRELU ? q->alpha : (q->act == SBG_ACT_RELU ? 0.f : 1.f); a.act_gain = q->act_gain; a.clamp = q->clamp;
-    a.dact_y = nullptr; a.dact_part = nullptr; a.dact_gpos = a.dact_gneg = 1.f; a.dact_rail = __builtin_inff();
-    a.post = q->post_scale;
+    fill_args(q, a);
     SBG_CHECK(!q->post_scale || (q->act != 0 && sbg_aligned16(q->post_scale)), "upfirdn2d: post_scale belongs to the forward tail (act != 0) and must be 16-byte aligned");
-    if (q->dact_y) {        // backward tail: slope of clamp(act(.) * gain) at the saved output (same tests as sbg_modconv_bwd)
+    if (a.tail == 2) {
         SBG_CHECK(q->act == 0, "upfirdn2d: forward and backward tails exclude each other");
         SBG_CHECK(q->dact_partial != nullptr, "upfirdn2d: the backward tail needs dact_partial (sbg_upfirdn2d_dact_rows() x 64 floats)");
         SBG_CHECK(q->dact_act == SBG_ACT_LINEAR || q->dact_act == SBG_ACT_RELU || q->dact_act == SBG_ACT_LRELU, "upfirdn2d: backward-tail activation must be linear, relu or lrelu");
         SBG_CHECK(q->dact_gain > 0.f && sbg_aligned16(q->dact_y), "upfirdn2d: backward tail: gain must be positive, dact_y 16-byte aligned");
-        a.tail = 2; a.dact_y = q->dact_y; a.dact_part = q->dact_partial;
-        a.dact_gpos = q->dact_gain;
-        a.dact_gneg = q->dact_act == SBG_ACT_LRELU ? q->dact_gain * q->dact_alpha : (q->dact_act == SBG_ACT_RELU ? 0.f : q->dact_gain);
-        a.dact_rail = q->dact_clamp >= 0.f ? q->dact_clamp : __builtin_inff();
     }
 
     // 8-channel vector path: channel-minor on both sides, every pixel start 16-B aligned.
@@ -845,10 +653,10 @@ extern "C" int sbg_upfirdn2d(const sbg_upfirdn2d_params* q, sbg_stream_t stream)
     hipStream_t s = (hipStream_t)stream;
     const bool exact16 = q->filter_exact16 != 0;
     if (a.tail == 2) {
-        SBG_CHECK(vec8 && sbg_upfirdn2d_dact_rows(q) > 0, "upfirdn2d: the backward tail needs the sliding-window matrix-core FIR (sbg_upfirdn2d_dact_rows)");
+        SBG_CHECK(vec8 && fir_mfma_accepts(a, exact16, es, FIR_RULE_LAUNCH), "upfirdn2d: the backward tail needs the sliding-window matrix-core FIR (sbg_upfirdn2d_dact_rows)");
     } else if (a.tail) {
         SBG_CHECK(q->act == SBG_ACT_LINEAR || q->act == SBG_ACT_RELU || q->act == SBG_ACT_LRELU, "upfirdn2d: fused activation must be linear, relu or lrelu");
-        SBG_CHECK(vec8 && sbg_upfirdn2d_tail_supported(q), "upfirdn2d: the fused tail needs the matrix-core FIR path (sbg_upfirdn2d_tail_supported)");
+        SBG_CHECK(vec8 && fir_mfma_accepts(a, exact16, es, FIR_RULE_SHAPE), "upfirdn2d: the fused tail needs the matrix-core FIR path (sbg_upfirdn2d_tail_supported)");
         SBG_CHECK((!q->oscale || sbg_aligned16(q->oscale)) && (!q->bias || sbg_aligned16(q->bias)), "upfirdn2d: oscale / bias must be 16-byte aligned");
     }
     if (q->dtype == SBG_F32) return launch_upfirdn<float>(a, vec8, false, s);

@@ -14,12 +14,15 @@ that its bound rejects the reference with one 8-channel input slab or one border
 Weight gradients run in exact mode and, besides, with support probes: a dy that is zero except on one region (first / last row and column,
 last partial tile, last image, last channel tail), so that region alone produces the result.
 """
+import itertools
+
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 import style_big_gan_amd  # noqa: F401
+from style_big_gan_amd import _lib
 from style_big_gan_amd.torch_utils.ops import conv2d_gradfix as CG, conv_bias_act, upfirdn2d as UP
 
 from exact_util import U32, U_OUT, assert_exact, assert_range, expect_launch, qgrid, qint, qpow2, within_bound
@@ -57,6 +60,7 @@ def fir(variant, up=1, down=1):
     return lambda d: d[6] == 10000 * variant + 16 * up + down
 
 
+# the codes the library logs; FIR_TILE / FIR_TILE_EDGE are retired (the tile matrix-core kernel is gone) and no launch logs them any more
 FIR_SLIDE, FIR_TILE, FIR_SLIDE_EDGE, FIR_TILE_EDGE, FIR_FIXED44, FIR_GENERIC, FIR_VEC8, FIR_SCALAR = range(1, 9)
 
 
@@ -431,9 +435,9 @@ def _fir_ref(x, f, up, down, pad, gain):
 # (id, dtype, n, c, h, w, up, down, pad, gain, channel-minor, leaf, filter)
 FIR_CASES = [
     ("slide", BF, 2, 64, 40, 64, 1, 1, (1, 2, 1, 2), 1.0, True, fir(FIR_SLIDE), "44"),
-    ("tile_outH_lt_16", F16, 2, 128, 9, 70, 1, 1, (1, 2, 1, 2), 1.0, True, fir(FIR_TILE), "44"),
+    ("tile_outH_lt_16", F16, 2, 128, 9, 70, 1, 1, (1, 2, 1, 2), 1.0, True, fir(FIR_SLIDE), "44"),
     ("slide_edge", BF, 1, 64, 30, 66, 1, 1, (2, 2, 2, 2), 1.0, True, fir(FIR_SLIDE_EDGE), "44"),
-    ("tile_edge", BF, 2, 64, 12, 99, 1, 1, (1, 1, 1, 1), 1.0, True, fir(FIR_TILE_EDGE), "44"),
+    ("tile_edge", BF, 2, 64, 12, 99, 1, 1, (1, 1, 1, 1), 1.0, True, fir(FIR_SLIDE_EDGE), "44"),
     ("fixed44_c24", BF, 2, 24, 19, 27, 1, 1, (1, 2, 1, 2), 1.0, True, fir(FIR_FIXED44), "44"),
     ("generic_3x3", BF, 2, 16, 19, 27, 1, 1, (1, 1, 1, 1), 1.0, True, fir(FIR_GENERIC), "33"),
     ("vec8_up2", BF, 2, 16, 13, 11, 2, 1, (2, 1, 2, 1), 4.0, True, fir(FIR_VEC8, 2, 1), "44"),
@@ -472,17 +476,22 @@ def test_fir_leaf_exact(dev, case):
         assert_exact(gx, gr, tag + " gradient")
 
 
-@pytest.mark.parametrize("post", [False, True])
-def test_fir_forward_tail_exact(dev, post):
-    """the sliding-window FIR with the forward tail (G's up-sampling layer: 128 ch, 257^2 -> 256^2, pad 1, gain 4):
+# (n, c, input rows, input columns): G's up-sampling layer (128 ch, 257^2 -> 256^2), and an image below 16 output rows (13 x 73 -> 12 x 72)
+FIR_TAIL_SHAPES = [(2, 128, 257, 257), (2, 64, 13, 73)]
+
+
+@pytest.mark.parametrize("post,shape", [(post, shape) for shape in FIR_TAIL_SHAPES for post in (False, True)],
+                         ids=["False", "True", "False-13x73", "True-13x73"])
+def test_fir_forward_tail_exact(dev, post, shape):
+    """the sliding-window FIR with the forward tail (pad 1, gain 4):
     y = clamp(lrelu(fir(t) * oscale + noise + bias) * gain) (* post) bit for bit (the transposed conv feeding it is the conv case
     G_up_128_to_257).  Dyadic oscale / noise / bias / post, lrelu slope 1/4, gain 2, clamp 60 + 2^-11."""
     gen = torch.Generator().manual_seed(13)
-    n, c, r = 2, 128, 257
-    t = qint(gen, (n, c, r, r), hi=40)
+    n, c, ih, iw = shape
+    t = qint(gen, (n, c, ih, iw), hi=40)
     f = _f44()
     filt = _fir_ref(t, f, 1, 1, (1, 1, 1, 1), 4.0)
-    osc, noise = qpow2(gen, (n, c)), qgrid(gen, (n, 1, 256, 256), -4, 4, 0.25)
+    osc, noise = qpow2(gen, (n, c)), qgrid(gen, (n, 1, ih - 1, iw - 1), -4, 4, 0.25)
     bias = qgrid(gen, (c,), -8, 8, 0.25) + 0.125
     v = filt * osc[:, :, None, None] + noise + bias[None, :, None, None]
     v = (torch.where(v > 0, v, v * 0.25) * 2.0)
@@ -498,7 +507,7 @@ def test_fir_forward_tail_exact(dev, post):
         y = UP.fir_bias_act(tg, f.to(dev), [1, 1, 1, 1], 4.0, osc.to(dev, torch.float32), noise.to(dev, torch.float32),
                             bias.to(dev, torch.float32), act="lrelu", alpha=0.25, act_gain=2.0, clamp=clamp,
                             post_scale=None if ps is None else ps.to(dev, torch.float32))
-    assert_exact(y, v, f"fir forward tail post={post}")
+    assert_exact(y, v, f"fir forward tail post={post} {ih}x{iw}")
 
 
 def test_fir_backward_dact_tail_exact(dev):
@@ -527,3 +536,42 @@ def test_fir_backward_dact_tail_exact(dev):
     assert_exact(got, ref, "fir dact gradient")
     assert_exact(db, ref.sum([0, 2, 3]), "fir dact bias gradient")
 
+
+def _fir_probe_block(dtype, c, rows, cols, taps, exact, cl, n=2, up=1, in_stride=None):
+    """a dense parameter block as ops/upfirdn2d.py fills it (no pointers: the two probe functions read sizes, strides and flags only)"""
+    p = _lib.UpfirdnParams()
+    ih, iw = rows + taps - 1, cols + taps - 1
+    p.dtype, p.upx, p.upy, p.downx, p.downy, p.gain = dtype, up, up, 1, 1, 1.0
+    p.inSize[:], p.outSize[:] = [iw, ih, c, n], [cols, rows, c, n]
+    p.inStride[:] = [c, iw * c, 1, ih * iw * c] if cl else [1, iw, ih * iw, c * ih * iw]
+    p.outStride[:] = [c, cols * c, 1, rows * cols * c] if cl else [1, cols, rows * cols, c * rows * cols]
+    for k, v in (in_stride or {}).items():
+        p.inStride[k] = v
+    p.filterSize[:], p.filterStride[:], p.filter_exact16 = [taps, taps], [1, taps], exact
+    return p
+
+
+def test_fir_matrix_core_rule_pinned():
+    """sbg_upfirdn2d_tail_supported() and sbg_upfirdn2d_dact_rows() over a table of parameter blocks: the Python layer asks them which launches
+    the matrix-core FIR takes and the entry point fails a tail launch the kernel then declines, so their answers are pinned.  The expected
+    values are those of the library before the acceptance rule became one function (recorded from that build, not derived from this one)."""
+    lib = _lib.load()
+    F32, H16, B16 = _lib.SBG_F32, _lib.SBG_F16, _lib.SBG_BF16
+    # every (dtype, C, output rows, output columns, taps, filter_exact16, channel-minor) of the product below that the forward tail accepts,
+    # and the dact_partial rows of those the backward tail accepts (16 rows at least); everything else: 0 and -1
+    tail_yes = {(d, 64, rows, 16, 4, 1, True) for d in (H16, B16) for rows in (8, 15, 16)}
+    dact_rows = {(H16, 64, 16, 16, 4, 1, True): 2, (B16, 64, 16, 16, 4, 1, True): 2}
+    count = 0
+    for key in itertools.product((F32, H16, B16), (64, 24), (7, 8, 15, 16), (15, 16), (3, 4), (0, 1), (True, False)):
+        p = _fir_probe_block(*key)
+        assert bool(lib.sbg_upfirdn2d_tail_supported(p)) == (key in tail_yes), key
+        assert lib.sbg_upfirdn2d_dact_rows(p) == dact_rows.get(key, -1), key
+        count += 1
+    assert count == 384
+    # beyond the product: (block, tail_supported, dact_rows).  The probe for the forward tail does not look at stride signs or at the
+    # operand's extent (the launch does); up-sampling is no FIR launch; segment geometry of two real shapes
+    ok = dict(dtype=B16, c=64, rows=16, cols=16, taps=4, exact=1, cl=True)
+    for extra, tail, rows in [(dict(in_stride={0: -64}), 1, -1), (dict(in_stride={3: 1 << 30}), 1, -1), (dict(up=2), 0, -1),
+                              (dict(n=4, c=128, rows=256, cols=257), 1, 1152), (dict(n=1, rows=64, cols=40), 1, 8)]:
+        p = _fir_probe_block(**{**ok, **extra})
+        assert (lib.sbg_upfirdn2d_tail_supported(p), lib.sbg_upfirdn2d_dact_rows(p)) == (tail, rows), extra
