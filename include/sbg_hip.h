@@ -463,6 +463,32 @@ int sbg_ws_truncate_mix(const float* W, const float* w_avg, float psi, const int
                         int S, int L, int D, int R, int Cn, sbg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Exact uint8 resampling: the two passes of PIL's `Image.resize` on 8-bit images (its `ImagingResampleHorizontal_8bpc` /
+ * `ImagingResampleVertical_8bpc`), which is the arithmetic of the reference's stylegan2ada/dataset_tool.py (`make_transform`, :199-248:
+ * `img.resize((w, h), LANCZOS | BOX)`).  Integer arithmetic only, so the result is the same bytes as PIL's.
+ * Images are uint8 with interleaved channels, [N, rows, width, C], C = 1 or 3; image n starts at `+ n * img_stride`, row y at
+ * `+ y * pitch` (bytes).  A crop box is the caller's pointer offset and extent: `src` may start at any byte.
+ * Tables (int32, on the device), one window per output index i of the resampled axis: bounds[2 i] = first input index,
+ * bounds[2 i + 1] = count <= ksize, and `count` coefficients with 22 fractional bits.
+ *   out = clamp((2^21 + sum_k in[first + k] * coeff[k]) >> 22, 0, 255),  the sum in wrapping int32, the shift arithmetic.
+ * A window that leaves the input extent (a table that does not belong to these sizes) is clipped, never dereferenced.
+ *
+ * sbg_u8_resample_h: every row of [N, rows, in_w, C] -> [N, rows, out_w, C].  `coeffs_t` is tap-major, int32 [ksize, out_w].  A
+ * workgroup stages the input span of `strip` consecutive output pixels of a row in LDS (dword loads, bytes at the unaligned ends) and
+ * each work-item sums one output pixel from it; `strip` is a power of two in [16, 256] and `span` the largest number of input pixels
+ * any strip's windows cover, both chosen by the caller from the table (the span must fit 60 KiB of LDS).  `dst` may have any pitch.
+ * sbg_u8_resample_v: every column of [N, in_h, row_bytes] -> [N, out_h, row_bytes], a row being a flat array of row_bytes = width * C
+ * bytes.  `coeffs` is int32 [out_h, ksize].  A work-item owns one dword of an output row: `dst`, `dst_pitch` and `dst_img_stride` must
+ * be multiples of 4 and dst_pitch >= row_bytes rounded up to 4 (the pad bytes of a row are written, with unspecified values).  `src`
+ * is read as dwords when its base, pitch and image stride are multiples of 4 and the pitch covers the rounded row (then up to 3 bytes
+ * behind the end of a row are read, the last row's included: they lie inside the row's pitch), else as guarded bytes. */
+int sbg_u8_resample_h(const uint8_t* src, int64_t src_img_stride, int64_t src_pitch, uint8_t* dst, int64_t dst_img_stride, int64_t dst_pitch,
+                      int N, int rows, int in_w, int out_w, int C, const int* bounds, const int* coeffs_t, int ksize, int strip, int span,
+                      sbg_stream_t stream);
+int sbg_u8_resample_v(const uint8_t* src, int64_t src_img_stride, int64_t src_pitch, uint8_t* dst, int64_t dst_img_stride, int64_t dst_pitch,
+                      int N, int row_bytes, int in_h, int out_h, const int* bounds, const int* coeffs, int ksize, sbg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * In-process launch timing (measurement only; bench.py's roofline figures come from here).
  * While enabled, every kernel launch of this library is bracketed by two hipEvents recorded on the launch stream
  * and logged with its algorithmic flops / bytes.  sbg_prof_fetch() synchronises the logged events, writes up to `max`
@@ -473,8 +499,10 @@ enum sbg_kernel_kind {
     SBG_K_SCALE_NC = 6, SBG_K_DOT_HW = 7, SBG_K_SN_POWER = 9, SBG_K_ATTENTION = 10, SBG_K_GRID_SAMPLE = 11, SBG_K_FILTER1D = 12, SBG_K_COLOR = 13, SBG_K_WEIGHT_PREP = 14, SBG_K_TORGB = 15, SBG_K_FROMRGB = 16,
     SBG_K_GROUPED_GEMM = 17, SBG_K_PPL = 18,    /* SBG_K_PPL: dims[0] = variant: 0 slerp / 1 lerp endpoints, 2 image prep, 3 distance */
     SBG_K_PROJECTOR = 19,       /* one record per launch; dims[0] = variant: 0 reg / 1 reg_bwd / 2 normalize / 3 sqdist / 4 sqdist_bwd, dims[1] = stage */
-    SBG_K_IMAGE_EXPORT = 20     /* dims[0] = variant: 0 quantize_tile (N, C, H, W, rule, dims[6] = 1 four planar pixels / 2 four channel-minor
+    SBG_K_IMAGE_EXPORT = 20,    /* dims[0] = variant: 0 quantize_tile (N, C, H, W, rule, dims[6] = 1 four planar pixels / 2 four channel-minor
                                  * pixels / 3 one pixel per work-item), 1 truncate_mix (R * Cn, L, D, dims[4] = 1 vec4 / 2 scalar) */
+    SBG_K_RESAMPLE = 21         /* dims[0] = variant: 0 h (N, rows, in_w, out_w, C, dims[6] = strip), 1 v (N, row_bytes, in_h, out_h, ksize,
+                                 * dims[6] = 1 dword / 2 byte loads) */
 };
 /* Kernel-variant codes in the records of the streaming kernels (which kernel served the launch):
  *   bias_act     dims[4] = 1 vec8 / 2 scalar,  dims[5] = bias mode (0 none, 1 channel-minor vector, 2 one per 8-vector, 3 generic)
