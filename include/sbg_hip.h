@@ -489,6 +489,24 @@ int sbg_u8_resample_v(const uint8_t* src, int64_t src_img_stride, int64_t src_pi
                       int N, int row_bytes, int in_h, int out_h, const int* bounds, const int* coeffs, int ksize, sbg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * k-nearest-neighbour arithmetic of the precision / recall metric (metrics/precision_recall.py of the reference) over fp16 feature
+ * matrices, dense rows of F elements, as an implicit rows x manifold GEMM on the matrix cores; the [R, C] distance matrix is never
+ * written.  n(x) = sum x_f^2 and s(x, y) = sum x_f y_f are fp32 sums of fp16 products, d2 = max((n(x) + n(y)) - 2 s, 0) in fp32,
+ * d = fp16_rn(sqrt_f32(d2)); selection and comparison happen on these fp16 values.
+ *   sbg_knn_kth_radius:  out[i] (fp16 [R]) = the (k + 1)-th smallest d(rows[i], manifold[j]) over j -- `dist.kthvalue(nhood_size + 1)`;
+ *                        when `rows` is a slice of `manifold` the self-distance takes part, as in the reference.
+ *   sbg_knn_in_manifold: out[i] (uint8 [P]) = 1 when d(probes[i], manifold[j]) <= radius[j] (fp16 [C]) for some j -- `(dist <= kth).any(dim=1)`.
+ * k + 1 <= 8, C >= k + 1, F a multiple of 8, features and workspace 16-byte aligned; anything else is an error.  The manifold columns
+ * are split over workgroups when the rows alone do not fill the chip; partial results go through `workspace`
+ * (sbg_knn_workspace(R, C, k, membership) bytes, -1 for unsupported sizes: the norms, R + C floats, and per (row, run) a list of 4 | 8
+ * floats for the radius or one byte for the membership, where k is ignored) and are merged by a second launch in a fixed order.  No
+ * atomics: two runs give the same bits. */
+int64_t sbg_knn_workspace(int R, int C, int k, int membership);
+int sbg_knn_kth_radius(const void* rows, const void* manifold, int R, int C, int64_t F, int k, void* out, void* workspace, sbg_stream_t stream);
+int sbg_knn_in_manifold(const void* probes, const void* manifold, const void* radius, int P, int C, int64_t F, uint8_t* out, void* workspace,
+                        sbg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * In-process launch timing (measurement only; bench.py's roofline figures come from here).
  * While enabled, every kernel launch of this library is bracketed by two hipEvents recorded on the launch stream
  * and logged with its algorithmic flops / bytes.  sbg_prof_fetch() synchronises the logged events, writes up to `max`
@@ -501,8 +519,10 @@ enum sbg_kernel_kind {
     SBG_K_PROJECTOR = 19,       /* one record per launch; dims[0] = variant: 0 reg / 1 reg_bwd / 2 normalize / 3 sqdist / 4 sqdist_bwd, dims[1] = stage */
     SBG_K_IMAGE_EXPORT = 20,    /* dims[0] = variant: 0 quantize_tile (N, C, H, W, rule, dims[6] = 1 four planar pixels / 2 four channel-minor
                                  * pixels / 3 one pixel per work-item), 1 truncate_mix (R * Cn, L, D, dims[4] = 1 vec4 / 2 scalar) */
-    SBG_K_RESAMPLE = 21         /* dims[0] = variant: 0 h (N, rows, in_w, out_w, C, dims[6] = strip), 1 v (N, row_bytes, in_h, out_h, ksize,
+    SBG_K_RESAMPLE = 21,        /* dims[0] = variant: 0 h (N, rows, in_w, out_w, C, dims[6] = strip), 1 v (N, row_bytes, in_h, out_h, ksize,
                                  * dims[6] = 1 dword / 2 byte loads) */
+    SBG_K_PR = 22               /* dims[0] = variant: 0 single / 1 split (the tile kernel, one / several column runs per row tile), 2 merge,
+                                 * 3 norms; then R, C, F, k, runs, dims[6] = 0 radius / 1 membership */
 };
 /* Kernel-variant codes in the records of the streaming kernels (which kernel served the launch):
  *   bias_act     dims[4] = 1 vec8 / 2 scalar,  dims[5] = bias mode (0 none, 1 channel-minor vector, 2 one per 8-vector, 3 generic)

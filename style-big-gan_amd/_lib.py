@@ -105,12 +105,13 @@ class ProfRecord(ctypes.Structure):
 
 KERNEL_KINDS = {1: "bias_act", 2: "upfirdn2d", 3: "conv_igemm", 4: "conv_wgrad", 5: "wgrad_reduce", 6: "scale_nc", 7: "dot_hw", 9: "sn_power", 10: "attention",
                 11: "grid_sample", 12: "filter1d", 13: "color", 14: "weight_prep", 15: "torgb", 16: "fromrgb", 17: "grouped_gemm", 18: "ppl",
-                19: "projector", 20: "image_export", 21: "resample"}
+                19: "projector", 20: "image_export", 21: "resample", 22: "pr"}
 PPL_VARIANTS = {0: "slerp", 1: "lerp", 2: "prep", 3: "dist"}        # dims[0] of a "ppl" launch record
 PROJ_VARIANTS = {0: "reg", 1: "reg_bwd", 2: "normalize", 3: "sqdist", 4: "sqdist_bwd"}      # dims[0] of a "projector" launch record
 IMG_VARIANTS = {0: "quantize_tile", 1: "truncate_mix"}      # dims[0] of an "image_export" launch record
 QUANT_RULES = {"grid": 0, "clamp": 1}                       # enum sbg_quant_rule
 RESAMPLE_VARIANTS = {0: "h", 1: "v"}                        # dims[0] of a "resample" launch record
+PR_VARIANTS = {0: "single", 1: "split", 2: "merge", 3: "norms"}    # dims[0] of a "pr" launch record (dims[6]: 0 radius, 1 membership)
 
 _lib = None
 _lock = threading.Lock()
@@ -190,6 +191,9 @@ SYMBOLS = [
     ("sbg_ws_truncate_mix", _c.c_int, [_c.c_void_p] * 2 + [_c.c_float] + [_c.c_void_p] * 4 + [_c.c_int] * 5 + [_c.c_void_p]),
     ("sbg_u8_resample_h", _c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int64] * 2 + [_c.c_int] * 5 + [_c.c_void_p] * 2 + [_c.c_int] * 3 + [_c.c_void_p]),
     ("sbg_u8_resample_v", _c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int64] * 2 + [_c.c_int] * 4 + [_c.c_void_p] * 2 + [_c.c_int, _c.c_void_p]),
+    ("sbg_knn_workspace", _c.c_int64, [_c.c_int] * 4),
+    ("sbg_knn_kth_radius", _c.c_int, [_c.c_void_p] * 2 + [_c.c_int, _c.c_int, _c.c_int64, _c.c_int] + [_c.c_void_p] * 3),
+    ("sbg_knn_in_manifold", _c.c_int, [_c.c_void_p] * 3 + [_c.c_int, _c.c_int, _c.c_int64] + [_c.c_void_p] * 3),
     ("sbg_prof_enable", _c.c_int, [_c.c_int]),
     ("sbg_prof_fetch", _c.c_int, [_c.POINTER(ProfRecord), _c.c_int]),
 ]

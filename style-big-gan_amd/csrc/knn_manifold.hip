@@ -1,0 +1,404 @@
+// knn_manifold.hip -- the k-nearest-neighbour arithmetic of the precision / recall metric (metrics/precision_recall.py of the reference,
+// `compute_distances` + `kthvalue` + `(dist <= kth).any`) as an implicit rows x manifold GEMM on the matrix cores whose [R, C] distance
+// matrix never leaves the chip.  Features are fp16 [*, F], dense rows.
+//   kth_radius:   out[i] = (k + 1)-th smallest of d(rows[i], manifold[j]) over j            (fp16)
+//   in_manifold:  out[i] = any_j d(probes[i], manifold[j]) <= radius[j]                      (uint8)
+// Arithmetic: n(x) = sum x_f^2 and s(x, y) = sum x_f y_f are fp32 sums of fp16 products; d2 = max((n(x) + n(y)) - 2 s, 0) in fp32;
+// d = fp16_rn(sqrt_f32(d2)).  Rounding is monotone, so the radius kernel selects on d2 and rounds the selected value once.
+//
+// Launches: a norm pass (one wave per row), the tile kernel, and -- when the manifold columns are split over workgroups -- a merge.
+// Tile kernel: workgroup = 256 lanes = 4 waves, tile 128 manifold points (MFMA A operand, rows of the accumulator = registers of a
+// lane) x 128 query rows (B operand, accumulator column = lane & 15), K-step 64, v_mfma_f32_16x16x32_f16.  So a lane holds, for each
+// of 4 query rows, 16 manifold candidates per tile, and reduces them into per-query registers: a sorted list of the KL smallest d2
+// (radius) or a flag (membership).  Staging is global -> VGPR -> LDS in full 128-B lines (8 lanes per row), issue early / write late,
+// two LDS stages, one barrier per K-step.  LDS image per operand: [k-group 0..7][130 cells of 16 B]: the 2-cell pad makes the 16 cells
+// a quarter-wave writes (2 rows x 8 k-groups) distinct mod 16, and a fragment read touches 16 consecutive cells: both conflict-free.
+// A workgroup owns one query tile and a contiguous run of manifold tiles; at the end the lists of the 8 lane groups that share a query
+// are merged through LDS.  With one run per query tile the result is written directly (variant `single`); otherwise every run writes
+// its partial list / flag to the workspace and a second launch merges the runs in index order (`split` + `merge`).  The k smallest of
+// a multiset and an OR do not depend on the order, and there are no atomics: two runs give the same bits.
+// Launch-log key: kind SBG_K_PR, dims = {variant (0 single, 1 split, 2 merge, 3 norms), R, C, F, k, runs, 0 radius / 1 membership}.
+#include "conv_common.h"
+
+using namespace sbgconv;
+
+namespace {
+
+constexpr int kPrSingle = 0, kPrSplit = 1, kPrMerge = 2, kPrNorms = 3;
+
+constexpr int BT = 128;                     // tile side: manifold points and query rows
+constexpr int BK = 64;                      // K-step
+constexpr int KG = BK / 8;                  // 16-B k-groups per K-step
+constexpr int KGS = BT + 2;                 // cells per k-group (padded, see above)
+constexpr int OP_BYTES = KG * KGS * 16;     // one operand of one stage
+constexpr int STAGE = 2 * OP_BYTES;
+constexpr int PARAM_OFF = 2 * STAGE;        // behind the two stages: norms and radii of the manifold tile, double-buffered by tile parity
+constexpr int LDS_BYTES = PARAM_OFF + 2 * 2 * BT * 4;
+constexpr int kMaxK1 = 8;                   // k + 1 <= 8
+constexpr int kTargetGroups = 512;          // workgroups to aim for: 256 CUs x 2 resident
+
+struct KnnArgs {
+    const unsigned short* q; const unsigned short* m;     // query rows [R, F], manifold [C, F]
+    const float* nq; const float* nm;                      // their squared norms
+    const unsigned short* radius;                          // membership: fp16 [C]
+    void* out; void* part;
+    int R, C, F, k, runs, ctiles, tiles_per_run;
+};
+
+__device__ __forceinline__ float wave_sum(float v)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+// n[r] = sum_f x[r, f]^2: one wave per row, 16-B loads, a lane-strided fp32 sum and a butterfly.
+__global__ __launch_bounds__(256) void knn_norms_kernel(const unsigned short* __restrict__ x, float* __restrict__ n, int rows, int F)
+{
+    const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const unsigned short* p = x + (int64_t)row * F;
+    float s = 0.f;
+    for (int c = lane * 8; c < F; c += 512) {
+        const short8_t v = *reinterpret_cast<const short8_t*>(p + c);
+#pragma unroll
+        for (int e = 0; e < 8; e++) { const float f = f16_bits_to_f32((unsigned short)v[e]); s = fmaf(f, f, s); }
+    }
+    s = wave_sum(s);
+    if (lane == 0) n[row] = s;
+}
+
+// keep the KL smallest, ascending; equal values are kept as often as they occur (kthvalue counts duplicates)
+template <int KL>
+__device__ __forceinline__ void list_insert(float (&L)[KL], float v)
+{
+    if (v < L[KL - 1]) {
+#pragma unroll
+        for (int t = 0; t < KL; t++) { const float lo = fminf(L[t], v); v = fmaxf(L[t], v); L[t] = lo; }
+    }
+}
+
+__device__ __forceinline__ float dist2(float nx, float ny, float s)
+{
+#pragma clang fp contract(off)
+    return fmaxf((nx + ny) - 2.0f * s, 0.f);
+}
+
+__device__ __forceinline__ float dist_f16(float d2) { return (float)(_Float16)sqrtf(d2); }
+
+template <int KL, bool MEMBER>
+__global__ __launch_bounds__(256) void knn_tile_kernel(KnnArgs p)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    float* const prm = reinterpret_cast<float*>(smem + PARAM_OFF);          // [parity][0: norm, 1: radius][BT]
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int qt = blockIdx.x / p.runs, run = blockIdx.x - qt * p.runs;
+    const int q0 = qt * BT;
+    const int t_begin = run * p.tiles_per_run;
+    const int t_end = min(t_begin + p.tiles_per_run, p.ctiles);
+
+    // staging coordinates: 8 consecutive lanes read one 128-B line of a row
+    const int lrow = tid >> 3, kg = tid & 7;
+    int64_t q_off[4]; bool q_ok[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int r = q0 + lrow + 32 * i;
+        q_ok[i] = r < p.R;
+        q_off[i] = (int64_t)(q_ok[i] ? r : 0) * p.F;
+    }
+
+    // MFMA coordinates: waves 2 (manifold) x 2 (query), wave tile 64 x 64 = 4 x 4 MFMA tiles
+    const int wc = (wave >> 1) * 64, wp = (wave & 1) * 64;
+    const int fr = lane & 15, fg = lane >> 4;
+    float nqv[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) { const int r = q0 + wp + 16 * j + fr; nqv[j] = r < p.R ? p.nq[r] : 0.f; }
+
+    float L[4][KL];
+    int inside[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        inside[j] = 0;
+#pragma unroll
+        for (int t = 0; t < KL; t++) L[j][t] = __builtin_inff();
+    }
+
+    const int nsteps = (p.F + BK - 1) / BK;
+    for (int tile = t_begin; tile < t_end; tile++) {
+        const int c0 = tile * BT, par = (tile - t_begin) & 1;
+        int64_t m_off[4]; bool m_ok[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int c = c0 + lrow + 32 * i;
+            m_ok[i] = c < p.C;
+            m_off[i] = (int64_t)(m_ok[i] ? c : 0) * p.F;
+        }
+        if (tid < BT) {       // a padded column is at +inf (and has a negative radius): read after the K loop's barriers
+            const int c = c0 + tid;
+            prm[(par * 2 + 0) * BT + tid] = c < p.C ? p.nm[c] : __builtin_inff();
+            if (MEMBER) prm[(par * 2 + 1) * BT + tid] = c < p.C ? f16_bits_to_f32(p.radius[c]) : -1.f;
+        }
+
+        short8_t ra[4], rb[4];
+        auto issue_loads = [&](int step) {
+            const int k0 = step * BK + kg * 8;
+            const bool kok = k0 < p.F;          // F % 8 == 0: a 16-B piece is wholly inside or outside the row
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                short8_t v = {0, 0, 0, 0, 0, 0, 0, 0};
+                if (kok && m_ok[i]) v = *reinterpret_cast<const short8_t*>(p.m + m_off[i] + k0);
+                ra[i] = v;
+            }
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                short8_t v = {0, 0, 0, 0, 0, 0, 0, 0};
+                if (kok && q_ok[i]) v = *reinterpret_cast<const short8_t*>(p.q + q_off[i] + k0);
+                rb[i] = v;
+            }
+        };
+        auto write_stage = [&](int buf) {
+            unsigned char* sa = smem + buf * STAGE;
+            unsigned char* sb = sa + OP_BYTES;
+#pragma unroll
+            for (int i = 0; i < 4; i++) *reinterpret_cast<short8_t*>(sa + (kg * KGS + lrow + 32 * i) * 16) = ra[i];
+#pragma unroll
+            for (int i = 0; i < 4; i++) *reinterpret_cast<short8_t*>(sb + (kg * KGS + lrow + 32 * i) * 16) = rb[i];
+        };
+
+        float4_t acc[4][4];
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+#pragma unroll
+            for (int j = 0; j < 4; j++) acc[i][j] = float4_t{0.f, 0.f, 0.f, 0.f};
+
+        issue_loads(0);
+        write_stage(0);
+        __syncthreads();
+        for (int s = 0; s < nsteps; s++) {
+            const int buf = s & 1;
+            if (s + 1 < nsteps) issue_loads(s + 1);
+            const unsigned char* sa = smem + buf * STAGE;
+            const unsigned char* sb = sa + OP_BYTES;
+#pragma unroll
+            for (int ks = 0; ks < 2; ks++) {
+                short8_t fa[4], fb[4];
+#pragma unroll
+                for (int i = 0; i < 4; i++) fa[i] = *reinterpret_cast<const short8_t*>(sa + ((4 * ks + fg) * KGS + wc + 16 * i + fr) * 16);
+#pragma unroll
+                for (int j = 0; j < 4; j++) fb[j] = *reinterpret_cast<const short8_t*>(sb + ((4 * ks + fg) * KGS + wp + 16 * j + fr) * 16);
+#pragma unroll
+                for (int i = 0; i < 4; i++)
+#pragma unroll
+                    for (int j = 0; j < 4; j++) acc[i][j] = Mfma<f16_mfma>::run(fa[i], fb[j], acc[i][j]);
+            }
+            if (s + 1 < nsteps) write_stage(buf ^ 1);
+            __syncthreads();
+        }
+
+        // the lane holds manifold points c0 + wc + 16 i + 4 fg + e of query rows q0 + wp + 16 j + fr
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                const int col = wc + 16 * i + 4 * fg + e;
+                const float nmv = prm[(par * 2 + 0) * BT + col];
+                const float rv = MEMBER ? prm[(par * 2 + 1) * BT + col] : 0.f;
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    const float d2 = dist2(nqv[j], nmv, acc[i][j][e]);
+                    if (MEMBER) inside[j] |= (dist_f16(d2) <= rv) ? 1 : 0;
+                    else list_insert<KL>(L[j], d2);
+                }
+            }
+        }
+    }
+
+    // merge the lane groups and the two manifold waves that share a query row; the staging area is free after the last barrier
+    const int q = q0 + tid;
+    if (MEMBER) {
+        int* fl = reinterpret_cast<int*>(smem);                  // [manifold wave][BT]
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            int v = inside[j];
+            v |= __shfl_xor(v, 16, 64);
+            v |= __shfl_xor(v, 32, 64);
+            if (fg == 0) fl[(wave >> 1) * BT + wp + 16 * j + fr] = v;
+        }
+        __syncthreads();
+        if (tid < BT && q < p.R) {
+            const unsigned char f = (unsigned char)((fl[tid] | fl[BT + tid]) != 0);
+            if (p.runs == 1) reinterpret_cast<unsigned char*>(p.out)[q] = f;
+            else reinterpret_cast<unsigned char*>(p.part)[(int64_t)run * p.R + q] = f;
+        }
+    } else {
+        constexpr int QS = 8 * KL + 1;                           // odd stride: the merging lanes hit distinct banks
+        float* ms = reinterpret_cast<float*>(smem);              // [BT][8 lists][KL]
+        const int slot = (wave >> 1) * 4 + fg;
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+#pragma unroll
+            for (int t = 0; t < KL; t++) ms[(wp + 16 * j + fr) * QS + slot * KL + t] = L[j][t];
+        __syncthreads();
+        if (tid < BT && q < p.R) {
+            float M[KL];
+#pragma unroll
+            for (int t = 0; t < KL; t++) M[t] = __builtin_inff();
+            for (int s = 0; s < 8 * KL; s++) list_insert<KL>(M, ms[tid * QS + s]);
+            if (p.runs == 1) {
+                float r = M[0];
+#pragma unroll
+                for (int t = 1; t < KL; t++) r = (t == p.k) ? M[t] : r;
+                reinterpret_cast<unsigned short*>(p.out)[q] = f32_to_f16_bits(sqrtf(r));
+            } else {
+                float* dst = reinterpret_cast<float*>(p.part) + ((int64_t)q * p.runs + run) * KL;
+#pragma unroll
+                for (int t = 0; t < KL; t++) dst[t] = M[t];
+            }
+        }
+    }
+}
+
+// Second stage of the split variant: one work-item per query row walks the runs in index order.
+template <int KL>
+__global__ __launch_bounds__(256) void knn_merge_radius_kernel(const float* __restrict__ part, unsigned short* __restrict__ out, int R, int runs, int k)
+{
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= R) return;
+    float M[KL];
+#pragma unroll
+    for (int t = 0; t < KL; t++) M[t] = __builtin_inff();
+    const float* src = part + (int64_t)q * runs * KL;
+    for (int s = 0; s < runs * KL; s++) list_insert<KL>(M, src[s]);
+    float r = M[0];
+#pragma unroll
+    for (int t = 1; t < KL; t++) r = (t == k) ? M[t] : r;
+    out[q] = f32_to_f16_bits(sqrtf(r));
+}
+
+__global__ __launch_bounds__(256) void knn_merge_member_kernel(const unsigned char* __restrict__ part, unsigned char* __restrict__ out, int R, int runs)
+{
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= R) return;
+    unsigned char f = 0;
+    for (int s = 0; s < runs; s++) f |= part[(int64_t)s * R + q];
+    out[q] = f;
+}
+
+struct KnnPlan { int rtiles, ctiles, tiles_per_run, runs; int64_t nq_off, nm_off, part_off, bytes; };
+
+int list_len(int k) { return k + 1 <= 4 ? 4 : 8; }
+
+// Runs per query tile: enough workgroups to fill the chip twice when the query tiles alone do not.  A function of the shape only, so
+// the workspace query and the launch agree and a result does not depend on the device it ran on.
+bool knn_plan(int R, int C, int k, bool member, KnnPlan& pl)
+{
+    if (R < 1 || C < 1 || k < 0 || k + 1 > kMaxK1 || R > (1 << 24) || C > (1 << 24)) return false;
+    pl.rtiles = (R + BT - 1) / BT;
+    pl.ctiles = (C + BT - 1) / BT;
+    int want = kTargetGroups / pl.rtiles;
+    want = want < 1 ? 1 : (want > pl.ctiles ? pl.ctiles : want);
+    pl.tiles_per_run = (pl.ctiles + want - 1) / want;
+    pl.runs = (pl.ctiles + pl.tiles_per_run - 1) / pl.tiles_per_run;
+    auto up16 = [](int64_t v) { return (v + 15) & ~(int64_t)15; };
+    pl.nq_off = 0;
+    pl.nm_off = up16(4 * (int64_t)R);
+    pl.part_off = pl.nm_off + up16(4 * (int64_t)C);
+    // partial results of the runs: a list of floats per (row, run) for the radius, one byte per (run, row) for the membership
+    pl.bytes = pl.part_off + (pl.runs > 1 ? (member ? up16((int64_t)R * pl.runs) : 4 * (int64_t)R * pl.runs * list_len(k)) : 0);
+    return true;
+}
+
+int knn_check(const char* what, const void* q, const void* m, const void* out, const void* ws, int R, int C, int64_t F, int k, bool member, KnnPlan& pl)
+{
+    SBG_CHECK(q && m && out && ws, "%s: null pointer", what);
+    SBG_CHECK(k >= 0 && k + 1 <= kMaxK1, "%s: k + 1 = %d neighbours, at most %d are supported", what, k + 1, kMaxK1);
+    SBG_CHECK(R >= 1 && C >= 1 && R <= (1 << 24) && C <= (1 << 24), "%s: bad sizes R=%d C=%d", what, R, C);
+    SBG_CHECK(C >= k + 1, "%s: the manifold has %d points, the (k + 1)-th neighbour needs %d", what, C, k + 1);
+    SBG_CHECK(F >= 8 && F % 8 == 0 && F <= (1 << 24), "%s: the feature width %lld must be a multiple of 8 (16-byte pieces) in [8, 2^24]", what, (long long)F);
+    SBG_CHECK(sbg_aligned16(q) && sbg_aligned16(m) && sbg_aligned16(ws), "%s: features and workspace must be 16-byte aligned", what);
+    SBG_CHECK(knn_plan(R, C, k, member, pl), "%s: bad sizes", what);
+    return SBG_OK;
+}
+
+int knn_norms(const unsigned short* x, float* n, int rows, int F, hipStream_t s)
+{
+    SbgProfScope prof(s, SBG_K_PR, 2.0 * rows * (double)F, 2.0 * rows * (double)F + 4.0 * rows, {kPrNorms, rows, 0, F});
+    SBG_LAUNCH(knn_norms_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, x, n, rows, F);
+    SBG_HIP_LAUNCH_CHECK();
+    return SBG_OK;
+}
+
+template <int KL, bool MEMBER>
+int knn_launch_tiles(const KnnArgs& a, const KnnPlan& pl, hipStream_t s)
+{
+    if (!SBG_RAISE_LDS_ONCE((knn_tile_kernel<KL, MEMBER>), LDS_BYTES))
+        return sbg_fail(SBG_ERR_LAUNCH, "knn_manifold: cannot raise the dynamic LDS limit to %d bytes", LDS_BYTES);
+    SbgProfScope prof(s, SBG_K_PR, 2.0 * a.R * (double)a.C * a.F, 2.0 * ((double)a.R + a.C) * a.F,
+                      {pl.runs == 1 ? kPrSingle : kPrSplit, a.R, a.C, a.F, a.k, pl.runs, MEMBER ? 1 : 0});
+    SBG_LAUNCH((knn_tile_kernel<KL, MEMBER>), dim3((unsigned)(pl.rtiles * pl.runs)), dim3(256), LDS_BYTES, s, a);
+    SBG_HIP_LAUNCH_CHECK();
+    return SBG_OK;
+}
+
+// What the two entry points share: argument checks, the plan, the norm passes and the tile launch.  On SBG_OK with pl.runs > 1 the
+// caller launches its merge over a.part.
+template <bool MEMBER>
+int knn_run(const char* what, const void* q, const void* m, const void* radius, int R, int C, int64_t F, int k, void* out, void* workspace,
+            hipStream_t s, KnnArgs& a, KnnPlan& pl)
+{
+    const int rc = knn_check(what, q, m, out, workspace, R, C, F, k, MEMBER, pl);
+    if (rc != SBG_OK) return rc;
+    char* ws = (char*)workspace;
+    a.q = (const unsigned short*)q; a.m = (const unsigned short*)m;
+    a.nq = (const float*)(ws + pl.nq_off); a.nm = (const float*)(ws + pl.nm_off); a.radius = (const unsigned short*)radius;
+    a.out = out; a.part = ws + pl.part_off;
+    a.R = R; a.C = C; a.F = (int)F; a.k = k; a.runs = pl.runs; a.ctiles = pl.ctiles; a.tiles_per_run = pl.tiles_per_run;
+    int st = knn_norms(a.q, (float*)(ws + pl.nq_off), R, a.F, s);
+    if (st != SBG_OK) return st;
+    st = knn_norms(a.m, (float*)(ws + pl.nm_off), C, a.F, s);
+    if (st != SBG_OK) return st;
+    if (MEMBER) return knn_launch_tiles<4, true>(a, pl, s);
+    return list_len(k) == 4 ? knn_launch_tiles<4, false>(a, pl, s) : knn_launch_tiles<8, false>(a, pl, s);
+}
+
+} // namespace
+
+extern "C" int64_t sbg_knn_workspace(int R, int C, int k, int membership)
+{
+    KnnPlan pl;
+    if (!knn_plan(R, C, membership ? 0 : k, membership != 0, pl)) return -1;
+    return pl.bytes;
+}
+
+extern "C" int sbg_knn_kth_radius(const void* rows, const void* manifold, int R, int C, int64_t F, int k, void* out, void* workspace, sbg_stream_t stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    KnnArgs a; KnnPlan pl;
+    const int st = knn_run<false>("knn_kth_radius", rows, manifold, nullptr, R, C, F, k, out, workspace, s, a, pl);
+    if (st != SBG_OK) return st;
+    if (pl.runs > 1) {
+        const int KL = list_len(k);
+        SbgProfScope prof(s, SBG_K_PR, 0.0, 4.0 * R * (double)pl.runs * KL + 2.0 * R, {kPrMerge, R, C, a.F, k, pl.runs, 0});
+        if (KL == 4) SBG_LAUNCH(knn_merge_radius_kernel<4>, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, s, (const float*)a.part, (unsigned short*)out, R, pl.runs, k);
+        else         SBG_LAUNCH(knn_merge_radius_kernel<8>, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, s, (const float*)a.part, (unsigned short*)out, R, pl.runs, k);
+        SBG_HIP_LAUNCH_CHECK();
+    }
+    return SBG_OK;
+}
+
+extern "C" int sbg_knn_in_manifold(const void* probes, const void* manifold, const void* radius, int P, int C, int64_t F, uint8_t* out, void* workspace,
+                                   sbg_stream_t stream)
+{
+    SBG_CHECK(radius, "knn_in_manifold: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    KnnArgs a; KnnPlan pl;
+    const int st = knn_run<true>("knn_in_manifold", probes, manifold, radius, P, C, F, 0, out, workspace, s, a, pl);
+    if (st != SBG_OK) return st;
+    if (pl.runs > 1) {
+        SbgProfScope prof(s, SBG_K_PR, 0.0, (double)P * pl.runs + P, {kPrMerge, P, C, a.F, 0, pl.runs, 1});
+        SBG_LAUNCH(knn_merge_member_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, (const unsigned char*)a.part, (unsigned char*)out, P, pl.runs);
+        SBG_HIP_LAUNCH_CHECK();
+    }
+    return SBG_OK;
+}

@@ -6,6 +6,7 @@ import numpy as np
 import scipy.linalg
 import torch
 
+from ..torch_utils.ops import knn_manifold
 from . import metric_utils
 
 INCEPTION = 'inception-2015-12-05.pt'      # reference: nvlabs-fi-cdn URL / './inception-2015-12-05.pt' (frechet_inception_distance.py:22-23)
@@ -116,6 +117,37 @@ def precision_recall(real_features, gen_features, nhood_size, row_batch_size, co
     return results['precision'], results['recall']
 
 
+def _rank_share(n, num_gpus, rank):
+    """contiguous share [lo, hi) of n rows for `rank`; the shares differ by at most one row"""
+    return n * rank // num_gpus, n * (rank + 1) // num_gpus
+
+
+def precision_recall_fused(real_features, gen_features, nhood_size, row_batch_size, num_gpus=1, rank=0):
+    """`precision_recall` on the fused k-NN ops (torch_utils/ops/knn_manifold.py): the distance matrix is never stored and nothing
+    crosses to the host but the two counts.  Every rank holds all features; it computes the radii of a contiguous share of the
+    manifold rows and the membership of a contiguous share of the probe rows, the radii are exchanged with one all_gather and
+    the membership counts with one all_reduce per direction, and every rank returns the numbers."""
+    assert 0 <= rank < num_gpus
+    results = dict()
+    for name, manifold, probes in [('precision', real_features, gen_features), ('recall', gen_features, real_features)]:
+        lo, hi = _rank_share(manifold.shape[0], num_gpus, rank)
+        kth = [knn_manifold.kth_radius(batch, manifold, nhood_size) for batch in manifold[lo:hi].split(row_batch_size)]
+        kth = torch.cat(kth) if kth else torch.empty([0], dtype=torch.float16, device=manifold.device)
+        if num_gpus > 1:        # shares differ by at most one row: pad to the largest, gather once, cut the pads
+            longest = -(-manifold.shape[0] // num_gpus)
+            parts = [torch.empty([longest], dtype=kth.dtype, device=kth.device) for _ in range(num_gpus)]
+            torch.distributed.all_gather(parts, torch.nn.functional.pad(kth, [0, longest - kth.shape[0]]))
+            kth = torch.cat([part[:b - a] for part, (a, b) in zip(parts, (_rank_share(manifold.shape[0], num_gpus, r) for r in range(num_gpus)))])
+        lo, hi = _rank_share(probes.shape[0], num_gpus, rank)
+        count = torch.zeros([], dtype=torch.int64, device=probes.device)
+        for batch in probes[lo:hi].split(row_batch_size):
+            count += knn_manifold.in_manifold(batch, manifold, kth).sum()
+        if num_gpus > 1:
+            torch.distributed.all_reduce(count)
+        results[name] = float(count.to(torch.float32) / probes.shape[0])       # the fp32 mean of the reference's 0 / 1 vector
+    return results['precision'], results['recall']
+
+
 def compute_pr(opts, max_real, num_gen, nhood_size, row_batch_size, col_batch_size, dataset_name='image_folder'):
     kw = metric_utils.detector_call_kwargs(opts, VGG16, dict(return_features=True))
     half = torch.float16 if torch.device(opts.device).type == 'cuda' else torch.float32
@@ -123,4 +155,6 @@ def compute_pr(opts, max_real, num_gen, nhood_size, row_batch_size, col_batch_si
                                                           capture_all=True, max_items=max_real).get_all_torch().to(half).to(opts.device)
     gen = metric_utils.compute_feature_stats_for_generator(opts=opts, dataset_name=dataset_name, detector_url=VGG16, detector_kwargs=kw, rel_lo=0, rel_hi=1,
                                                            capture_all=True, max_items=num_gen).get_all_torch().to(half).to(opts.device)
+    if torch.device(opts.device).type == 'cuda':      # fused HIP kernels; the CPU keeps the reference's cdist / kthvalue structure
+        return precision_recall_fused(real, gen, nhood_size, row_batch_size, opts.num_gpus, opts.rank)
     return precision_recall(real, gen, nhood_size, row_batch_size, col_batch_size, opts.num_gpus, opts.rank)

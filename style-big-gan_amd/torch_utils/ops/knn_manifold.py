@@ -1,0 +1,96 @@
+"""The k-nearest-neighbour arithmetic of the precision / recall metric as fused HIP kernels (csrc/knn_manifold.hip).
+
+``kth_radius`` is the reference's ``dist.kthvalue(nhood_size + 1)`` and ``in_manifold`` its ``(dist <= kth).any(dim=1)``
+(stylegan2ada/metrics/precision_recall.py:48-60), both without the distance matrix ever being stored.  One definition for both devices:
+
+    n(x) = sum x_f^2,  s(x, y) = sum x_f y_f        products of the fp16 values, summed in fp32 (any order)
+    d2   = max((n(x) + n(y)) - 2 s, 0)               fp32, in that association
+    d    = fp16(sqrt_f32(d2))                        selection and comparison happen on these fp16 values
+
+Device tensors must be fp16 and run the kernels; a missing kernel or an unsupported input is an error, never a quiet torch fallback.
+CPU tensors run the same definition in torch (float64 sums rounded to fp32, then the steps above), so the metric's plumbing is testable
+without a GPU.
+"""
+import torch
+
+from ... import _lib
+
+MAX_NEIGHBOURS = 8          # k + 1 <= 8 (csrc/knn_manifold.hip)
+_CPU_ROWS = 1024            # rows per block of the CPU path
+
+
+def _check(rows, manifold, k):
+    if rows.ndim != 2 or manifold.ndim != 2 or rows.shape[1] != manifold.shape[1]:
+        raise RuntimeError(f"knn_manifold: expects [R, F] and [C, F], got {tuple(rows.shape)} and {tuple(manifold.shape)}")
+    if rows.device != manifold.device:
+        raise RuntimeError(f"knn_manifold: tensors on different devices ({rows.device}, {manifold.device})")
+    if not 0 <= k < MAX_NEIGHBOURS:
+        raise RuntimeError(f"knn_manifold: k + 1 = {k + 1} neighbours, at most {MAX_NEIGHBOURS} are supported")
+    if manifold.shape[0] < k + 1:
+        raise RuntimeError(f"knn_manifold: the manifold has {manifold.shape[0]} points, the (k + 1)-th neighbour needs {k + 1}")
+
+
+def _f16(x, what):
+    if x.dtype != torch.float16:
+        raise RuntimeError(f"{what}: device tensors must be float16, got {x.dtype}")
+    return x.contiguous()
+
+
+def _cpu_distances(rows, manifold, n_manifold):
+    """[r, C] fp16 distances of a block of rows by the definition above"""
+    x = rows.to(torch.float64)
+    n_rows = x.square().sum(1).to(torch.float32)
+    s = (x @ manifold.to(torch.float64).T).to(torch.float32)
+    d2 = ((n_rows[:, None] + n_manifold[None, :]) - 2 * s).clamp_(min=0)
+    return d2.sqrt().to(torch.float16)
+
+
+def _workspace(lib, R, C, k, membership, device):
+    nbytes = lib.sbg_knn_workspace(R, C, k, int(membership))
+    if nbytes < 0:
+        raise RuntimeError(f"knn_manifold: unsupported sizes R={R} C={C} k={k}")
+    return torch.empty([(nbytes + 3) // 4], dtype=torch.float32, device=device)
+
+
+def kth_radius(rows, manifold, k):
+    """rows [R, F], manifold [C, F] -> fp16 [R]: the (k + 1)-th smallest distance from each row to the manifold's points.  When
+    `rows` is a slice of `manifold` the self-distance takes part, as in the reference."""
+    _check(rows, manifold, k)
+    R, F = rows.shape
+    C = manifold.shape[0]
+    if rows.device.type != "cuda":
+        n_manifold = manifold.to(torch.float64).square().sum(1).to(torch.float32)
+        out = [_cpu_distances(b, manifold, n_manifold).to(torch.float32).kthvalue(k + 1).values.to(torch.float16) for b in rows.split(_CPU_ROWS)]
+        return torch.cat(out) if out else torch.empty([0], dtype=torch.float16)
+    rows, manifold = _f16(rows, "knn_manifold.kth_radius"), _f16(manifold, "knn_manifold.kth_radius")
+    out = torch.empty([R], dtype=torch.float16, device=rows.device)
+    if R == 0:
+        return out
+    lib = _lib.load()
+    ws = _workspace(lib, R, C, k, False, rows.device)
+    _lib.check(lib.sbg_knn_kth_radius(rows.data_ptr(), manifold.data_ptr(), R, C, F, k, out.data_ptr(), ws.data_ptr(), _lib.stream_ptr(rows.device)),
+               "sbg_knn_kth_radius")
+    return out
+
+
+def in_manifold(probes, manifold, radius):
+    """probes [P, F], manifold [C, F], radius [C] -> bool [P]: does the probe lie inside the ball of some manifold point"""
+    _check(probes, manifold, 0)
+    P, F = probes.shape
+    C = manifold.shape[0]
+    if radius.shape != (C,) or radius.device != manifold.device:
+        raise RuntimeError(f"knn_manifold.in_manifold: expects one radius per manifold point on its device, got {tuple(radius.shape)} on {radius.device}")
+    if probes.device.type != "cuda":
+        n_manifold = manifold.to(torch.float64).square().sum(1).to(torch.float32)
+        r = radius.to(torch.float16)
+        out = [(_cpu_distances(b, manifold, n_manifold) <= r).any(dim=1) for b in probes.split(_CPU_ROWS)]
+        return torch.cat(out) if out else torch.empty([0], dtype=torch.bool)
+    probes, manifold, radius = (_f16(t, "knn_manifold.in_manifold") for t in (probes, manifold, radius))
+    out = torch.empty([P], dtype=torch.uint8, device=probes.device)
+    if P == 0:
+        return out.bool()
+    lib = _lib.load()
+    ws = _workspace(lib, P, C, 0, True, probes.device)
+    _lib.check(lib.sbg_knn_in_manifold(probes.data_ptr(), manifold.data_ptr(), radius.data_ptr(), P, C, F, out.data_ptr(), ws.data_ptr(),
+                                       _lib.stream_ptr(probes.device)), "sbg_knn_in_manifold")
+    return out.bool()

@@ -422,6 +422,34 @@ class SyntheticDataset:
         return img, c
 
 
+def training_set_kwargs_from_config(config, seed, path=None, mirror=None, use_labels=None):
+    """the data set constructor's kwargs a run on `config` trains with (reference train.py:230-261: probe the data once, then be explicit
+    about resolution / labels / size).  The trainer passes nothing but the seed; calc_metrics, whose snapshots hold no such record,
+    overrides the path (--data), the flips (--mirror) and lets the labels follow the network."""
+    from .datasets import datasets
+    kw = {k: v for k, v in dict(config.get("datasets_args", {}).get(config.data.dataset, {})).items() if k not in ("args", "kwargs") and v != utils.MISSING}
+    kw["path"] = config.data.dataset_path if path is None else path
+    if use_labels:
+        kw["use_labels"] = True         # a conditional network: probe the data set with its labels
+    probe = datasets[config.data.dataset](**kw)
+    kw.update(resolution=probe.resolution, use_labels=probe.has_labels, max_size=len(probe))
+    cond = config.data.cond if use_labels is None else use_labels
+    if cond and not kw["use_labels"]:
+        raise ValueError("data.cond=true requires labels specified in dataset.json" if use_labels is None else
+                         "the network is conditional: the data set needs labels specified in dataset.json")
+    if not cond:
+        kw["use_labels"] = False
+    if config.data.subset:
+        if not 1 <= config.data.subset <= kw["max_size"]:
+            raise ValueError(f"data.subset must be between 1 and {kw['max_size']}")
+        if config.data.subset < kw["max_size"]:
+            kw.update(max_size=int(config.data.subset), random_seed=seed)
+    if config.data.mirror if mirror is None else mirror:
+        kw["xflip"] = True
+    probe.close()
+    return kw
+
+
 @trainers.add_to_registry("base")
 class BaseTrainer:
     """One data-parallel G / D pair (reference BaseTrainer :155-876, hot path only)."""
@@ -468,22 +496,7 @@ class BaseTrainer:
         self.num_gpus, self.batch_size, self.batch_gpu = gpus, gen.batch, batch_gpu
         if self.real_data:      # reference :230-261: probe the data once, then be explicit about resolution / labels / size
             from .datasets import datasets
-            kw = {k: v for k, v in dict(config.get("datasets_args", {}).get(config.data.dataset, {})).items() if k not in ("args", "kwargs") and v != utils.MISSING}
-            kw["path"] = config.data.dataset_path
-            probe = datasets[config.data.dataset](**kw)
-            kw.update(resolution=probe.resolution, use_labels=probe.has_labels, max_size=len(probe))
-            if config.data.cond and not kw["use_labels"]:
-                raise ValueError("data.cond=true requires labels specified in dataset.json")
-            if not config.data.cond:
-                kw["use_labels"] = False
-            if config.data.subset:
-                if not 1 <= config.data.subset <= kw["max_size"]:
-                    raise ValueError(f"data.subset must be between 1 and {kw['max_size']}")
-                if config.data.subset < kw["max_size"]:
-                    kw.update(max_size=int(config.data.subset), random_seed=gen.seed)
-            if config.data.mirror:
-                kw["xflip"] = True
-            probe.close()
+            kw = training_set_kwargs_from_config(config, seed=gen.seed)
             self.training_set_kwargs = kw
             self.data_loader_kwargs = {k: v for k, v in dict(config.get("dataloaders_args", {}).get(config.data.dataloader, {})).items()
                                        if k not in ("args", "kwargs") and v != utils.MISSING}
