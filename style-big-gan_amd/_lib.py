@@ -242,6 +242,19 @@ def require_cuda(t, what):
             "(device type 'cuda'); there is no CPU path in the product (the CPU restatement lives in oracle/ and is test-only).")
 
 
+def require_dtype(t, dtype, what):
+    if t.dtype != dtype:
+        raise RuntimeError(f"{what}: expects {str(dtype).replace('torch.', '')}, got {t.dtype}")
+    return t
+
+
+def workspace(nbytes, device, what):
+    """the fp32 scratch tensor (never empty) behind a `*_workspace` size query `what`; a negative size is the library's refusal"""
+    if nbytes < 0:
+        check(1, what)
+    return torch.empty([max((nbytes + 3) // 4, 1)], dtype=torch.float32, device=device)
+
+
 def prof_enable(on):
     """switch the library's per-launch hipEvent timing on / off (measurement only)"""
     return load().sbg_prof_enable(int(bool(on)))

@@ -19,6 +19,7 @@
 // a multiset and an OR do not depend on the order, and there are no atomics: two runs give the same bits.
 // Launch-log key: kind SBG_K_PR, dims = {variant (0 single, 1 split, 2 merge, 3 norms), R, C, F, k, runs, 0 radius / 1 membership}.
 #include "conv_common.h"
+#include "reduce.h"
 
 using namespace sbgconv;
 
@@ -44,13 +45,6 @@ struct KnnArgs {
     void* out; void* part;
     int R, C, F, k, runs, ctiles, tiles_per_run;
 };
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 // n[r] = sum_f x[r, f]^2: one wave per row, 16-B loads, a lane-strided fp32 sum and a butterfly.
 __global__ __launch_bounds__(256) void knn_norms_kernel(const unsigned short* __restrict__ x, float* __restrict__ n, int rows, int F)

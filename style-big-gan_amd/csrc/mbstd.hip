@@ -5,19 +5,9 @@
 //   y: fp32 [N, C + F, H, W]: y[:, :C] = x;  y[g*M + m, C + f, :, :] = stat[m, f] = mean_{cc,h,w} sqrt(var_g(x[g*M + m, f*c + cc, h, w]) + 1e-8)
 // Backward (first order): dx = dy[:, :C] + dstat[m, f] * (x - mean_g) / (G * c*H*W * sqrt(var + 1e-8)),  dstat[m, f] = sum_{g,h,w} dy[g*M+m, C+f, h, w].
 #include "sbg_common.h"
+#include "reduce.h"
 
 namespace {
-
-__device__ __forceinline__ float block_sum256(float v, float* red)
-{
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    __syncthreads();
-    if ((tid & 63) == 0) red[tid >> 6] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
 
 // Forward, pass 1: workgroup (m, f, chunk) handles 256 consecutive positions of the group's c * H * W (one per lane): mean / variance over the
 // G samples, copy of x into y, partial sum of sqrt(var + 1e-8) -> part[(f * M + m) * nchunk + chunk].  (A first version ran ONE workgroup per
@@ -44,7 +34,7 @@ __global__ __launch_bounds__(256) void mbstd_fwd_kernel(const float* x, float* y
         }
         s = sqrtf(var / (float)G + 1e-8f);
     }
-    const float tot = block_sum256(s, red);
+    const float tot = block_sum<256>(s, red);
     if (threadIdx.x == 0) part[(int64_t)mf * nchunk + chunk] = tot;
 }
 
@@ -56,7 +46,7 @@ __global__ __launch_bounds__(256) void mbstd_stat_kernel(const float* part, floa
     const int C = F * c, CO = C + F;
     float s = 0.f;
     for (int k = threadIdx.x; k < nchunk; k += 256) s += part[(int64_t)blockIdx.x * nchunk + k];
-    const float stat = block_sum256(s, red) / (float)(c * HW);
+    const float stat = block_sum<256>(s, red) / (float)(c * HW);
     for (int i = threadIdx.x; i < G * HW; i += 256) {
         const int g = i / HW, p = i - g * HW;
         y[(int64_t)(g * M + m) * CO * HW + (int64_t)(C + f) * HW + p] = stat;
@@ -76,7 +66,7 @@ __global__ __launch_bounds__(256) void mbstd_bwd_kernel(const float* x, const fl
         const int g = i / HW, p = i - g * HW;
         part += dy[(int64_t)(g * M + m) * CO * HW + (int64_t)(C + f) * HW + p];
     }
-    const float dstat = block_sum256(part, red) / ((float)npos * (float)G);
+    const float dstat = block_sum<256>(part, red) / ((float)npos * (float)G);
     const int pos = chunk * 256 + threadIdx.x;
     if (pos >= npos) return;
     const int64_t xo = (int64_t)(f * c) * HW + pos;

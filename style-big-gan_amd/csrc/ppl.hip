@@ -4,20 +4,15 @@
 // square, sum, divide); the registered metrics run 25 000 batch-of-2 iterations of it, so the chains are launch latency.  Here:
 //   endpoints:  one launch writes the [2B, ...] synthesis batch (rows 0..B-1 at t, rows B..2B-1 at t + eps), z space (slerp) or w space (lerp)
 //   prep:       one pass from the synthesis output (any strides) to the detector input [2B, 3 | C, S, S] fp32 dense
-//   dist:       [2B, F] -> [B] = sum_f (x[b, f] - x[B + b, f])^2 / eps^2, two launches with a fixed-order second stage (no float atomics)
+//   dist:       [2B, F] -> [B] = sum_f (x[b, f] - x[B + b, f])^2 / eps^2: the shared two-launch kernel pair of sqdist.h on rows b and B + b
 // Launch-log key: kind SBG_K_PPL, dims[0] = variant (0 slerp, 1 lerp, 2 prep, 3 dist), then the shape.
 #include "sbg_common.h"
+#include "reduce.h"
+#include "sqdist.h"
 
 namespace {
 
 constexpr int kPplSlerp = 0, kPplLerp = 1, kPplPrep = 2, kPplDist = 3;
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 // One wave per output row r = side * B + b: the reference's slerp(z0[b], z1[b], t_side) with t_0 = t[b], t_1 = t[b] + eps (fp32 add, like
 // `t.unsqueeze(1) + self.epsilon`).  Every norm and dot product is a lane-strided sum followed by a butterfly over the wave.
@@ -115,61 +110,6 @@ __global__ __launch_bounds__(256) void ppl_prep_kernel(const float* __restrict__
     }
 }
 
-constexpr int kDistThreads = 256;
-constexpr int kDistChunk = kDistThreads * 4 * 8;      // elements of one row per workgroup: 8 float4 per work-item
-
-__device__ __forceinline__ float block_sum(float v, float* red)
-{
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
-// Stage 1: workgroup (chunk, b) sums (x[b, f] - x[B + b, f])^2 over f in [chunk * kDistChunk, (chunk + 1) * kDistChunk) -> part[b, chunk].
-// Every work-item's share, the wave butterfly and the four-wave sum have a fixed order, so the partial is the same on every run.
-__global__ __launch_bounds__(kDistThreads) void ppl_dist_partial_kernel(const float* __restrict__ x, float* __restrict__ part, int B, int64_t F,
-                                                                        int nchunk, int vec4)
-{
-    __shared__ float red[4];
-    const int chunk = blockIdx.x, b = blockIdx.y;
-    const float* pa = x + (int64_t)b * F;
-    const float* pb = x + (int64_t)(B + b) * F;
-    const int64_t f0 = (int64_t)chunk * kDistChunk;
-    float s = 0.f;
-    if (vec4) {         // F % 4 == 0 and 16-byte aligned rows: a float4 is wholly inside or wholly outside the row
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const int64_t f = f0 + 4 * ((int64_t)k * kDistThreads + threadIdx.x);
-            if (f < F) {
-                const float4_t a = *reinterpret_cast<const float4_t*>(pa + f), c = *reinterpret_cast<const float4_t*>(pb + f);
-#pragma unroll
-                for (int q = 0; q < 4; q++) { const float d = a[q] - c[q]; s += d * d; }
-            }
-        }
-    } else {
-        for (int k = 0; k < 32; k++) {
-            const int64_t f = f0 + (int64_t)k * kDistThreads + threadIdx.x;
-            if (f < F) { const float d = pa[f] - pb[f]; s += d * d; }
-        }
-    }
-    const float tot = block_sum(s, red);
-    if (threadIdx.x == 0) part[(int64_t)b * nchunk + chunk] = tot;
-}
-
-// Stage 2: one workgroup per b adds the nchunk partials in a fixed order and divides once by eps^2.
-__global__ __launch_bounds__(kDistThreads) void ppl_dist_final_kernel(const float* __restrict__ part, float* __restrict__ dist, int nchunk, float eps2)
-{
-    __shared__ float red[4];
-    const int b = blockIdx.x;
-    float s = 0.f;
-    for (int k = threadIdx.x; k < nchunk; k += kDistThreads) s += part[(int64_t)b * nchunk + k];
-    const float tot = block_sum(s, red);
-    if (threadIdx.x == 0) dist[b] = tot / eps2;
-}
-
-int64_t dist_chunks(int64_t F) { return (F + kDistChunk - 1) / kDistChunk; }
-
 } // namespace
 
 extern "C" int sbg_ppl_slerp_endpoints(const float* z0, const float* z1, const float* t, float eps, float* out, int B, int D, sbg_stream_t stream)
@@ -231,8 +171,9 @@ extern "C" int sbg_ppl_dist(const float* feats, float* dist, void* workspace, in
     hipStream_t s = (hipStream_t)stream;
     const int vec4 = (F % 4 == 0) && sbg_aligned16(feats);
     SbgProfScope prof(s, SBG_K_PPL, 3.0 * B * (double)F, 4.0 * (2.0 * B * (double)F + 2.0 * B * nchunk + B), {kPplDist, B, (int)(F >> 10), (int)(F & 1023), vec4});
-    SBG_LAUNCH(ppl_dist_partial_kernel, dim3((unsigned)nchunk, (unsigned)B), dim3(kDistThreads), 0, s, feats, (float*)workspace, B, F, (int)nchunk, vec4);
-    SBG_LAUNCH(ppl_dist_final_kernel, dim3((unsigned)B), dim3(kDistThreads), 0, s, (const float*)workspace, dist, (int)nchunk, eps2);
+    SBG_LAUNCH(sqdist_partial_kernel<true>, dim3((unsigned)nchunk, (unsigned)B), dim3(kDistThreads), 0, s, feats, feats + (int64_t)B * F, (float*)workspace,
+               F, (int)nchunk, vec4);
+    SBG_LAUNCH(sqdist_final_kernel, dim3((unsigned)B), dim3(kDistThreads), 0, s, (const float*)workspace, dist, (int)nchunk, eps2);
     SBG_HIP_LAUNCH_CHECK();
     return SBG_OK;
 }

@@ -10,6 +10,8 @@
 // Launch-log key: kind SBG_K_PROJECTOR, one record per launch, dims[0] = variant (0 reg, 1 reg_bwd, 2 normalize, 3 sqdist,
 // 4 sqdist_bwd), dims[1] = stage within the variant, then the shape.
 #include "sbg_common.h"
+#include "reduce.h"
+#include "sqdist.h"
 
 namespace {
 
@@ -20,7 +22,6 @@ constexpr int kPoolTile = 128;          // level-0 side of one pooling workgroup
 constexpr int kProdElems = 4096;        // elements of one level per products workgroup
 constexpr int kNormChunk = kThreads * 4 * 4;    // elements per first-stage normalisation workgroup: 4 float4 per work-item
 constexpr int kNormThreads = 1024;
-constexpr int kDistChunk = kThreads * 4 * 8;    // elements per first-stage distance workgroup: 8 float4 per work-item
 
 // The buffer set, passed by value as a kernel argument.  Buffer b is [R_b, R_b], R_b = 1 << log2r[b].
 struct BufTable {
@@ -58,25 +59,6 @@ __device__ __forceinline__ int find_buffer(const BufTable& T, int block)
 __device__ __forceinline__ const float* level_ptr(const BufTable& T, const float* pyr, int b, int k)
 {
     return k == 0 ? T.buf[b] : pyr + T.pyr_off[b] + level_offset(T.log2r[b], k);
-}
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-// fixed-order sum over the workgroup: butterfly in each wave, then the waves in order.  `red` holds blockDim / 64 floats.
-__device__ __forceinline__ float block_sum(float v, float* red)
-{
-    v = wave_sum(v);
-    __syncthreads();                    // `red` may still be read by a previous call
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float s = red[0];
-    for (int w = 1; w < (int)(blockDim.x >> 6); w++) s += red[w];
-    return s;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- regulariser forward
@@ -150,8 +132,8 @@ __global__ __launch_bounds__(kThreads) void proj_products_kernel(BufTable T, con
         sx += px0; sx += px1; sx += px2; sx += px3;
         sy += py0; sy += py1; sy += py2; sy += py3;
     }
-    const float tx = block_sum(sx, red);
-    const float ty = block_sum(sy, red);
+    const float tx = block_sum<kThreads>(sx, red);
+    const float ty = block_sum<kThreads>(sy, red);
     if (threadIdx.x == 0) {
         float2 o; o.x = tx; o.y = ty;
         reinterpret_cast<float2*>(part)[pidx + c] = o;
@@ -250,7 +232,7 @@ __global__ __launch_bounds__(kThreads) void proj_norm_partial_kernel(BufTable T,
             s += v[0]; s += v[1]; s += v[2]; s += v[3];
         }
     }
-    const float tot = block_sum(s, red);
+    const float tot = block_sum<kThreads>(s, red);
     if (threadIdx.x == 0) part[T.part_off[b] + c] = tot;
 }
 
@@ -280,7 +262,7 @@ __global__ __launch_bounds__(kNormThreads) void proj_norm_apply_kernel(BufTable 
 #pragma unroll
         for (int q = 0; q < 4; q++) { const float c = v[q] - mean; const float c2 = c * c; ss += c2; }
     }
-    const float scale = rsqrtf(block_sum(ss, red) / area);
+    const float scale = rsqrtf(block_sum<kNormThreads>(ss, red) / area);
     for (int64_t e = 4 * (int64_t)threadIdx.x; e < total; e += 4 * kNormThreads) {
         const float4_t v = *reinterpret_cast<const float4_t*>(p + e);
         float4_t o;
@@ -291,42 +273,7 @@ __global__ __launch_bounds__(kNormThreads) void proj_norm_apply_kernel(BufTable 
 }
 
 // ---------------------------------------------------------------------------------------------------------------- LPIPS distance
-// Stage 1: workgroup `chunk` sums (t[f] - s[f])^2 over its kDistChunk features; stage 2: one workgroup adds the partials in order.
-__global__ __launch_bounds__(kThreads) void proj_sqdist_partial_kernel(const float* __restrict__ t, const float* __restrict__ s,
-                                                                       float* __restrict__ part, int64_t F, int vec4)
-{
-#pragma clang fp contract(off)
-    __shared__ float red[kThreads / 64];
-    const int64_t f0 = (int64_t)blockIdx.x * kDistChunk;
-    float acc = 0.f;
-    if (vec4) {         // F % 4 == 0 and 16-byte aligned: a float4 is wholly inside or wholly outside the row
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const int64_t f = f0 + 4 * ((int64_t)k * kThreads + threadIdx.x);
-            if (f < F) {
-                const float4_t a = *reinterpret_cast<const float4_t*>(t + f), c = *reinterpret_cast<const float4_t*>(s + f);
-#pragma unroll
-                for (int q = 0; q < 4; q++) { const float d = a[q] - c[q]; const float d2 = d * d; acc += d2; }
-            }
-        }
-    } else {
-        for (int k = 0; k < 32; k++) {
-            const int64_t f = f0 + (int64_t)k * kThreads + threadIdx.x;
-            if (f < F) { const float d = t[f] - s[f]; const float d2 = d * d; acc += d2; }
-        }
-    }
-    const float tot = block_sum(acc, red);
-    if (threadIdx.x == 0) part[blockIdx.x] = tot;
-}
-
-__global__ __launch_bounds__(kThreads) void proj_sqdist_final_kernel(const float* __restrict__ part, float* __restrict__ dist, int nchunk)
-{
-    __shared__ float red[kThreads / 64];
-    float acc = 0.f;
-    for (int k = threadIdx.x; k < nchunk; k += kThreads) acc += part[k];
-    const float tot = block_sum(acc, red);
-    if (threadIdx.x == 0) dist[0] = tot;
-}
+// The forward value is the shared kernel pair of sqdist.h on one row.
 
 // ds[f] = (2 (s[f] - t[f])) * g: the value autograd gives the reference's (t - s).square().sum() for s (pow backward, then the negation)
 __global__ __launch_bounds__(kThreads) void proj_sqdist_bwd_kernel(const float* __restrict__ t, const float* __restrict__ s,
@@ -400,7 +347,6 @@ RegLayout reg_layout(const BufTable& T)
 int64_t pyr_bytes_aligned(const RegLayout& l) { return (l.pyr_floats * 4 + 255) / 256 * 256; }
 
 int64_t norm_chunks(int lr) { return (((int64_t)1 << (2 * lr)) + kNormChunk - 1) / kNormChunk; }
-int64_t dist_chunks(int64_t F) { return (F + kDistChunk - 1) / kDistChunk; }
 
 } // namespace
 
@@ -540,11 +486,11 @@ extern "C" int sbg_proj_sqdist(const float* t, const float* s_, float* dist, voi
     const int vec4 = (F % 4 == 0) && sbg_aligned16(t) && sbg_aligned16(s_);
     {
         SbgProfScope prof(s, SBG_K_PROJECTOR, 3.0 * F, 8.0 * F + 4.0 * nchunk, {kProjSqdist, 0, (int)(F >> 10), (int)(F & 1023), vec4});
-        SBG_LAUNCH(proj_sqdist_partial_kernel, dim3((unsigned)nchunk), dim3(kThreads), 0, s, t, s_, (float*)workspace, F, vec4);
+        SBG_LAUNCH(sqdist_partial_kernel<false>, dim3((unsigned)nchunk, 1), dim3(kDistThreads), 0, s, t, s_, (float*)workspace, F, (int)nchunk, vec4);
     }
     {
         SbgProfScope prof(s, SBG_K_PROJECTOR, 1.0 * nchunk, 4.0 * nchunk + 4.0, {kProjSqdist, 1, (int)(F >> 10), (int)(F & 1023), vec4});
-        SBG_LAUNCH(proj_sqdist_final_kernel, dim3(1), dim3(kThreads), 0, s, (const float*)workspace, dist, (int)nchunk);
+        SBG_LAUNCH(sqdist_final_kernel, dim3(1), dim3(kDistThreads), 0, s, (const float*)workspace, dist, (int)nchunk, 1.0f);
     }
     SBG_HIP_LAUNCH_CHECK();
     return SBG_OK;

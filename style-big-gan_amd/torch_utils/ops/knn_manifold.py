@@ -30,12 +30,6 @@ def _check(rows, manifold, k):
         raise RuntimeError(f"knn_manifold: the manifold has {manifold.shape[0]} points, the (k + 1)-th neighbour needs {k + 1}")
 
 
-def _f16(x, what):
-    if x.dtype != torch.float16:
-        raise RuntimeError(f"{what}: device tensors must be float16, got {x.dtype}")
-    return x.contiguous()
-
-
 def _cpu_distances(rows, manifold, n_manifold):
     """[r, C] fp16 distances of a block of rows by the definition above"""
     x = rows.to(torch.float64)
@@ -49,7 +43,7 @@ def _workspace(lib, R, C, k, membership, device):
     nbytes = lib.sbg_knn_workspace(R, C, k, int(membership))
     if nbytes < 0:
         raise RuntimeError(f"knn_manifold: unsupported sizes R={R} C={C} k={k}")
-    return torch.empty([(nbytes + 3) // 4], dtype=torch.float32, device=device)
+    return _lib.workspace(nbytes, device, "sbg_knn_workspace")
 
 
 def kth_radius(rows, manifold, k):
@@ -62,7 +56,7 @@ def kth_radius(rows, manifold, k):
         n_manifold = manifold.to(torch.float64).square().sum(1).to(torch.float32)
         out = [_cpu_distances(b, manifold, n_manifold).to(torch.float32).kthvalue(k + 1).values.to(torch.float16) for b in rows.split(_CPU_ROWS)]
         return torch.cat(out) if out else torch.empty([0], dtype=torch.float16)
-    rows, manifold = _f16(rows, "knn_manifold.kth_radius"), _f16(manifold, "knn_manifold.kth_radius")
+    rows, manifold = (_lib.require_dtype(t, torch.float16, "knn_manifold.kth_radius").contiguous() for t in (rows, manifold))
     out = torch.empty([R], dtype=torch.float16, device=rows.device)
     if R == 0:
         return out
@@ -85,7 +79,7 @@ def in_manifold(probes, manifold, radius):
         r = radius.to(torch.float16)
         out = [(_cpu_distances(b, manifold, n_manifold) <= r).any(dim=1) for b in probes.split(_CPU_ROWS)]
         return torch.cat(out) if out else torch.empty([0], dtype=torch.bool)
-    probes, manifold, radius = (_f16(t, "knn_manifold.in_manifold") for t in (probes, manifold, radius))
+    probes, manifold, radius = (_lib.require_dtype(t, torch.float16, "knn_manifold.in_manifold").contiguous() for t in (probes, manifold, radius))
     out = torch.empty([P], dtype=torch.uint8, device=probes.device)
     if P == 0:
         return out.bool()

@@ -22,12 +22,6 @@ def slerp(a, b, t):
     return d
 
 
-def _f32(x, what):
-    if x.dtype != torch.float32:
-        raise RuntimeError(f"{what}: expects float32, got {x.dtype}")
-    return x.contiguous()
-
-
 def slerp_endpoints(z0, z1, t, epsilon):
     """z0, z1 [B, D], t [B] -> [2B, D]: cat[slerp(z0, z1, t), slerp(z0, z1, t + epsilon)] (:64-65)"""
     B, D = z0.shape
@@ -35,7 +29,7 @@ def slerp_endpoints(z0, z1, t, epsilon):
     if z0.device.type != "cuda":
         t = t.unsqueeze(1)
         return torch.cat([slerp(z0, z1, t), slerp(z0, z1, t + epsilon)])
-    z0, z1, t = _f32(z0, "ppl slerp"), _f32(z1, "ppl slerp"), _f32(t, "ppl slerp")
+    z0, z1, t = (_lib.require_dtype(x, torch.float32, "ppl slerp").contiguous() for x in (z0, z1, t))
     out = torch.empty([2 * B, D], dtype=torch.float32, device=z0.device)
     _lib.check(_lib.load().sbg_ppl_slerp_endpoints(z0.data_ptr(), z1.data_ptr(), t.data_ptr(), float(epsilon), out.data_ptr(), B, D,
                                                    _lib.stream_ptr(z0.device)), "sbg_ppl_slerp_endpoints")
@@ -49,7 +43,7 @@ def lerp_endpoints(w0, w1, t, epsilon):
     if w0.device.type != "cuda":
         tb = t.reshape([B] + [1] * (w0.ndim - 1))
         return torch.cat([w0.lerp(w1, tb), w0.lerp(w1, tb + epsilon)])
-    w0, w1, t = _f32(w0, "ppl lerp"), _f32(w1, "ppl lerp"), _f32(t, "ppl lerp")
+    w0, w1, t = (_lib.require_dtype(x, torch.float32, "ppl lerp").contiguous() for x in (w0, w1, t))
     out = torch.empty([2 * B] + list(w0.shape[1:]), dtype=torch.float32, device=w0.device)
     _lib.check(_lib.load().sbg_ppl_lerp_endpoints(w0.data_ptr(), w1.data_ptr(), t.data_ptr(), float(epsilon), out.data_ptr(), B, w0[0].numel(),
                                                   _lib.stream_ptr(w0.device)), "sbg_ppl_lerp_endpoints")
@@ -90,10 +84,10 @@ def lpips_distance(feats, epsilon):
     if feats.device.type != "cuda":
         f0, f1 = feats.chunk(2)
         return (f0 - f1).square().sum(1) / epsilon ** 2
-    feats = _f32(feats, "ppl distance")
+    feats = _lib.require_dtype(feats, torch.float32, "ppl distance").contiguous()
     B, F = feats.shape[0] // 2, feats.shape[1]
     lib = _lib.load()
-    ws = torch.empty([lib.sbg_ppl_dist_workspace(B, F) // 4], dtype=torch.float32, device=feats.device)
+    ws = _lib.workspace(lib.sbg_ppl_dist_workspace(B, F), feats.device, "sbg_ppl_dist_workspace")
     dist = torch.empty([B], dtype=torch.float32, device=feats.device)
     eps2 = float(torch.tensor(epsilon ** 2, dtype=torch.float32))
     _lib.check(lib.sbg_ppl_dist(feats.data_ptr(), dist.data_ptr(), ws.data_ptr(), B, F, eps2, _lib.stream_ptr(feats.device)), "sbg_ppl_dist")

@@ -82,11 +82,8 @@ def _noise_reg_device(bufs):
     """-> (means [2M], reg [], workspace holding the pyramid)"""
     lib = _lib.load()
     ptrs, res, n = _noise_table(bufs, "proj noise reg")
-    wsb = lib.sbg_proj_noise_reg_workspace(res, n)
-    if wsb < 0:
-        _lib.check(1, "sbg_proj_noise_reg_workspace")
     dev = bufs[0].device
-    ws = torch.empty([max(wsb // 4, 1)], dtype=torch.float32, device=dev)
+    ws = _lib.workspace(lib.sbg_proj_noise_reg_workspace(res, n), dev, "sbg_proj_noise_reg_workspace")
     means = torch.empty([2 * sum(num_levels(int(b.shape[0])) for b in bufs)], dtype=torch.float32, device=dev)
     reg = torch.empty([], dtype=torch.float32, device=dev)
     _lib.check(lib.sbg_proj_noise_reg(ptrs, res, n, means.data_ptr(), reg.data_ptr(), ws.data_ptr(), _lib.stream_ptr(dev)), "sbg_proj_noise_reg")
@@ -147,27 +144,18 @@ def noise_normalize_(bufs):
             return
         lib = _lib.load()
         ptrs, res, n = _noise_table([b.detach() for b in bufs], "proj noise normalize")
-        wsb = lib.sbg_proj_noise_normalize_workspace(res, n)
-        if wsb < 0:
-            _lib.check(1, "sbg_proj_noise_normalize_workspace")
         dev = bufs[0].device
-        ws = torch.empty([max(wsb // 4, 1)], dtype=torch.float32, device=dev)
+        ws = _lib.workspace(lib.sbg_proj_noise_normalize_workspace(res, n), dev, "sbg_proj_noise_normalize_workspace")
         _lib.check(lib.sbg_proj_noise_normalize(ptrs, res, n, ws.data_ptr(), _lib.stream_ptr(dev)), "sbg_proj_noise_normalize")
-
-
-def _flat_f32(x, what):
-    if x.dtype != torch.float32:
-        raise RuntimeError(f"{what}: expects float32, got {x.dtype}")
-    return x.contiguous().reshape(-1)
 
 
 class _SqDist(torch.autograd.Function):
     @staticmethod
     def forward(ctx, t, s):
-        tf, sf = _flat_f32(t.detach(), "proj sqdist"), _flat_f32(s.detach(), "proj sqdist")
+        tf, sf = (_lib.require_dtype(x.detach(), torch.float32, "proj sqdist").contiguous().reshape(-1) for x in (t, s))
         lib = _lib.load()
         Fn = tf.numel()
-        ws = torch.empty([lib.sbg_proj_sqdist_workspace(Fn) // 4], dtype=torch.float32, device=tf.device)
+        ws = _lib.workspace(lib.sbg_proj_sqdist_workspace(Fn), tf.device, "sbg_proj_sqdist_workspace")
         dist = torch.empty([], dtype=torch.float32, device=tf.device)
         _lib.check(lib.sbg_proj_sqdist(tf.data_ptr(), sf.data_ptr(), dist.data_ptr(), ws.data_ptr(), Fn, _lib.stream_ptr(tf.device)), "sbg_proj_sqdist")
         ctx.save_for_backward(tf, sf)

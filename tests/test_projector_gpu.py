@@ -163,6 +163,23 @@ def test_noise_normalize_bound(dev, name):
         assert bool((err <= bound * r.abs()).all()), float((err / r.abs().clamp_min(1e-30)).max())
 
 
+@pytest.mark.parametrize("side", [64, 128])
+def test_noise_normalize_counts_every_wave_once(dev, side):
+    """a +-1 checkerboard: the mean is exactly 0 and the sum of squares exactly R^2 in any order, so the scale is rsqrt(1).  At side 64
+    each of the 16 waves of the second stage's 1024-wide workgroup contributes exactly one float4 per lane, at 128 four.  Every element
+    must keep its sign and have one common magnitude within 1 ulp of 1 (2^-23: HIP documents rsqrtf within 1 ulp, and +-1 times the
+    scale is exact); a dropped or double-counted wave scales by sqrt(16 / 15) or sqrt(16 / 17), ~3 % off"""
+    i = torch.arange(side)
+    board = (1.0 - 2.0 * ((i[:, None] + i[None, :]) % 2)).float()
+    buf = board.to(dev)
+    proj_ops.noise_normalize_([buf])
+    out = buf.cpu()
+    mags = out.abs().unique()
+    assert mags.numel() == 1, mags
+    assert abs(float(mags[0]) - 1.0) <= 2.0 ** -23, float(mags[0])
+    assert torch.equal(out.sign(), board)
+
+
 # ---------------------------------------------------------------------------------------------------------------- LPIPS distance
 
 @pytest.mark.parametrize("F_", [1, 1000, 3 * 8192 + 5, 8 * 1024 * 1024 - 4, 8_016_000])
