@@ -282,7 +282,10 @@ int sbg_split_bf16_cat_nd(const float* x, const int64_t* shape, const int64_t* x
  *   out[n, q, :] = softmax_m( theta[n, q, :] . phi[n, m, :] ) @ g[n, m, :]
  * theta: fp32 [N, Q, D], phi: fp32 [N, M, D], g: fp32 [N, M, DV], out: fp32 [N, Q, DV], all row-major dense.
  * Exact-fp32 matrix-core kernel (v_mfma_f32_16x16x4_f32); the [Q, M] attention map never touches HBM.
- * Supported: Q % 16 == 0, M % 16 == 0, M <= 256, D % 4 == 0, DV % 16 == 0 (sbg_attention_supported). */
+ * M <= 256: the whole key strip of a wave's 16 queries is held at once (M / 16 in {1, 2, 4, 8, 16}).  M > 256: the keys are walked in chunks
+ * with a running maximum, sum and output per row (online softmax), one division at the end; any M % 16 == 0.
+ * Supported: Q % 16 == 0, M % 16 == 0, D % 4 == 0, DV % 16 == 0, and for M > 256 per-sample matrices of at most 2^31 - 1 elements
+ * (M * max(D, DV), Q * max(D, DV)) (sbg_attention_supported). */
 int sbg_attention_supported(int Q, int M, int D, int DV);
 int sbg_attention_fwd(const float* theta, const float* phi, const float* g, float* out, int N, int Q, int M, int D, int DV,
                       sbg_stream_t stream);
@@ -290,6 +293,8 @@ int sbg_attention_fwd(const float* theta, const float* phi, const float* g, floa
  *   dg = P^T dout,  dS = P o (dout g^T - rowsum(dout o out)),  dtheta = dS phi,  dphi = dS^T theta,   P = softmax(theta phi^T)
  * recomputed from theta / phi / g in two passes (per query tile, per key tile); the [Q, M] map never touches HBM and every sum over
  * queries stays inside one wave (fixed order).  workspace: sbg_attention_bwd_workspace(N, Q) bytes of row statistics.
+ * M > 256 takes three launches: the forward recomputed in registers for lse and delta = rowsum(dout o out) (nothing of the forward is saved),
+ * dtheta streamed over the key chunks from those statistics, then the same per-key-tile pass as M <= 256.
  * Supported: the forward's shapes with D <= 64 and DV / 16 in {1, 2, 4, 8, 16} (sbg_attention_bwd_supported). */
 int sbg_attention_bwd_supported(int Q, int M, int D, int DV);
 int64_t sbg_attention_bwd_workspace(int N, int Q);
@@ -535,7 +540,9 @@ enum sbg_kernel_kind {
  *                (dims[3] = layout, 3 dot_hw_scale, 2 modconv_bwd, 4 modconv_bwd_prescaled, 5 moments_hw: dims[4] = 1 vec8 / 2 scalar)
  *   weight_prep  pack (dims[3] = 0): dims[4] = 1 transposing LDS tiles / 2 one lane per (row, column)
  *   torgb        forward (dims[4] = 0): dims[5] = 1 matrix cores / 2 streaming, 3 outputs / 3 streaming, 4 outputs
- *   fromrgb      backward (dims[4] = 1): dims[5] = image channels unrolled (3, or 4 for any), dims[6] = 1 with the image gradient */
+ *   fromrgb      backward (dims[4] = 1): dims[5] = image channels unrolled (3, or 4 for any), dims[6] = 1 with the image gradient
+ *   attention    (N, Q, M, D, DV), dims[5] = 0 forward / 1 backward, dims[6] = 0 single (M <= 256; the backward is one record for both
+ *                passes) / 1 stream (forward) / 2 stream_stats / 3 stream_dq / 4 stream_dkv (the three launches of the streamed backward) */
 typedef struct sbg_prof_record {
     int    kind;            /* enum sbg_kernel_kind */
     int    dims[7];         /* kernel specific shape key (see each kernel's source) */

@@ -112,6 +112,7 @@ IMG_VARIANTS = {0: "quantize_tile", 1: "truncate_mix"}      # dims[0] of an "ima
 QUANT_RULES = {"grid": 0, "clamp": 1}                       # enum sbg_quant_rule
 RESAMPLE_VARIANTS = {0: "h", 1: "v"}                        # dims[0] of a "resample" launch record
 PR_VARIANTS = {0: "single", 1: "split", 2: "merge", 3: "norms"}    # dims[0] of a "pr" launch record (dims[6]: 0 radius, 1 membership)
+ATT_VARIANTS = {0: "single", 1: "stream", 2: "stream_stats", 3: "stream_dq", 4: "stream_dkv"}     # dims[6] of an "attention" launch record (dims[5]: 0 forward, 1 backward)
 
 _lib = None
 _lock = threading.Lock()

@@ -9,13 +9,17 @@ Mirror of the reference's ``biggan/layers.py`` API used by the registered models
   d sigma / d W = outer(u', v) is an autograd Function, the weight is divided by sigma as in the reference (:99);
 * convolutions are the implicit-GEMM MFMA kernels (``conv2d_gradfix``), ReLU is ``bias_act``, nearest up-sampling and 2x2
   average pooling are ``upfirdn2d`` with 2x2 box filters;
-* attention: ``softmax(theta^T phi) g`` is one exact-fp32 matrix-core kernel (``sbg_attention_fwd``) -- the [HW, HW/4] map
-  never reaches HBM; its backward re-derives the map with library batched GEMMs (differentiable again, so R1 works);
+* attention: ``softmax(theta^T phi) g`` is one exact-fp32 matrix-core kernel (``sbg_attention_fwd``) at any resolution -- the
+  [HW, HW/4] map never reaches HBM (above 32x32 the keys are streamed in chunks, online softmax) and is never saved; first-order
+  backward recomputes it in the ``sbg_attention_bwd`` kernels, a gradient that is differentiated again (R1) is composed from
+  library batched GEMMs;
 * batch norm: statistics by the ``sbg_dot_hw`` reductions (sum, sum of squares), normalise + class-conditional gain/bias in
   one ``sbg_scale_shift_nc`` pass; ``cross_replica=True`` all-reduces [sum, sum^2, count] over RCCL (differentiable) and
   uses the reference's synchronized formula (sync_batchnorm/batchnorm.py:147-158) -- the reference's DataParallel-only
   mechanism is not reproduced.
 """
+import warnings
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -183,6 +187,7 @@ class _AttentionCore(torch.autograd.Function):
                                                  _lib.ptr(grads[2]), _lib.ptr(ws), n, q, m, d, dv, _lib.stream_ptr(theta.device)), "sbg_attention_bwd")
                 grads = [gr.to(t.dtype) for gr, t in zip(grads, (theta, phi, g))]
             else:
+                _warn_composition("backward", (q, m, d, dv))
                 with torch.enable_grad():
                     ins = [t.detach().requires_grad_(True) for t in (theta, phi, g)]
                     out = _attention_reference(*ins)
@@ -190,11 +195,25 @@ class _AttentionCore(torch.autograd.Function):
         return tuple(gr if need else None for gr, need in zip(grads, ctx.needs_input_grad))
 
 
+_composition_warned = set()
+
+
+def _warn_composition(direction, shape):
+    """once per (direction, shape): a CUDA attention that leaves the library for the torch composition stores the [N, Q, M] map"""
+    if (direction, shape) not in _composition_warned:
+        _composition_warned.add((direction, shape))
+        warnings.warn("attention_core %s: Q=%d M=%d D=%d DV=%d is outside the HIP kernels' shape contract (include/sbg_hip.h); running the torch "
+                      "bmm / softmax / bmm composition, which materialises the [N, Q, M] map" % ((direction,) + tuple(shape)))
+
+
 def attention_core(theta, phi, g):
     """theta [N, Q, D], phi [N, M, D], g [N, M, DV] -> softmax(theta phi^T, -1) g"""
     lib = _lib.load()
-    if theta.device.type == "cuda" and lib.sbg_attention_supported(theta.shape[1], phi.shape[1], theta.shape[2], g.shape[2]):
-        return _AttentionCore.apply(theta, phi, g)
+    if theta.device.type == "cuda":
+        shape = (theta.shape[1], phi.shape[1], theta.shape[2], g.shape[2])
+        if lib.sbg_attention_supported(*shape):
+            return _AttentionCore.apply(theta, phi, g)
+        _warn_composition("forward", shape)
     return _attention_reference(theta, phi, g)
 
 

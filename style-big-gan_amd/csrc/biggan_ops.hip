@@ -6,7 +6,9 @@
 //  * attention_fwd_kernel: out = softmax(theta phi^T) g per sample (biggan/layers.py:162-166) on the fp32-input matrix cores
 //    (v_mfma_f32_16x16x4_f32: bit-for-bit an fp32 fma chain, so parity with the fp32 reference is to rounding).  One wave
 //    owns 16 query rows: S = Q K^T lives in accumulator registers, the row softmax runs on them (16-lane shuffles), P goes
-//    through a 16 x M LDS strip to become the A operand of P V.  Keys <= 256, so no online-softmax rescaling is needed.
+//    through a 16 x M LDS strip to become the A operand of P V.  Keys <= 256 take these kernels: no online-softmax rescaling.
+//  * attention_fwd_stream_kernel / attention_bwd_dq_stream_kernel: the same wave-per-16-queries structure for any number of keys,
+//    walking them in chunks with a running (max, sum, output) per row; the [Q, M] map still never reaches HBM.
 #include "sbg_common.h"
 
 namespace {
@@ -304,6 +306,221 @@ __global__ __launch_bounds__(256) void attention_bwd_dkv_kernel(const float* the
         }
 }
 
+// ---- streaming (online-softmax) form, M > ATT_MAX_M.  A wave still owns 16 query rows and walks the keys in chunks of ATT_CHUNK (the last
+// chunk holds the remainder, a multiple of 16): one chunk is the S[] / LDS-strip structure of the kernels above.  ATT_CHUNK is 128, not
+// ATT_MAX_M: with the output tiles resident next to S[] a 256-key chunk takes the whole register file (one wave per SIMD); at 128 keys
+// two to three waves fit and the strip is 33 KiB per workgroup.  Per row it carries a running
+// maximum m, a running sum l of exp(s - m) and the DV / 16 output tiles O = sum exp(s - m) v.  A chunk with maximum mc moves the state to
+//   m' = max(m, mc),  c = exp(m - m'),  l' = c l + sum_chunk exp(s - m'),  O' = c O + exp(S_chunk - m') V_chunk
+// (m starts at -FLT_MAX, so the first chunk's c is exp(-huge) = 0 on l = 0, O = 0: no infinity enters the arithmetic).  One division by l at
+// the end; lse = m + log(l).
+#ifndef ATT_CHUNK
+#define ATT_CHUNK 128                // keys of one chunk (<= ATT_MAX_M)
+#endif
+#define ATT_CT (ATT_CHUNK / 16)     // key tiles of one chunk
+#define ATT_NEG_HUGE (-3.402823466e+38f)
+
+// S[j] += Q K_chunk^T for the nt <= ATT_CT key tiles of the chunk at Kc (tiles >= nt stay untouched)
+static __device__ __forceinline__ void att_chunk_scores(float4_t (&S)[ATT_CT], const float* Qp, const float* Kc, int nt, int D, int fr, int fk)
+{
+    for (int k0 = 0; k0 < D; k0 += 4) {
+        const float a = Qp[(int64_t)fr * D + k0 + fk];
+#pragma unroll
+        for (int j = 0; j < ATT_CT; j++)
+            if (j < nt) S[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, Kc[(int64_t)(16 * j + fr) * D + k0 + fk], S[j], 0, 0, 0);
+    }
+}
+
+// STATS = false: the forward, out columns [16 * DVT * blockIdx.z, +16 * DVT).  STATS = true (backward, whole DV = 16 * DVT): the forward
+// recomputed for the row statistics only -- lse and delta = rowsum(dout o out) -- nothing else is written.
+template <int DVT, bool STATS>
+__global__ __launch_bounds__(256) void attention_fwd_stream_kernel(const float* theta, const float* phi, const float* g, const float* dout,
+                                                                   float* out, float* lse, float* delta, int Q, int M, int D, int DV)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int n = blockIdx.y;
+    const int q0 = (blockIdx.x * 4 + wave) * 16;
+    const int cb = blockIdx.z * DVT * 16;                    // first output column of this workgroup
+    const int pitch = ATT_CHUNK + 4;
+    float* P = reinterpret_cast<float*>(smem) + wave * 16 * pitch;
+    if (q0 >= Q) return;
+    const float* Qp = theta + ((int64_t)n * Q + q0) * D;
+    const float* Kp = phi + (int64_t)n * M * D;
+    const float* Vp = g + (int64_t)n * M * DV + cb;
+    const int fr = lane & 15, fk = lane >> 4;
+
+    float4_t O[DVT];
+#pragma unroll
+    for (int c = 0; c < DVT; c++) O[c] = float4_t{0.f, 0.f, 0.f, 0.f};
+    float mrun[4], lrun[4];
+#pragma unroll
+    for (int e = 0; e < 4; e++) { mrun[e] = ATT_NEG_HUGE; lrun[e] = 0.f; }
+
+    for (int mb = 0; mb < M; mb += ATT_CHUNK) {
+        const int nt = (M - mb < ATT_CHUNK ? M - mb : ATT_CHUNK) / 16;
+        float4_t S[ATT_CT];
+#pragma unroll
+        for (int j = 0; j < ATT_CT; j++) S[j] = float4_t{0.f, 0.f, 0.f, 0.f};
+        att_chunk_scores(S, Qp, Kp + (int64_t)mb * D, nt, D, fr, fk);
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            float m = S[0][e];
+#pragma unroll
+            for (int j = 1; j < ATT_CT; j++) if (j < nt) m = fmaxf(m, S[j][e]);
+#pragma unroll
+            for (int off = 1; off < 16; off <<= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+            const float mnew = fmaxf(mrun[e], m);
+            const float sc = expf(mrun[e] - mnew);
+            float s = 0.f;
+#pragma unroll
+            for (int j = 0; j < ATT_CT; j++) if (j < nt) { const float pv = expf(S[j][e] - mnew); S[j][e] = pv; s += pv; }
+#pragma unroll
+            for (int off = 1; off < 16; off <<= 1) s += __shfl_xor(s, off, 64);
+            lrun[e] = lrun[e] * sc + s;
+            mrun[e] = mnew;
+#pragma unroll
+            for (int c = 0; c < DVT; c++) O[c][e] *= sc;     // row 4 * fk + e of every output tile
+        }
+        __builtin_amdgcn_wave_barrier();                     // the previous chunk's strip reads are issued before it is overwritten
+#pragma unroll
+        for (int j = 0; j < ATT_CT; j++)
+            if (j < nt) {
+#pragma unroll
+                for (int e = 0; e < 4; e++) P[(4 * fk + e) * pitch + 16 * j + fr] = S[j][e];
+            }
+        __builtin_amdgcn_s_waitcnt(0xC07F);
+        __builtin_amdgcn_wave_barrier();
+        const float* Vc = Vp + (int64_t)mb * DV;
+        for (int m0 = 0; m0 < 16 * nt; m0 += 4) {
+            const float a = P[fr * pitch + m0 + fk];
+            const float* vr = Vc + (int64_t)(m0 + fk) * DV + fr;
+#pragma unroll
+            for (int c = 0; c < DVT; c++) O[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, vr[16 * c], O[c], 0, 0, 0);
+        }
+    }
+    if (STATS) {
+        const float* dOp = dout + ((int64_t)n * Q + q0) * DV;
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            float d = 0.f;
+#pragma unroll
+            for (int c = 0; c < DVT; c++) d += dOp[(int64_t)(4 * fk + e) * DV + 16 * c + fr] * (O[c][e] / lrun[e]);
+#pragma unroll
+            for (int off = 1; off < 16; off <<= 1) d += __shfl_xor(d, off, 64);
+            if (fr == 0) {
+                lse[(int64_t)n * Q + q0 + 4 * fk + e] = mrun[e] + logf(lrun[e]);
+                delta[(int64_t)n * Q + q0 + 4 * fk + e] = d;
+            }
+        }
+    } else {
+        float* Op = out + ((int64_t)n * Q + q0) * DV + cb;
+#pragma unroll
+        for (int c = 0; c < DVT; c++)
+#pragma unroll
+            for (int e = 0; e < 4; e++) Op[(int64_t)(4 * fk + e) * DV + 16 * c + fr] = O[c][e] / lrun[e];
+    }
+}
+
+// Pass A of the backward, streamed: lse and delta are known (attention_fwd_stream_kernel<., true>), so the key chunks are walked once:
+// P = exp(S - lse), dP = dO V^T, dS = P o (dP - delta) through the strip, dtheta += dS K_chunk in ceil(D / 16) accumulator tiles.
+template <int DT>
+__global__ __launch_bounds__(256) void attention_bwd_dq_stream_kernel(const float* theta, const float* phi, const float* g, const float* dout,
+                                                                      const float* lse, const float* delta, float* dtheta, int Q, int M, int D, int DV)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int n = blockIdx.y;
+    const int q0 = (blockIdx.x * 4 + wave) * 16;
+    const int pitch = ATT_CHUNK + 4;
+    float* P = reinterpret_cast<float*>(smem) + wave * 16 * pitch;
+    if (q0 >= Q) return;
+    const float* Qp = theta + ((int64_t)n * Q + q0) * D;
+    const float* Kp = phi + (int64_t)n * M * D;
+    const float* Vp = g + (int64_t)n * M * DV;
+    const float* dOp = dout + ((int64_t)n * Q + q0) * DV;
+    const int fr = lane & 15, fk = lane >> 4;
+    float l[4], dl[4];
+#pragma unroll
+    for (int e = 0; e < 4; e++) { l[e] = lse[(int64_t)n * Q + q0 + 4 * fk + e]; dl[e] = delta[(int64_t)n * Q + q0 + 4 * fk + e]; }
+    float4_t A[DT];
+#pragma unroll
+    for (int c = 0; c < DT; c++) A[c] = float4_t{0.f, 0.f, 0.f, 0.f};
+
+    for (int mb = 0; mb < M; mb += ATT_CHUNK) {
+        const int nt = (M - mb < ATT_CHUNK ? M - mb : ATT_CHUNK) / 16;
+        const float* Kc = Kp + (int64_t)mb * D;
+        const float* Vc = Vp + (int64_t)mb * DV;
+        float4_t S[ATT_CT], dP[ATT_CT];
+#pragma unroll
+        for (int j = 0; j < ATT_CT; j++) { S[j] = float4_t{0.f, 0.f, 0.f, 0.f}; dP[j] = float4_t{0.f, 0.f, 0.f, 0.f}; }
+        att_chunk_scores(S, Qp, Kc, nt, D, fr, fk);
+        att_chunk_scores(dP, dOp, Vc, nt, DV, fr, fk);       // dP = dO V_chunk^T: the same product with (dO, V, DV) for (Q, K, D)
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int j = 0; j < ATT_CT; j++)
+            if (j < nt) {
+#pragma unroll
+                for (int e = 0; e < 4; e++) P[(4 * fk + e) * pitch + 16 * j + fr] = expf(S[j][e] - l[e]) * (dP[j][e] - dl[e]);       // dS
+            }
+        __builtin_amdgcn_s_waitcnt(0xC07F);
+        __builtin_amdgcn_wave_barrier();
+        for (int m0 = 0; m0 < 16 * nt; m0 += 4) {
+            const float a = P[fr * pitch + m0 + fk];
+            const float* kr = Kc + (int64_t)(m0 + fk) * D;
+#pragma unroll
+            for (int c = 0; c < DT; c++) A[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, (16 * c + fr < D) ? kr[16 * c + fr] : 0.f, A[c], 0, 0, 0);
+        }
+    }
+    float* dQp = dtheta + ((int64_t)n * Q + q0) * D;
+#pragma unroll
+    for (int c = 0; c < DT; c++)
+        if (16 * c + fr < D) {
+#pragma unroll
+            for (int e = 0; e < 4; e++) dQp[(int64_t)(4 * fk + e) * D + 16 * c + fr] = A[c][e];
+        }
+}
+
+// records of kind SBG_K_ATTENTION: dims = (N, Q, M, D, DV, 0 forward / 1 backward, variant)
+enum { ATT_V_SINGLE = 0, ATT_V_STREAM = 1, ATT_V_STREAM_STATS = 2, ATT_V_STREAM_DQ = 3, ATT_V_STREAM_DKV = 4 };
+
+#define ATT_STREAM_LDS (4 * 16 * (ATT_CHUNK + 4) * (int)sizeof(float))
+
+template <int DVT, bool STATS>
+static int launch_att_stream(const float* theta, const float* phi, const float* g, const float* dout, float* out, float* lse, float* delta,
+                             int N, int Q, int M, int D, int DV, hipStream_t s)
+{
+    if (!SBG_RAISE_LDS_ONCE((attention_fwd_stream_kernel<DVT, STATS>), ATT_STREAM_LDS))
+        return sbg_fail(SBG_ERR_LAUNCH, "attention (streamed): cannot raise the dynamic LDS limit to %d bytes", ATT_STREAM_LDS);
+    SBG_LAUNCH((attention_fwd_stream_kernel<DVT, STATS>), dim3((Q + 63) / 64, N, DV / (16 * DVT)), dim3(256), ATT_STREAM_LDS, s,
+               theta, phi, g, dout, out, lse, delta, Q, M, D, DV);
+    return SBG_OK;
+}
+
+template <bool STATS>
+static int launch_att_stream_dvt(int dvt, const float* theta, const float* phi, const float* g, const float* dout, float* out, float* lse, float* delta,
+                                 int N, int Q, int M, int D, int DV, hipStream_t s)
+{
+    switch (dvt) {
+        case 1:  return launch_att_stream<1, STATS>(theta, phi, g, dout, out, lse, delta, N, Q, M, D, DV, s);
+        case 2:  return launch_att_stream<2, STATS>(theta, phi, g, dout, out, lse, delta, N, Q, M, D, DV, s);
+        case 4:  return launch_att_stream<4, STATS>(theta, phi, g, dout, out, lse, delta, N, Q, M, D, DV, s);
+        case 8:  return launch_att_stream<8, STATS>(theta, phi, g, dout, out, lse, delta, N, Q, M, D, DV, s);
+        case 16: return launch_att_stream<16, STATS>(theta, phi, g, dout, out, lse, delta, N, Q, M, D, DV, s);
+        default: return sbg_fail(SBG_ERR_UNSUPPORTED, "attention (streamed): %d output tiles per workgroup", dvt);
+    }
+}
+
+template <int DT>
+static int launch_att_bwd_dq_stream(const float* theta, const float* phi, const float* g, const float* dout, const float* lse, const float* delta,
+                                    float* dtheta, int N, int Q, int M, int D, int DV, hipStream_t s)
+{
+    if (!SBG_RAISE_LDS_ONCE(attention_bwd_dq_stream_kernel<DT>, ATT_STREAM_LDS))
+        return sbg_fail(SBG_ERR_LAUNCH, "attention_bwd (streamed): cannot raise the dynamic LDS limit to %d bytes", ATT_STREAM_LDS);
+    SBG_LAUNCH((attention_bwd_dq_stream_kernel<DT>), dim3((Q + 63) / 64, N), dim3(256), ATT_STREAM_LDS, s, theta, phi, g, dout, lse, delta, dtheta, Q, M, D, DV);
+    return SBG_OK;
+}
+
 template <int MT>
 static int launch_att(const float* theta, const float* phi, const float* g, float* out, int N, int Q, int M, int D, int DV, hipStream_t s)
 {
@@ -344,7 +561,11 @@ extern "C" int sbg_sn_power_iteration(const float* W, const float* u, float* v, 
 
 extern "C" int sbg_attention_supported(int Q, int M, int D, int DV)
 {
-    return (Q >= 16 && Q % 16 == 0 && M >= 16 && M % 16 == 0 && M <= ATT_MAX_M && D >= 4 && D % 4 == 0 && DV >= 16 && DV % 16 == 0) ? 1 : 0;
+    if (!(Q >= 16 && Q % 16 == 0 && M >= 16 && M % 16 == 0 && D >= 4 && D % 4 == 0 && DV >= 16 && DV % 16 == 0)) return 0;
+    if (M <= ATT_MAX_M) return 1;
+    // streamed form: any M whose per-sample matrices keep 32-bit element counts (sample bases are 64-bit)
+    const int64_t w = D > DV ? D : DV;
+    return ((int64_t)M * w <= INT32_MAX && (int64_t)Q * w <= INT32_MAX) ? 1 : 0;
 }
 
 template <int MT>
@@ -379,6 +600,44 @@ extern "C" int sbg_attention_bwd_supported(int Q, int M, int D, int DV)
 
 extern "C" int64_t sbg_attention_bwd_workspace(int N, int Q) { return 2 * (int64_t)N * Q * (int64_t)sizeof(float); }
 
+// Streamed backward, M > ATT_MAX_M: three launches, each with its own record.  O is not taken from the forward: the first launch recomputes
+// it in registers for lse and delta = rowsum(dout o out), so the saved state is the three inputs, as for the single-chunk kernels.
+static int attention_bwd_stream(const float* theta, const float* phi, const float* g, const float* dout, float* dtheta, float* dphi, float* dg,
+                                float* lse, float* delta, int N, int Q, int M, int D, int DV, hipStream_t s)
+{
+    const double qm = 2.0 * N * (double)Q * M, qd = (double)Q * D, qv = (double)Q * DV, mk = (double)M * (D + DV);
+    int rc = SBG_OK;
+    {
+        SbgProfScope prof(s, SBG_K_ATTENTION, qm * (D + DV), 4.0 * N * (qd + mk + qv + 2.0 * Q), {N, Q, M, D, DV, 1, ATT_V_STREAM_STATS});
+        rc = launch_att_stream_dvt<true>(DV / 16, theta, phi, g, dout, nullptr, lse, delta, N, Q, M, D, DV, s);
+    }
+    if (rc != SBG_OK) return rc;
+    {
+        SbgProfScope prof(s, SBG_K_ATTENTION, qm * (2.0 * D + DV), 4.0 * N * (2.0 * qd + mk + qv + 2.0 * Q), {N, Q, M, D, DV, 1, ATT_V_STREAM_DQ});
+        switch ((D + 15) / 16) {
+            case 1: rc = launch_att_bwd_dq_stream<1>(theta, phi, g, dout, lse, delta, dtheta, N, Q, M, D, DV, s); break;
+            case 2: rc = launch_att_bwd_dq_stream<2>(theta, phi, g, dout, lse, delta, dtheta, N, Q, M, D, DV, s); break;
+            case 4: rc = launch_att_bwd_dq_stream<4>(theta, phi, g, dout, lse, delta, dtheta, N, Q, M, D, DV, s); break;
+            default: rc = sbg_fail(SBG_ERR_UNSUPPORTED, "attention_bwd: D = %d needs 1, 2 or 4 column tiles of 16", D);
+        }
+    }
+    if (rc != SBG_OK) return rc;
+    {
+        SbgProfScope prof(s, SBG_K_ATTENTION, qm * (2.0 * D + 2.0 * DV), 4.0 * N * (qd + qv + 2.0 * mk + 2.0 * Q), {N, Q, M, D, DV, 1, ATT_V_STREAM_DKV});
+        switch (DV / 16) {
+            case 1:  rc = launch_att_bwd_dkv<1>(theta, phi, g, dout, lse, delta, dphi, dg, N, Q, M, D, DV, s); break;
+            case 2:  rc = launch_att_bwd_dkv<2>(theta, phi, g, dout, lse, delta, dphi, dg, N, Q, M, D, DV, s); break;
+            case 4:  rc = launch_att_bwd_dkv<4>(theta, phi, g, dout, lse, delta, dphi, dg, N, Q, M, D, DV, s); break;
+            case 8:  rc = launch_att_bwd_dkv<8>(theta, phi, g, dout, lse, delta, dphi, dg, N, Q, M, D, DV, s); break;
+            case 16: rc = launch_att_bwd_dkv<16>(theta, phi, g, dout, lse, delta, dphi, dg, N, Q, M, D, DV, s); break;
+            default: rc = sbg_fail(SBG_ERR_UNSUPPORTED, "attention_bwd: DV / 16 must be 1, 2, 4, 8 or 16 (got DV = %d)", DV);
+        }
+    }
+    if (rc != SBG_OK) return rc;
+    SBG_HIP_LAUNCH_CHECK();
+    return SBG_OK;
+}
+
 // First-order gradients of out = softmax(theta phi^T) g.  workspace: sbg_attention_bwd_workspace(N, Q) bytes (row statistics).
 extern "C" int sbg_attention_bwd(const float* theta, const float* phi, const float* g, const float* dout, float* dtheta, float* dphi, float* dg,
                                  void* workspace, int N, int Q, int M, int D, int DV, sbg_stream_t stream)
@@ -389,6 +648,7 @@ extern "C" int sbg_attention_bwd(const float* theta, const float* phi, const flo
     hipStream_t s = (hipStream_t)stream;
     float* lse = (float*)workspace;
     float* delta = lse + (int64_t)N * Q;
+    if (M > ATT_MAX_M) return attention_bwd_stream(theta, phi, g, dout, dtheta, dphi, dg, lse, delta, N, Q, M, D, DV, s);
     SbgProfScope prof(s, SBG_K_ATTENTION, 2.0 * N * (double)Q * M * (3.0 * D + 3.0 * DV), 4.0 * N * (2.0 * Q * D + 2.0 * M * (D + DV) + 2.0 * Q * DV), {N, Q, M, D, DV, 1});
     int rc = SBG_OK;
     switch (M / 16) {
@@ -422,6 +682,16 @@ extern "C" int sbg_attention_fwd(const float* theta, const float* phi, const flo
     hipStream_t s = (hipStream_t)stream;
     SbgProfScope prof(s, SBG_K_ATTENTION, 2.0 * N * (double)Q * M * (D + DV), 4.0 * N * ((double)Q * D + (double)M * (D + DV) + (double)Q * DV), {N, Q, M, D, DV});
     int rc = SBG_OK;
+    if (M > ATT_MAX_M) {
+        // as many of the DV / 16 output tiles per workgroup as divide them (16, 8, 4, 2 or 1); the other column groups go to grid.z
+        int dvt = 16;
+        while ((DV / 16) % dvt) dvt >>= 1;
+        prof.set_dim(6, ATT_V_STREAM);
+        rc = launch_att_stream_dvt<false>(dvt, theta, phi, g, nullptr, out, nullptr, nullptr, N, Q, M, D, DV, s);
+        if (rc != SBG_OK) return rc;
+        SBG_HIP_LAUNCH_CHECK();
+        return SBG_OK;
+    }
     switch (M / 16) {
         case 1:  rc = launch_att<1>(theta, phi, g, out, N, Q, M, D, DV, s); break;
         case 2:  rc = launch_att<2>(theta, phi, g, out, N, Q, M, D, DV, s); break;
