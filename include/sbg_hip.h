@@ -512,6 +512,28 @@ int sbg_knn_in_manifold(const void* probes, const void* manifold, const void* ra
                         sbg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * End of a training phase over a flat fp32 gradient bucket: the reference's per-parameter loop `misc.nan_to_num(param.grad, nan=0,
+ * posinf=1e5, neginf=-1e5, out=param.grad)` (train_parts/trainers.py:745-747), the 1/world averaging of a data-parallel exchange and
+ * the gradient-health statistics of the run log, in one pass over the bucket.  For flat[0..n) and a scale s:
+ *   y = x * s (one fp32 multiply, skipped when s == 1.0f);  z = isnan(y) ? +0 : y == +inf ? 1e5f : y == -inf ? -1e5f : y;  flat[i] = z;
+ *   count = #{i : y_i not finite},  sumsq = sum (double)z_i * (double)z_i,  absmax = max |z_i|.
+ * Every workgroup owns a contiguous chunk whose length depends on n alone, never on the device (4096 * ceil(n / 2^24) elements, so
+ * at most 4096 chunks), and writes one float64 record [count, sumsq, absmax] to `partials`; the sums inside a workgroup follow
+ * csrc/reduce.h.
+ *   sbg_grad_finish_records (trainers.py:745-747): host only; the number of records a sweep over n elements writes
+ *                           (ceil(n / chunk); 0 for n == 0, -1 for n < 0).  The largest n with one record is the chunk length of every n <= 2^24.
+ *   sbg_grad_finish_sweep   (trainers.py:745-747): the pass above.  `flat` must be 16-byte aligned (an error otherwise, never a slower
+ *                           path), `partials` holds 3 * records doubles.
+ *   sbg_grad_finish_merge   (trainers.py:745-747): one workgroup adds `records` consecutive records into result[0..3) (count and
+ *                           sumsq added, absmax maximised) in an order fixed by `records` alone: lane t of its 256 adds records t, t + 256, ...
+ *                           in ascending order, the lanes are added as in csrc/reduce.h.  The records of several sweeps laid out back to back are merged
+ *                           by one call; records == 0 gives zeros.
+ * No atomics, two launches instead of an in-kernel finish: two runs give the same bits. */
+int64_t sbg_grad_finish_records(int64_t n);
+int sbg_grad_finish_sweep(float* flat, int64_t n, float scale, double* partials, sbg_stream_t stream);
+int sbg_grad_finish_merge(const double* partials, int64_t records, double* result, sbg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * In-process launch timing (measurement only; bench.py's roofline figures come from here).
  * While enabled, every kernel launch of this library is bracketed by two hipEvents recorded on the launch stream
  * and logged with its algorithmic flops / bytes.  sbg_prof_fetch() synchronises the logged events, writes up to `max`
@@ -526,8 +548,10 @@ enum sbg_kernel_kind {
                                  * pixels / 3 one pixel per work-item), 1 truncate_mix (R * Cn, L, D, dims[4] = 1 vec4 / 2 scalar) */
     SBG_K_RESAMPLE = 21,        /* dims[0] = variant: 0 h (N, rows, in_w, out_w, C, dims[6] = strip), 1 v (N, row_bytes, in_h, out_h, ksize,
                                  * dims[6] = 1 dword / 2 byte loads) */
-    SBG_K_PR = 22               /* dims[0] = variant: 0 single / 1 split (the tile kernel, one / several column runs per row tile), 2 merge,
+    SBG_K_PR = 22,              /* dims[0] = variant: 0 single / 1 split (the tile kernel, one / several column runs per row tile), 2 merge,
                                  * 3 norms; then R, C, F, k, runs, dims[6] = 0 radius / 1 membership */
+    SBG_K_GRAD_FINISH = 23      /* dims[0] = variant: 0 sweep (records, n clipped to INT32_MAX, dims[3] = 1 when the scale is applied),
+                                 * 1 merge (records) */
 };
 /* Kernel-variant codes in the records of the streaming kernels (which kernel served the launch):
  *   bias_act     dims[4] = 1 vec8 / 2 scalar,  dims[5] = bias mode (0 none, 1 channel-minor vector, 2 one per 8-vector, 3 generic)

@@ -105,13 +105,14 @@ class ProfRecord(ctypes.Structure):
 
 KERNEL_KINDS = {1: "bias_act", 2: "upfirdn2d", 3: "conv_igemm", 4: "conv_wgrad", 5: "wgrad_reduce", 6: "scale_nc", 7: "dot_hw", 9: "sn_power", 10: "attention",
                 11: "grid_sample", 12: "filter1d", 13: "color", 14: "weight_prep", 15: "torgb", 16: "fromrgb", 17: "grouped_gemm", 18: "ppl",
-                19: "projector", 20: "image_export", 21: "resample", 22: "pr"}
+                19: "projector", 20: "image_export", 21: "resample", 22: "pr", 23: "grad_finish"}
 PPL_VARIANTS = {0: "slerp", 1: "lerp", 2: "prep", 3: "dist"}        # dims[0] of a "ppl" launch record
 PROJ_VARIANTS = {0: "reg", 1: "reg_bwd", 2: "normalize", 3: "sqdist", 4: "sqdist_bwd"}      # dims[0] of a "projector" launch record
 IMG_VARIANTS = {0: "quantize_tile", 1: "truncate_mix"}      # dims[0] of an "image_export" launch record
 QUANT_RULES = {"grid": 0, "clamp": 1}                       # enum sbg_quant_rule
 RESAMPLE_VARIANTS = {0: "h", 1: "v"}                        # dims[0] of a "resample" launch record
 PR_VARIANTS = {0: "single", 1: "split", 2: "merge", 3: "norms"}    # dims[0] of a "pr" launch record (dims[6]: 0 radius, 1 membership)
+GRAD_FINISH_VARIANTS = {0: "sweep", 1: "merge"}             # dims[0] of a "grad_finish" launch record
 ATT_VARIANTS = {0: "single", 1: "stream", 2: "stream_stats", 3: "stream_dq", 4: "stream_dkv"}     # dims[6] of an "attention" launch record (dims[5]: 0 forward, 1 backward)
 
 _lib = None
@@ -195,6 +196,9 @@ SYMBOLS = [
     ("sbg_knn_workspace", _c.c_int64, [_c.c_int] * 4),
     ("sbg_knn_kth_radius", _c.c_int, [_c.c_void_p] * 2 + [_c.c_int, _c.c_int, _c.c_int64, _c.c_int] + [_c.c_void_p] * 3),
     ("sbg_knn_in_manifold", _c.c_int, [_c.c_void_p] * 3 + [_c.c_int, _c.c_int, _c.c_int64] + [_c.c_void_p] * 3),
+    ("sbg_grad_finish_records", _c.c_int64, [_c.c_int64]),
+    ("sbg_grad_finish_sweep", _c.c_int, [_c.c_void_p, _c.c_int64, _c.c_float, _c.c_void_p, _c.c_void_p]),
+    ("sbg_grad_finish_merge", _c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_void_p]),
     ("sbg_prof_enable", _c.c_int, [_c.c_int]),
     ("sbg_prof_fetch", _c.c_int, [_c.POINTER(ProfRecord), _c.c_int]),
 ]

@@ -13,7 +13,8 @@ the next backward synchronises" latch -- with an MI355X-oriented mechanism:
   that finish backward first overlaps the backward of the rest;
 * ``finish()`` ends a phase: every bucket that still holds un-exchanged gradients is reduced, then waited for, averaged and
   passed through ``nan_to_num`` (the reference's per-parameter loop, trainers.py:745-747) over the flat buckets -- a handful
-  of launches instead of hundreds;
+  of launches instead of hundreds; with ``health`` on, one fused HIP pass per bucket does all three and also leaves the phase's
+  gradient health (``last_health``) on the device;
 * ``zero_grad()`` is one memset per bucket.
 
 Several synchronising backwards between ``zero_grad()`` and ``finish()`` (path-length or gradient-penalty regularisers run one
@@ -29,7 +30,7 @@ forward clears what an earlier backward left half-marked (parameters it did not 
 Instrumentation for ``bench.py`` (off by default, no host synchronisation when on): ``timing`` collects a device-event pair
 around every wait for an exchange -- the time the compute stream is actually stalled by the collective, i.e. what backward did
 NOT hide --, ``nonfinite`` accumulates the count of non-finite gradient elements per ``finish()`` BEFORE ``nan_to_num`` erases
-them.
+them (with ``health`` on the count comes from ``last_health``, without a further pass over the buckets).
 
 With ``world_size == 1`` nothing is communicated and the class is just the flat-gradient container.  The collective backend
 is whatever ``torch.distributed`` was initialised with: ``nccl`` (= RCCL) on GPUs, ``gloo`` in the CPU tests.
@@ -39,6 +40,8 @@ import time
 
 import torch
 import torch.distributed as dist
+
+from .torch_utils.ops import grad_finish
 
 
 class _Bucket:
@@ -71,6 +74,10 @@ class GradReducer(torch.nn.Module):
         self._bucket_of = dict()
         self.timing = None              # list of (event, event) / (t0, t1) pairs around waits when bench.py switches it on
         self.nonfinite = None           # device scalar: non-finite gradient elements seen by finish() before nan_to_num
+        self.health = False             # finish() through the fused HIP pass that also measures the gradients (the run log switches it on)
+        self.last_health = None         # float64 [3] on the buckets' device after a finish() with `health`: [non-finite count, sum of squares, max magnitude]
+        self._health_ws = None          # float64 [records of all buckets, 3]: the partial records of the sweeps, merged by one launch
+        self._health_rows = None
 
         params = [p for p in module.parameters()]
         if self.world_size > 1 and broadcast:
@@ -148,8 +155,9 @@ class GradReducer(torch.nn.Module):
             b.dirty = False
             b.ready.clear()
 
-    def _wait(self, b):
-        """complete bucket b's exchange and turn its sum into a mean"""
+    def _wait(self, b, scale=True):
+        """complete bucket b's exchange and turn its sum into a mean; `scale=False` leaves the multiply by 1/world to the caller
+        (finish() folds it into its one pass over the bucket)"""
         if self.timing is None:
             b.work.wait()
         elif b.flat.is_cuda:        # work.wait() makes the compute stream wait for RCCL's: the event pair brackets exactly that stall
@@ -160,7 +168,8 @@ class GradReducer(torch.nn.Module):
             t0 = time.perf_counter(); b.work.wait()
             self.timing.append((t0, time.perf_counter()))
         b.work = None
-        b.flat.mul_(1.0 / self.world_size)
+        if scale:
+            b.flat.mul_(1.0 / self.world_size)
 
     def _settle(self):
         """wait for the exchanges in flight and turn their sums into means"""
@@ -189,19 +198,53 @@ class GradReducer(torch.nn.Module):
     def finish(self, nan_to_num=True, reduce=True):
         """End of a phase: exchange what no backward hook has exchanged yet (buckets whose parameters did not all receive a
         gradient, or whose last backward ran under ``no_sync``), wait, average, sanitise.  After this every rank holds the
-        mean over ranks of everything accumulated since ``zero_grad()``.  ``reduce=False`` keeps un-exchanged gradients local."""
+        mean over ranks of everything accumulated since ``zero_grad()``.  ``reduce=False`` keeps un-exchanged gradients local.
+
+        With ``health`` off (the default) the buckets go through the torch ops: ``mul_`` by 1/world, ``nan_to_num`` (reference
+        trainers.py:745-747).  With ``health`` on, a device bucket takes ONE pass instead (csrc/grad_finish.hip): the 1/world scale of an
+        exchange that was still in flight here, the same ``nan_to_num`` bit for bit and, from the same read, the records that one merge
+        launch adds up to ``last_health`` = float64 [non-finite elements before sanitising, sum of squares after, largest magnitude
+        after] over all buckets -- a fresh device tensor, no host read.  CPU buckets fill it with the same formulas in torch.
+        ``nan_to_num=False`` (the caller discards the gradients) only waits and averages and leaves ``last_health`` alone."""
+        fused = self.health and nan_to_num
+        unscaled = set()
         if self.world_size > 1:
             if reduce:
                 for b in self._buckets:
                     if b.dirty and b.work is None:
                         self._launch(b)
-            self._settle()
+            for b in self._buckets:
+                if b.work is not None:
+                    fold = fused and b.flat.is_cuda
+                    self._wait(b, scale=not fold)
+                    if fold:
+                        unscaled.add(id(b))
         for b in self._buckets:
             b.ready.clear()
-            if self.nonfinite is not None:
-                self.nonfinite += (~torch.isfinite(b.flat)).sum()
-            if nan_to_num:
-                torch.nan_to_num(b.flat, nan=0, posinf=1e5, neginf=-1e5, out=b.flat)
+        if not fused:
+            for b in self._buckets:
+                if self.nonfinite is not None:
+                    self.nonfinite += (~torch.isfinite(b.flat)).sum()
+                if nan_to_num:
+                    torch.nan_to_num(b.flat, nan=0, posinf=1e5, neginf=-1e5, out=b.flat)
+            return
+        if not self._buckets:
+            return
+        dev = self._buckets[0].flat.device
+        if dev.type == "cuda":
+            if self._health_ws is None:
+                self._health_rows = [grad_finish.records(b.flat.numel()) for b in self._buckets]
+                self._health_ws = torch.zeros([max(sum(self._health_rows), 1), 3], dtype=torch.float64, device=dev)
+            row = 0
+            for b, rows in zip(self._buckets, self._health_rows):
+                grad_finish.sweep(b.flat, 1.0 / self.world_size if id(b) in unscaled else 1.0, self._health_ws[row:row + rows])
+                row += rows
+            self.last_health = grad_finish.merge(self._health_ws[:row])
+        else:
+            parts = torch.stack([grad_finish.finish_cpu(b.flat) for b in self._buckets])
+            self.last_health = torch.stack([parts[:, 0].sum(), parts[:, 1].sum(), parts[:, 2].max()])
+        if self.nonfinite is not None:
+            self.nonfinite += self.last_health[0].to(self.nonfinite.dtype)
 
     def exposed_wait_ms(self, reset=True):
         """sum of the stalls recorded in `timing` (ms); the caller synchronises the device first"""

@@ -36,8 +36,12 @@ _STAGE_ARGS = {"distribute_torch": lambda temp_dir, max_iterations: (temp_dir,),
 def multiprocesses_main(rank, trainer, temp_dir, max_iterations=None):
     """one rank: every lifecycle stage in order"""
     trainer.rank = rank
-    for stage in LIFECYCLE:
-        getattr(trainer, stage)(*_STAGE_ARGS.get(stage, lambda *_: ())(temp_dir, max_iterations))
+    trainer.run_capped = max_iterations is not None     # log.run_log=auto: a run without a cap is a real run and keeps a run log
+    try:
+        for stage in LIFECYCLE:
+            getattr(trainer, stage)(*_STAGE_ARGS.get(stage, lambda *_: ())(temp_dir, max_iterations))
+    finally:
+        trainer.close_logs()
 
 
 if __name__ == "__main__":

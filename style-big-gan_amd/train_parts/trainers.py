@@ -6,14 +6,17 @@ regularisation (``setup_training_phases`` :601-633: Gmain / Greg / Dmain / Dreg,
 ``zero_grad`` -> accumulation rounds of ``loss.accumulate_gradients`` -> ``nan_to_num`` of the gradients ->
 ``opt.step()``), the generator EMA (:752-761) and the data-parallel wiring of ``distrib_acrros_gpu`` (:587-597) /
 ``SG2Trainer`` (:883-893: mapping, synthesis and D are separate data-parallel modules so they can be synchronised
-independently).  Logging, snapshots, metrics and dataset plumbing are out of scope of this engine.
+independently).  The engine itself logs nothing; two switches (`time_phases`, `report_grad_health`) let the trainer's run log read
+per-phase device times and the gradient health of every phase without a host synchronisation.
 
 MI355X specifics: gradients live in flat fp32 buckets (``parallel.GradReducer``) that are all-reduced over RCCL as soon
 as their last gradient of the phase's final accumulation round has been written, overlapping xGMI traffic with the rest
 of backward; ``nan_to_num`` and Adam run over the flat buckets / foreach lists instead of per-parameter launches.
 """
 import copy
+import json
 import os
+import time
 
 import numpy as np
 import torch
@@ -93,6 +96,39 @@ def lazy_reg_opt_kwargs(opt_kwargs, interval):
     return out
 
 
+def format_time(seconds):
+    """seconds -> '42s' | '3m 07s' | '5h 00m 12s' | '2d 03h 15m' (reference stylegan2ada/dnnlib/util.py:139-150)"""
+    s = int(np.rint(seconds))
+    if s < 60:
+        return f"{s}s"
+    if s < 60 * 60:
+        return f"{s // 60}m {s % 60:02}s"
+    if s < 24 * 60 * 60:
+        return f"{s // (60 * 60)}h {(s // 60) % 60:02}m {s % 60:02}s"
+    return f"{s // (24 * 60 * 60)}d {(s // (60 * 60)) % 24:02}h {(s // 60) % 60:02}m"
+
+
+def cpu_mem_gb():
+    """resident set of this process in GiB, from /proc/self/statm (0 where there is no procfs)"""
+    try:
+        with open("/proc/self/statm") as fh:
+            return int(fh.read().split()[1]) * os.sysconf("SC_PAGE_SIZE") / 2 ** 30
+    except (OSError, ValueError, IndexError):
+        return 0.0
+
+
+def _option_lines(obj, tabs=0):
+    """nested options, one 'key : value' line each, groups indented by four (the layout of the reference's banner, :121-128)"""
+    out = []
+    for key, value in obj.items():
+        if isinstance(value, dict):
+            out.append(" " * tabs + f"{key}:")
+            out += _option_lines(value, tabs + 4)
+        else:
+            out.append(" " * tabs + f"{key} : {value}")
+    return out
+
+
 @trainers.add_to_registry("step_engine")
 class StepEngine:
     """Owns G, D, G_ema, the optimizers and the phase schedule; `train_iteration` is one G+D step on this rank.
@@ -118,6 +154,9 @@ class StepEngine:
         self._round_proven = set()  # merged-round plans that have run once without exhausting device memory
         self._count_nonfinite = False
         self.comm_stats = None      # bench.py: {phase: dict(pairs=[event pairs around waits for exchanges], nonfinite=device counter)}
+        self.time_phases = False            # a device-event pair around every executed phase (reference :730, :749); nothing on a CPU device
+        self.report_grad_health = False     # Grad/<phase>/{norm, absmax, nonfinite} after every phase's finish(): device scalars, no sync (set_grad_health)
+        self._phase_events = {}             # phase name -> (start, end): the pair of the phase's latest execution
 
         torch.manual_seed(seed * max(world_size, 1) + rank)     # reference :507-508
         self.G = generators[generator](**(gen_kwargs or {})).train().requires_grad_(False).to(self.device)
@@ -222,6 +261,11 @@ class StepEngine:
         for phase, phase_z, phase_c in zip(self.phases, zs, cs):
             if phase.idle or self.batch_idx % phase.interval != 0:
                 continue
+            events = None
+            if self.time_phases and self.device.type == 'cuda':
+                events = self._phase_events.get(phase.name) or (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+                self._phase_events[phase.name] = None       # not readable until the end event is recorded
+                events[0].record(torch.cuda.current_stream(self.device))
             with torch.autograd.profiler.record_function(phase.name):
                 for r in phase.reducers:
                     r.zero_grad()
@@ -270,7 +314,12 @@ class StepEngine:
                         r.nonfinite = None
                 if st is not None:
                     st['runs'] += 1
+                if self.report_grad_health:
+                    self._report_grad_health(phase)
                 phase.opt.step()
+            if events is not None:
+                events[1].record(torch.cuda.current_stream(self.device))
+                self._phase_events[phase.name] = events
 
         if self.G_ema is not None:
             with torch.autograd.profiler.record_function('Gema'):
@@ -296,6 +345,32 @@ class StepEngine:
                 # the sampler keeps the old strength for exactly one more iteration, then switches (deterministic, identical on all ranks)
                 self.augment_pipe.announce_strength_update()
                 self._ada_adopt_at = self.batch_idx + 1
+
+    def set_grad_health(self, on=True):
+        """switch `report_grad_health` and, with it, the reducers' fused finish that measures the gradients (GradReducer.health)"""
+        self.report_grad_health = bool(on)
+        for r in self.dp_modules.values():
+            r.health = bool(on)
+
+    def _report_grad_health(self, phase):
+        """Grad/<phase>/norm = sqrt of the reducers' sums of squares added up, /absmax, /nonfinite (elements that were not finite BEFORE
+        nan_to_num replaced them), from the records finish() left on the device (GradReducer.last_health)"""
+        health = [r.last_health for r in phase.reducers if r.last_health is not None]
+        if not health:
+            return
+        h = torch.stack(health)
+        training_stats.report(f'Grad/{phase.name}/norm', h[:, 1].sum().sqrt())
+        training_stats.report(f'Grad/{phase.name}/absmax', h[:, 2].max())
+        training_stats.report(f'Grad/{phase.name}/nonfinite', h[:, 0].sum())
+
+    def phase_times(self):
+        """{phase name: milliseconds of its latest execution} from the event pairs of `time_phases`; waits for each end event"""
+        out = {}
+        for name, events in self._phase_events.items():
+            if events is not None:
+                events[1].synchronize()
+                out[name] = events[0].elapsed_time(events[1])
+        return out
 
     def collect_comm_stats(self, on=True, nonfinite=True):
         """bench.py: per phase, the device-event pairs around every wait for a gradient exchange (what backward did not hide) and, with
@@ -460,6 +535,11 @@ class BaseTrainer:
         self.rank = 0
         self.config = None
         self.grid_size = self.grid_z = self.grid_c = None       # the snapshot image grid, set by the first save_image_snapshot
+        self.run_capped = True      # starter.multiprocesses_main says whether training_loop gets an iteration cap (log.run_log=auto reads it)
+        self.run_log = False        # decided by setup_logs
+        self.cur_tick = 0           # the tick in progress
+        self.start_time = None
+        self._log_txt = self._stats_jsonl = None
 
     # -- argument assembly / validation (reference :155-395) -----------------------------------------------------------
     def setup_arguments(self, config):
@@ -483,6 +563,13 @@ class BaseTrainer:
             raise ValueError(f"trans.resume={self.resume_path}: no such snapshot file (named transfer-learning sources are URL fetches and "
                              "reference .pkl snapshots are pickled modules; neither is loaded here -- pass a .pt written by save_snapshot)")
         self.run_dir = os.path.join(str(config.log.output), str(config.exp.name)) if config.exp.get("name", utils.MISSING) != utils.MISSING else None
+        mode = config.log.get("run_log", "auto")
+        mode = {True: "on", False: "off"}.get(mode, mode) if isinstance(mode, bool) else mode      # yaml reads a bare on / off as a boolean
+        if mode not in ("auto", "on", "off"):
+            raise ValueError(f"log.run_log={mode}: use auto, on or off")
+        self.run_log_mode = mode
+        self.kimg_per_tick = float(config.log.kimg_per_tick)
+        self.snap_ticks = int(config.log.snap) if config.log.snap else None        # ticks between image / network snapshots of the run log
         self.snapshot_iterations = None     # iterations between snapshots; None = only on request
         self.image_snapshot_iterations = None       # iterations between image snapshots (fakes<kimg>.png); None = only on request
         from ..metrics import metric_main
@@ -592,7 +679,55 @@ class BaseTrainer:
 
     # -- lifecycle ------------------------------------------------------------------------------------------------------
     def setup_logs(self):
+        """log.run_log: `on`, `off`, or `auto` = on exactly when the training loop runs without an iteration cap.  With the run log on,
+        rank 0 creates the run directory, prints the banner (reference :418-430) and opens log.txt and stats.jsonl for appending (a
+        resumed run continues both files)."""
         self.stats = training_stats.Collector(regex=".*")
+        self.start_time = time.time()
+        self.run_log = self.run_log_mode == "on" or (self.run_log_mode == "auto" and not self.run_capped)
+        if not self.run_log:
+            return
+        if self.kimg_per_tick <= 0:
+            raise ValueError("log.kimg_per_tick must be positive")
+        if self.run_dir is None:
+            raise ValueError("the run log needs exp.name (the run directory is log.output/exp.name); log.run_log=off turns it off")
+        if self.rank != 0:
+            return
+        os.makedirs(self.run_dir, exist_ok=True)
+        self._log_txt = open(os.path.join(self.run_dir, "log.txt"), "at")
+        self._stats_jsonl = open(os.path.join(self.run_dir, "stats.jsonl"), "at")
+        data = self.config.data
+        self.log("", "Training options:", *_option_lines(self.config), "",
+                 f"Output directory:   {self.run_dir}",
+                 f"Training data:      {data.dataset_path if self.real_data else 'synthetic'}",
+                 f"Training duration:  {self.total_kimg} kimg",
+                 f"Number of GPUs:     {self.num_gpus}",
+                 f"Number of images:   {len(self.dataset)}",
+                 f"Image resolution:   {self.dataset.resolution}",
+                 f"Conditional model:  {bool(self.dataset.has_labels)}",
+                 f"Dataset x-flips:    {bool(data.mirror)}", "")
+
+    def log(self, *lines):
+        """everything the trainer says: rank 0 prints each line and, with the run log on, appends it to log.txt"""
+        if self.rank != 0:
+            return
+        for line in lines:
+            print(line, flush=True)
+            if self._log_txt is not None:
+                self._log_txt.write(str(line) + "\n")
+        if self._log_txt is not None:
+            self._log_txt.flush()
+
+    def close_logs(self):
+        for fh in (self._log_txt, self._stats_jsonl):
+            if fh is not None:
+                fh.close()
+        self._log_txt = self._stats_jsonl = None
+
+    def __getstate__(self):
+        state = dict(self.__dict__)     # the trainer crosses to the rank processes before any file is open; never carry a handle
+        state["_log_txt"] = state["_stats_jsonl"] = None
+        return state
 
     def distribute_torch(self, temp_dir):
         if self.num_gpus > 1:
@@ -636,24 +771,28 @@ class BaseTrainer:
                                  batch=self.batch_size // self.num_gpus, batch_gpu=self.batch_gpu, ema_kimg=self.config.ema.kimg,
                                  ema_rampup=self.ema_rampup, use_ema=self.config.ema.use_ema, world_size=self.num_gpus, rank=self.rank,
                                  seed=gen.seed, **self.aug)
+        self.engine.time_phases = self.run_log
+        self.engine.set_grad_health(self.run_log)
 
     def setup_augmentations(self):
         self.augment_pipe = self.engine.augment_pipe        # built by StepEngine (it owns the loss object the pipe plugs into)
         if self.resume_path is not None:    # networks, pipe and optimizers exist now: continue from the snapshot
             self.resume(self.resume_path)
 
-    def save_snapshot(self, cur_nimg=None, run_dir=None):
+    def save_snapshot(self, cur_nimg=None, run_dir=None, cur_tick=None):
         """network-snapshot-<kimg>.pt + training_options.json with `start_options` (reference :636-656, :821-832).  Rank 0 writes."""
         run_dir = run_dir or self.run_dir
         assert run_dir is not None, "save_snapshot needs exp.name / log.output or an explicit run_dir"
         cur_nimg = self.engine.cur_nimg if cur_nimg is None else cur_nimg
         path = os.path.join(run_dir, f"network-snapshot-{cur_nimg // 1000:06d}.pt")
         if self.rank == 0:
-            import json
             os.makedirs(run_dir, exist_ok=True)
             state = self.engine.state_dict()
+            start_options = dict(cur_nimg=int(self.engine.cur_nimg), batch_idx=int(self.engine.batch_idx))
+            if self.run_log:        # the tick a run resumed from this file starts with (reference :827)
+                state["progress"]["cur_tick"] = start_options["cur_tick"] = int(self.cur_tick if cur_tick is None else cur_tick)
             torch.save(state, path)
-            options = dict(start_options=dict(cur_nimg=int(self.engine.cur_nimg), batch_idx=int(self.engine.batch_idx)),
+            options = dict(start_options=start_options,
                            snapshot=os.path.basename(path), num_gpus=self.num_gpus, batch_size=self.batch_size, batch_gpu=self.batch_gpu)
             with open(os.path.join(run_dir, "training_options.json"), "wt") as f:
                 json.dump(options, f, indent=2)
@@ -691,6 +830,8 @@ class BaseTrainer:
     def resume(self, path, networks_only=False):
         state = torch.load(path, map_location=self.engine.device, weights_only=True)
         self.engine.load_state_dict(state, networks_only=networks_only)
+        if not networks_only:
+            self.cur_tick = int(state["progress"].get("cur_tick", 0))
         if self.num_gpus > 1:       # every rank read the same file; keep the data-parallel invariant explicit
             for module in (self.engine.G, self.engine.D):
                 for t in list(module.parameters()) + list(module.buffers()):
@@ -705,7 +846,7 @@ class BaseTrainer:
 
     def export_sample_images(self):
         """reals.png and fakes_init.png at the start of a run (reference :677-696), when image snapshots are switched on"""
-        if self.image_snapshot_iterations:
+        if self.image_snapshot_iterations or self.run_log:
             self.save_image_snapshot()
 
     def save_image_snapshot(self, run_dir=None):
@@ -723,7 +864,7 @@ class BaseTrainer:
         os.makedirs(run_dir, exist_ok=True)
         first = self.grid_size is None
         if first:
-            print('Exporting sample images...')
+            self.log('Exporting sample images...')
             self.grid_size, images, labels = setup_snapshot_image_grid(training_set=self.dataset)
             save_image_grid(images, os.path.join(run_dir, 'reals.png'), drange=[0, 255], grid_size=self.grid_size)
             self.grid_z = torch.randn([labels.shape[0], eng.z_dim], device=eng.device).split(self.batch_gpu)
@@ -743,8 +884,14 @@ class BaseTrainer:
         return path
 
     def training_loop(self, max_iterations=None):
+        """Iterate until gen.kimg (or the cap).  With the run log on, a tick after the first iteration of a fresh run, then whenever
+        log.kimg_per_tick thousand images have passed since the last one, and one at the end (reference :773-776)."""
         eng = self.engine
         total = self.total_kimg * 1000
+        if self.run_log:
+            self.log(f"Training for {self.total_kimg} kimg...", "")
+            self._tick_start_nimg, self._tick_start_time = eng.cur_nimg, time.time()
+            self._maintenance_time = self._tick_start_time - self.start_time
         it = 0
         while (max_iterations is None or it < max_iterations) and (total < 0 or eng.cur_nimg < total or it == 0):
             img, c = self.next_batch(eng.batch, eng.device)
@@ -756,10 +903,63 @@ class BaseTrainer:
                     self.evaluate_metrics(snapshot_path=path)
             if self.image_snapshot_iterations and it % self.image_snapshot_iterations == 0:
                 self.save_image_snapshot()
+            if self.run_log:
+                done = (total >= 0 and eng.cur_nimg >= total) or (max_iterations is not None and it >= max_iterations)
+                if done or self.cur_tick == 0 or eng.cur_nimg >= self._tick_start_nimg + self.kimg_per_tick * 1000:
+                    self.tick(done)
             if max_iterations is None and total >= 0 and eng.cur_nimg >= total:
                 break
-        self.stats.update()
+        if not self.run_log:        # with the run log the closing tick has made the update: one collective and one host synchronisation per tick
+            self.stats.update()
         return it
+
+    def tick(self, done):
+        """One tick of the run log, in the reference's order (:778-876): status line, image snapshot, network snapshot, metrics, phase
+        times, ONE Collector.update() on all ranks (the tick's host synchronisation), one stats.jsonl line on rank 0, counters."""
+        eng = self.engine
+        report0 = training_stats.report0
+        cur_nimg, cur_tick = eng.cur_nimg, self.cur_tick
+        tick_end_time = time.time()
+        sec_per_tick = tick_end_time - self._tick_start_time
+        sec_per_kimg = sec_per_tick / max(cur_nimg - self._tick_start_nimg, 1) * 1e3
+        total_sec = tick_end_time - self.start_time
+        kimg_left = max(self.total_kimg - cur_nimg / 1000, 0) if self.total_kimg >= 0 else 0
+        snapshots_left = int(kimg_left / self.kimg_per_tick) // (self.snap_ticks or 1) + 1
+        on_gpu = eng.device.type == "cuda"
+        gpu_mem = torch.cuda.max_memory_allocated(eng.device) / 2 ** 30 if on_gpu else 0.0
+        if on_gpu:
+            torch.cuda.reset_peak_memory_stats(eng.device)
+        augment = float(self.augment_pipe._strength()) if self.augment_pipe is not None else 0.0       # the pipe's host copy: no device read
+        fields = [f"tick {report0('Progress/tick', cur_tick):<5d}",
+                  f"kimg {report0('Progress/kimg', cur_nimg / 1e3):<8.1f}",
+                  f"time {format_time(report0('Timing/total_sec', total_sec)):<12s}",
+                  f"time left {format_time(int(kimg_left * sec_per_kimg) + snapshots_left * self.metrics_time):<12s}",
+                  f"sec/tick {report0('Timing/sec_per_tick', sec_per_tick):<7.1f}",
+                  f"sec/kimg {report0('Timing/sec_per_kimg', sec_per_kimg):<7.2f}",
+                  f"maintenance {report0('Timing/maintenance_sec', self._maintenance_time):<6.1f}",
+                  f"cpumem {report0('Resources/cpu_mem_gb', cpu_mem_gb()):<6.2f}",
+                  f"gpumem {report0('Resources/peak_gpu_mem_gb', gpu_mem):<6.2f}",
+                  f"augment {report0('Progress/augment', augment):.3f}"]
+        report0('Timing/total_hours', total_sec / (60 * 60))
+        report0('Timing/total_days', total_sec / (24 * 60 * 60))
+        self.log(' '.join(fields))
+
+        if self.snap_ticks is not None and (done or cur_tick % self.snap_ticks == 0):
+            self.save_image_snapshot()
+            path = self.save_snapshot(cur_tick=cur_tick + 1)
+            if self.metrics:
+                self.evaluate_metrics(snapshot_path=path)
+
+        for name, ms in eng.phase_times().items():
+            report0('Timing/' + name, ms)
+        self.stats.update()
+        if self._stats_jsonl is not None:
+            self._stats_jsonl.write(json.dumps(dict(self.stats.as_dict(), timestamp=time.time())) + "\n")
+            self._stats_jsonl.flush()
+
+        self.cur_tick = cur_tick + 1
+        self._tick_start_nimg, self._tick_start_time = cur_nimg, time.time()
+        self._maintenance_time = self._tick_start_time - tick_end_time
 
 
 @trainers.add_to_registry("sg2")
