@@ -534,6 +534,22 @@ int sbg_grad_finish_sweep(float* flat, int64_t n, float scale, double* partials,
 int sbg_grad_finish_merge(const double* partials, int64_t records, double* result, sbg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * A training batch out of a device-resident uint8 image store.  Replaces, per step, the reference's host input path: the item read of
+ * train_parts/datasets.py `Dataset.__getitem__` (:78-83; `image[:, :, ::-1]` for a mirrored item), the stock DataLoader's collate and
+ * PCIe copy, and the normalisation `img.to(torch.float32) / 127.5 - 1` of train_parts/trainers.py:716.
+ * `store` is dense uint8 [S, C, H, W]; `slot` int32 [B]; `flip` uint8 [B] or NULL (nothing mirrored).
+ *   out_f32 = 0:  out uint8 [B, C, H, W],  out[b, c, y, x] = store[slot[b], c, y, flip[b] ? W - 1 - x : x]
+ *   out_f32 = 1:  out fp32  [B, C, H, W],  lut[that byte], `lut` being 256 floats on the device (ignored for uint8 output)
+ * The kernel does no floating-point arithmetic: the caller supplies the 256 values, evaluated by whatever expression and on whatever
+ * device the consumer would have used, so the result has that expression's bits (the table sits in LDS).  Image offsets are 64-bit.
+ * A slot outside [0, S) is never dereferenced: that image of `out` is NaN (fp32) or 0 (uint8), as for the row indices of the
+ * truncate-mix kernel above.  With W % 4 == 0, `store` 4-byte aligned and `out` 16-byte aligned (4-byte for uint8) a work-item moves
+ * 4 pixels of a row (one dword load, byte-reversed from column W - 4 - x when mirrored; one 16-byte or dword store); otherwise one
+ * pixel with byte loads.  An fp32 `out` must be 4-byte aligned in either case; C * H * W may be at most 2^31 - 257. */
+int sbg_u8_gather_images(const uint8_t* store, int64_t S, int C, int H, int W, const int32_t* slot, const uint8_t* flip, int B, void* out,
+                         int out_f32, const float* lut, sbg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * In-process launch timing (measurement only; bench.py's roofline figures come from here).
  * While enabled, every kernel launch of this library is bracketed by two hipEvents recorded on the launch stream
  * and logged with its algorithmic flops / bytes.  sbg_prof_fetch() synchronises the logged events, writes up to `max`
@@ -550,8 +566,9 @@ enum sbg_kernel_kind {
                                  * dims[6] = 1 dword / 2 byte loads) */
     SBG_K_PR = 22,              /* dims[0] = variant: 0 single / 1 split (the tile kernel, one / several column runs per row tile), 2 merge,
                                  * 3 norms; then R, C, F, k, runs, dims[6] = 0 radius / 1 membership */
-    SBG_K_GRAD_FINISH = 23      /* dims[0] = variant: 0 sweep (records, n clipped to INT32_MAX, dims[3] = 1 when the scale is applied),
+    SBG_K_GRAD_FINISH = 23,     /* dims[0] = variant: 0 sweep (records, n clipped to INT32_MAX, dims[3] = 1 when the scale is applied),
                                  * 1 merge (records) */
+    SBG_K_RESIDENT = 24         /* dims = B, C, H, W, out_f32, 0, dims[6] = 1 dword path (4 pixels per work-item) / 2 byte path */
 };
 /* Kernel-variant codes in the records of the streaming kernels (which kernel served the launch):
  *   bias_act     dims[4] = 1 vec8 / 2 scalar,  dims[5] = bias mode (0 none, 1 channel-minor vector, 2 one per 8-vector, 3 generic)

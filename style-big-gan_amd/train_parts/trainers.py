@@ -587,6 +587,8 @@ class BaseTrainer:
             self.training_set_kwargs = kw
             self.data_loader_kwargs = {k: v for k, v in dict(config.get("dataloaders_args", {}).get(config.data.dataloader, {})).items()
                                        if k not in ("args", "kwargs") and v != utils.MISSING}
+            if self.data_loader_kwargs.pop("device", None) is not None:     # a loader's `device` is the rank's training device (setup_dataset)
+                raise ValueError(f"dataloaders_args.{config.data.dataloader}.device is not a setting: the trainer passes each rank's training device")
             self.dataset = datasets[config.data.dataset](**kw)
         else:
             self.dataset = SyntheticDataset(int(config.data.get("resolution", 32)), 3,
@@ -700,12 +702,23 @@ class BaseTrainer:
         self.log("", "Training options:", *_option_lines(self.config), "",
                  f"Output directory:   {self.run_dir}",
                  f"Training data:      {data.dataset_path if self.real_data else 'synthetic'}",
+                 f"Data loader:        {self._loader_line()}",
                  f"Training duration:  {self.total_kimg} kimg",
                  f"Number of GPUs:     {self.num_gpus}",
                  f"Number of images:   {len(self.dataset)}",
                  f"Image resolution:   {self.dataset.resolution}",
                  f"Conditional model:  {bool(self.dataset.has_labels)}",
                  f"Dataset x-flips:    {bool(data.mirror)}", "")
+
+    def _loader_line(self):
+        """the banner's loader entry: the registry name, and for the resident loader the size of the store it is about to build"""
+        if not self.real_data:
+            return "none (synthetic batches)"
+        name = str(self.config.data.dataloader)
+        if name != "resident":
+            return name
+        from .dataloaders import resident_footprint
+        return f"{name} (store {resident_footprint(self.dataset)[0] / 2 ** 30:.3f} GiB)"
 
     def log(self, *lines):
         """everything the trainer says: rank 0 prints each line and, with the run log on, appends it to log.txt"""
@@ -747,13 +760,17 @@ class BaseTrainer:
 
     def setup_dataset(self):
         """real data: endless rank-sharded stream of uint8 batches (reference :517-524); synthetic batches are drawn on demand"""
-        self.training_set_iterator = None
+        self.training_set_iterator = self.training_image_iterator = None
         if self.real_data:
-            from .dataloaders import dataloaders
+            from .dataloaders import accepts_device, dataloaders
             sampler = misc.InfiniteSampler(dataset=self.dataset, rank=self.rank, num_replicas=self.num_gpus, seed=self.config.gen.seed)
-            loader = dataloaders[self.config.data.dataloader](dataset=self.dataset, sampler=sampler, batch_size=self.batch_size // self.num_gpus,
-                                                              **self.data_loader_kwargs)
+            loader_class = dataloaders[self.config.data.dataloader]
+            if accepts_device(loader_class):        # a loader that delivers device tensors is told the training device
+                self.data_loader_kwargs = dict(self.data_loader_kwargs, device=self.device())
+            loader = loader_class(dataset=self.dataset, sampler=sampler, batch_size=self.batch_size // self.num_gpus, **self.data_loader_kwargs)
             self.training_set_iterator = iter(loader)
+            if hasattr(loader, "batches"):          # normalised fp32 batches straight from the loader (next_images)
+                self.training_image_iterator = loader.batches(normalized=True)
 
     def next_batch(self, n, device):
         """-> (uint8 images [n, C, H, W], float32 labels [n, label_dim]) on `device` (normalisation happens there)"""
@@ -761,6 +778,16 @@ class BaseTrainer:
             return self.dataset.batch(n, device)
         img, c = next(self.training_set_iterator)
         return img.to(device, non_blocking=True), c.to(device, non_blocking=True)
+
+    def next_images(self, n, device):
+        """-> (float32 images [n, C, H, W] in [-1, 1], float32 labels [n, label_dim]) on `device`: what a training iteration is fed.  A
+        loader that offers `batches` (the resident one) delivers them normalised; every other source goes through `next_batch` and
+        the reference's expression (:716)"""
+        if getattr(self, "training_image_iterator", None) is not None:
+            img, c = next(self.training_image_iterator)
+            return img.to(device, non_blocking=True), c.to(device, non_blocking=True)
+        img, c = self.next_batch(n, device)
+        return img.to(torch.float32) / 127.5 - 1, c
 
     def setup_networks(self):
         gen = self.config.gen
@@ -894,8 +921,7 @@ class BaseTrainer:
             self._maintenance_time = self._tick_start_time - self.start_time
         it = 0
         while (max_iterations is None or it < max_iterations) and (total < 0 or eng.cur_nimg < total or it == 0):
-            img, c = self.next_batch(eng.batch, eng.device)
-            eng.train_iteration(img.to(torch.float32) / 127.5 - 1, c)
+            eng.train_iteration(*self.next_images(eng.batch, eng.device))
             it += 1
             if self.snapshot_iterations and it % self.snapshot_iterations == 0:
                 path = self.save_snapshot()
