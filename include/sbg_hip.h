@@ -550,6 +550,29 @@ int sbg_u8_gather_images(const uint8_t* store, int64_t S, int C, int H, int W, c
                          int out_f32, const float* lut, sbg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * DiffAugment (Zhao et al., "Differentiable Augmentation for Data-Efficient GAN Training", NeurIPS 2020: colour, translation, cutout)
+ * in front of the discriminator, fused: fp32 dense [N, C, H, W], C = 1..4, rows are axis 2 and columns axis 3.
+ * `table` is the packed per-sample parameter table, int32 [N, SBG_DIFFAUG_WORDS] on the device, 4-byte aligned; words of sample n:
+ *   0 b   1 s   2 k        brightness, saturation, contrast: the bit patterns of three fp32 values
+ *   3 t_row   4 t_col      translation, int32:  y[i, j] = x[i + t_row, j + t_col]
+ *   5 r0  6 r1  7 c0  8 c1 cutout rectangle, int32, half-open: rows [r0, r1) x columns [c0, c1) of the OUTPUT are zeroed
+ *   9..11                  unused (a sample's entry is 48 bytes)
+ * Any integers are safe: a shift of the extent or more gives zeros, a rectangle is clipped to the image, r1 <= r0 or c1 <= c0 is empty.
+ * Forward, with M = mean(x[n]) + b: an output pixel (i, j) outside the rectangle whose source (p, q) = (i + t_row, j + t_col) is inside
+ * the image is   v = x[:, p, q] + b;  v <- s v + (1 - s) mean_c(v);  y[:, i, j] = k v + (1 - k) M;   every other pixel is 0.  With
+ * b = 0, s = k = 1, t = 0 and an empty rectangle y is x bit for bit.  `drop_b` != 0 evaluates the same with b = 0: the adjoint's adjoint.
+ * Adjoint (g = dL/dy -> dx = dL/dx): u[:, p, q] = g[:, p - t_row, q - t_col] where that output pixel exists and is not cut, else 0;
+ *   S = sum(u) / (C H W);  w = k u + (1 - k) S;  dx = s w + (1 - s) mean_c(w).
+ * The per-sample sums are fixed-order (csrc/reduce.h inside chunks of 4096 elements, the chunk sums in ascending order): no atomics,
+ * a sample's bits depend on neither N, its place in the batch nor the run.  C H W <= 4096: one launch, the sample staged in LDS;
+ * larger: a sum launch and an apply launch, with sbg_diffaug_workspace(N, C, H, W) bytes of `workspace` (0: none needed, may be NULL;
+ * -1: unsupported sizes).  x and y (g and dx) must not overlap.  W % 4 == 0 and 16-byte aligned tensors take 16-byte accesses. */
+#define SBG_DIFFAUG_WORDS 12
+int64_t sbg_diffaug_workspace(int N, int C, int H, int W);
+int sbg_diffaug_fwd(const float* x, const int32_t* table, float* y, float* workspace, int N, int C, int H, int W, int drop_b, sbg_stream_t stream);
+int sbg_diffaug_adj(const float* g, const int32_t* table, float* dx, float* workspace, int N, int C, int H, int W, sbg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * In-process launch timing (measurement only; bench.py's roofline figures come from here).
  * While enabled, every kernel launch of this library is bracketed by two hipEvents recorded on the launch stream
  * and logged with its algorithmic flops / bytes.  sbg_prof_fetch() synchronises the logged events, writes up to `max`
@@ -568,7 +591,9 @@ enum sbg_kernel_kind {
                                  * 3 norms; then R, C, F, k, runs, dims[6] = 0 radius / 1 membership */
     SBG_K_GRAD_FINISH = 23,     /* dims[0] = variant: 0 sweep (records, n clipped to INT32_MAX, dims[3] = 1 when the scale is applied),
                                  * 1 merge (records) */
-    SBG_K_RESIDENT = 24         /* dims = B, C, H, W, out_f32, 0, dims[6] = 1 dword path (4 pixels per work-item) / 2 byte path */
+    SBG_K_RESIDENT = 24,        /* dims = B, C, H, W, out_f32, 0, dims[6] = 1 dword path (4 pixels per work-item) / 2 byte path */
+    SBG_K_DIFFAUG = 25          /* dims[0] = variant: 0 sum / 1 apply / 2 adjoint sum / 3 adjoint apply (the two launches of C H W > 4096),
+                                 * 4 single-pass forward / 5 single-pass adjoint (C H W <= 4096); then N, C, H, W, dims[5] = 1 16-byte / 2 dword accesses */
 };
 /* Kernel-variant codes in the records of the streaming kernels (which kernel served the launch):
  *   bias_act     dims[4] = 1 vec8 / 2 scalar,  dims[5] = bias mode (0 none, 1 channel-minor vector, 2 one per 8-vector, 3 generic)

@@ -105,7 +105,7 @@ class ProfRecord(ctypes.Structure):
 
 KERNEL_KINDS = {1: "bias_act", 2: "upfirdn2d", 3: "conv_igemm", 4: "conv_wgrad", 5: "wgrad_reduce", 6: "scale_nc", 7: "dot_hw", 9: "sn_power", 10: "attention",
                 11: "grid_sample", 12: "filter1d", 13: "color", 14: "weight_prep", 15: "torgb", 16: "fromrgb", 17: "grouped_gemm", 18: "ppl",
-                19: "projector", 20: "image_export", 21: "resample", 22: "pr", 23: "grad_finish", 24: "resident"}
+                19: "projector", 20: "image_export", 21: "resample", 22: "pr", 23: "grad_finish", 24: "resident", 25: "diffaug"}
 RESIDENT_PATHS = {1: "dword", 2: "byte"}                    # dims[6] of a "resident" launch record
 PPL_VARIANTS = {0: "slerp", 1: "lerp", 2: "prep", 3: "dist"}        # dims[0] of a "ppl" launch record
 PROJ_VARIANTS = {0: "reg", 1: "reg_bwd", 2: "normalize", 3: "sqdist", 4: "sqdist_bwd"}      # dims[0] of a "projector" launch record
@@ -114,6 +114,8 @@ QUANT_RULES = {"grid": 0, "clamp": 1}                       # enum sbg_quant_rul
 RESAMPLE_VARIANTS = {0: "h", 1: "v"}                        # dims[0] of a "resample" launch record
 PR_VARIANTS = {0: "single", 1: "split", 2: "merge", 3: "norms"}    # dims[0] of a "pr" launch record (dims[6]: 0 radius, 1 membership)
 GRAD_FINISH_VARIANTS = {0: "sweep", 1: "merge"}             # dims[0] of a "grad_finish" launch record
+DIFFAUG_VARIANTS = {0: "sum", 1: "apply", 2: "adj_sum", 3: "adj_apply", 4: "single", 5: "adj_single"}      # dims[0] of a "diffaug" launch record
+DIFFAUG_WORDS = 12                                          # SBG_DIFFAUG_WORDS: int32 words per sample of the packed parameter table
 ATT_VARIANTS = {0: "single", 1: "stream", 2: "stream_stats", 3: "stream_dq", 4: "stream_dkv"}     # dims[6] of an "attention" launch record (dims[5]: 0 forward, 1 backward)
 
 _lib = None
@@ -202,6 +204,9 @@ SYMBOLS = [
     ("sbg_grad_finish_merge", _c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_void_p]),
     ("sbg_u8_gather_images", _c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int,
                                         _c.c_void_p, _c.c_void_p]),
+    ("sbg_diffaug_workspace", _c.c_int64, [_c.c_int] * 4),
+    ("sbg_diffaug_fwd", _c.c_int, [_c.c_void_p] * 4 + [_c.c_int] * 5 + [_c.c_void_p]),
+    ("sbg_diffaug_adj", _c.c_int, [_c.c_void_p] * 4 + [_c.c_int] * 4 + [_c.c_void_p]),
     ("sbg_prof_enable", _c.c_int, [_c.c_int]),
     ("sbg_prof_fetch", _c.c_int, [_c.POINTER(ProfRecord), _c.c_int]),
 ]

@@ -27,6 +27,7 @@ from .. import utils
 from .. import _lib
 from ..torch_utils.ops import upfirdn2d
 from ..torch_utils.ops import grid_sample_gradfix
+from ..torch_utils.ops import diffaug as diffaug_op
 
 augmentations = utils.ClassRegistry()
 
@@ -53,6 +54,20 @@ augpipe_specs['bgc'] = {**augpipe_specs['bg'], **augpipe_specs['color']}
 augpipe_specs['bgcf'] = {**augpipe_specs['bgc'], **augpipe_specs['filter']}
 augpipe_specs['bgcfn'] = {**augpipe_specs['bgcf'], **augpipe_specs['noise']}
 augpipe_specs['bgcfnc'] = {**augpipe_specs['bgcfn'], **augpipe_specs['cutout']}
+
+# the DiffAugment policies: any combination of the three published groups; `config.aug.augpipe` selects one under aug.aug_type=diffaug
+diffaug_specs = {
+    'color':       dict(color=1),
+    'translation': dict(translation=1),
+    'cutout':      dict(cutout=1),
+}
+diffaug_specs['color_translation'] = {**diffaug_specs['color'], **diffaug_specs['translation']}
+diffaug_specs['color_cutout'] = {**diffaug_specs['color'], **diffaug_specs['cutout']}
+diffaug_specs['translation_cutout'] = {**diffaug_specs['translation'], **diffaug_specs['cutout']}
+diffaug_specs['color_translation_cutout'] = {**diffaug_specs['color_translation'], **diffaug_specs['cutout']}
+
+# registry name of a pipe (`config.aug.aug_type`) -> its table of policies
+policy_tables = {'sg2_ada': augpipe_specs, 'diffaug': diffaug_specs}
 
 
 class _Filter1d(torch.autograd.Function):
@@ -109,8 +124,48 @@ class _ColorTransform(torch.autograd.Function):
         return (_ColorTransform.apply(dy, Mt, zero_off) if ctx.needs_input_grad[0] else None), None, None
 
 
+class _StrengthPipe(torch.nn.Module):
+    """What StepEngine needs of a pipe besides ``forward``: the device buffer ``p`` (registered by the subclass) and its host mirror."""
+    _p_cache = (None, None, 1.0)            # (data_ptr, version, value) of the host mirror of `p`
+    _p_pending = None
+
+    def _strength(self):
+        """Host copy of `p`, read (one synchronising read) whenever the buffer was written by someone who did not announce it --
+        construction, ``load_state_dict``, user code.  An owner that updates `p` on the device every few iterations (StepEngine's ADA
+        heuristic) announces the write instead and picks the point at which the new value takes effect, see below."""
+        key = (self.p.data_ptr(), self.p._version)
+        if self._p_cache[:2] != key:
+            self._p_pending = None
+            self._p_cache = key + (float(self.p),)
+        return self._p_cache[2]
+
+    def announce_strength_update(self):
+        """`p` has just been rewritten on the device by the caller: start an asynchronous copy of the new value into pinned memory.
+        The sampler keeps using the previous strength until ``adopt_strength()``."""
+        value = self._strength() if self._p_cache[0] is None else self._p_cache[2]
+        if self.p.device.type != "cuda":
+            self._p_cache = (self.p.data_ptr(), self.p._version, float(self.p))
+            return
+        pinned = torch.empty([], dtype=self.p.dtype, pin_memory=True)
+        pinned.copy_(self.p.detach(), non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.p.device))
+        self._p_pending = (pinned, ev)
+        self._p_cache = (self.p.data_ptr(), self.p._version, value)
+
+    def adopt_strength(self):
+        """Make the announced value current.  Called at a point fixed in the iteration count (one iteration after the update), so the
+        strength every sampler call sees is a function of the iteration alone -- the same on all ranks and from run to run; by then
+        the copy has completed and the event wait returns at once."""
+        pend = getattr(self, "_p_pending", None)
+        if pend is not None:
+            pend[1].synchronize()
+            self._p_cache = self._p_cache[:2] + (float(pend[0]),)
+            self._p_pending = None
+
+
 @augmentations.add_to_registry("sg2_ada")
-class AugmentPipe(torch.nn.Module):
+class AugmentPipe(_StrengthPipe):
     def __init__(self,
         xflip=0, rotate90=0, xint=0, xint_max=0.125,
         scale=0, rotate=0, aniso=0, xfrac=0, scale_std=0.2, rotate_max=1, aniso_std=0.2, xfrac_std=0.125,
@@ -146,41 +201,6 @@ class AugmentPipe(torch.nn.Module):
         self.register_buffer('Hz_fbank', torch.as_tensor(fbank, dtype=torch.float32))
         self._p_cache = (None, None, 1.0)       # (data_ptr, version, value) of the host mirror of `p`
         self._fbank_host = torch.as_tensor(fbank, dtype=torch.float32)
-
-    # -- strength mirror ---------------------------------------------------------------------------------------------
-    def _strength(self):
-        """Host copy of `p`, read (one synchronising read) whenever the buffer was written by someone who did not announce it --
-        construction, ``load_state_dict``, user code.  An owner that updates `p` on the device every few iterations (StepEngine's ADA
-        heuristic) announces the write instead and picks the point at which the new value takes effect, see below."""
-        key = (self.p.data_ptr(), self.p._version)
-        if self._p_cache[:2] != key:
-            self._p_pending = None
-            self._p_cache = key + (float(self.p),)
-        return self._p_cache[2]
-
-    def announce_strength_update(self):
-        """`p` has just been rewritten on the device by the caller: start an asynchronous copy of the new value into pinned memory.
-        The sampler keeps using the previous strength until ``adopt_strength()``."""
-        value = self._strength() if self._p_cache[0] is None else self._p_cache[2]
-        if self.p.device.type != "cuda":
-            self._p_cache = (self.p.data_ptr(), self.p._version, float(self.p))
-            return
-        pinned = torch.empty([], dtype=self.p.dtype, pin_memory=True)
-        pinned.copy_(self.p.detach(), non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(self.p.device))
-        self._p_pending = (pinned, ev)
-        self._p_cache = (self.p.data_ptr(), self.p._version, value)
-
-    def adopt_strength(self):
-        """Make the announced value current.  Called at a point fixed in the iteration count (one iteration after the update), so the
-        strength every sampler call sees is a function of the iteration alone -- the same on all ranks and from run to run; by then
-        the copy has completed and the event wait returns at once."""
-        pend = getattr(self, "_p_pending", None)
-        if pend is not None:
-            pend[1].synchronize()
-            self._p_cache = self._p_cache[:2] + (float(pend[0]),)
-            self._p_pending = None
 
     # -- parameters --------------------------------------------------------------------------------------------------
     def sample(self, batch_size, num_channels, height, width, debug_percentile=None, p=None):
@@ -464,3 +484,75 @@ class AugmentPipe(torch.nn.Module):
         assert isinstance(images, torch.Tensor) and images.ndim == 4
         n, ch, H, W = images.shape
         return self.apply(images, self.sample(n, ch, H, W, debug_percentile=debug_percentile))
+
+
+@augmentations.add_to_registry("diffaug")
+class DiffAugmentPipe(_StrengthPipe):
+    """DiffAugment (Zhao et al., "Differentiable Augmentation for Data-Efficient GAN Training", NeurIPS 2020): colour, translation and
+    cutout, each a group that is applied to a sample with probability `p` (one uniform draw per group and sample) and otherwise replaced
+    by its identity parameters; `p` = 1 is the published behaviour.  The buffer `p` and its host mirror are AugmentPipe's, so
+    ``aug.aug=fixed``, the ADA heuristic, the status line and snapshots work unchanged.  The image work is one fused op
+    (torch_utils/ops/diffaug.py); the parameters are drawn on the host and uploaded as one packed table."""
+
+    def __init__(self, color=0, translation=0, cutout=0, translation_ratio=0.125, cutout_ratio=0.5):
+        super().__init__()
+        self.register_buffer('p', torch.ones([]))       # probability of each enabled group per sample
+        self.color, self.translation, self.cutout = float(color), float(translation), float(cutout)
+        self.translation_ratio, self.cutout_ratio = float(translation_ratio), float(cutout_ratio)
+
+    @staticmethod
+    def cutout_rect(offset, size, extent):
+        """the rows (columns) `clamp(i + offset - size // 2, 0, extent - 1)`, i < size, the published cutout clears: after clamping always
+        the non-empty half-open range this returns (int tensors / ints in, the same out)"""
+        lo = offset - size // 2
+        return torch.clamp(lo, 0, extent - 1), torch.clamp(lo + size - 1, 0, extent - 1) + 1
+
+    def sample(self, batch_size, num_channels, height, width, p=None):
+        """Draw the parameters of one call on the host with torch's CPU generator.  Order of the draws:
+          1. rand([groups enabled, N]): the gates, rows in the order colour, translation, cutout;
+          2. colour enabled:       b = rand(N) - 0.5,  s = rand(N) * 2,  k = rand(N) + 0.5;
+          3. translation enabled:  t_row = randint(-lim_h, lim_h + 1, [N]), then t_col with lim_w;  lim = int(extent * ratio + 0.5);
+          4. cutout enabled:       the row offset = randint(0, H + (1 - size_h % 2), [N]), then the column offset;  size = int(extent * ratio + 0.5).
+        A sample whose gate draw is not below `p` gets the group's identity parameters.  Returns CPU tensors: b, s, k fp32 [N], t int32
+        [N, 2] (row, column), rect int32 [N, 4] (r0, r1, c0, c1; half-open, empty = zeros)."""
+        n, H, W = batch_size, height, width
+        p = float(self._strength() if p is None else p)
+        enabled = [g for g, on in (('color', self.color), ('translation', self.translation), ('cutout', self.cutout)) if on > 0]
+        gates = torch.rand([len(enabled), n]) < p
+        gate = {g: gates[i] for i, g in enumerate(enabled)}
+        out = diffaug_op.identity_params(n)
+        if 'color' in gate:
+            b, s, k = torch.rand([n]) - 0.5, torch.rand([n]) * 2, torch.rand([n]) + 0.5
+            out['b'] = torch.where(gate['color'], b, out['b'])
+            out['s'] = torch.where(gate['color'], s, out['s'])
+            out['k'] = torch.where(gate['color'], k, out['k'])
+        if 'translation' in gate:
+            lim_h, lim_w = int(H * self.translation_ratio + 0.5), int(W * self.translation_ratio + 0.5)
+            t_row = torch.randint(-lim_h, lim_h + 1, [n])
+            t_col = torch.randint(-lim_w, lim_w + 1, [n])
+            t = torch.stack([t_row, t_col], dim=1).to(torch.int32)
+            out['t'] = torch.where(gate['translation'].unsqueeze(1), t, out['t'])
+        if 'cutout' in gate:
+            size_h, size_w = int(H * self.cutout_ratio + 0.5), int(W * self.cutout_ratio + 0.5)
+            o_row = torch.randint(0, H + (1 - size_h % 2), [n])
+            o_col = torch.randint(0, W + (1 - size_w % 2), [n])
+            r0, r1 = self.cutout_rect(o_row, size_h, H)
+            c0, c1 = self.cutout_rect(o_col, size_w, W)
+            rect = torch.stack([r0, r1, c0, c1], dim=1).to(torch.int32)
+            out['rect'] = torch.where(gate['cutout'].unsqueeze(1), rect, out['rect'])
+        return out
+
+    def apply(self, images, params):
+        """Run the transforms `params` (from sample(), or any dict torch_utils/ops/diffaug.py accepts) describes on `images` [N, C, H, W]:
+        one upload of the packed table, then the fused op."""
+        table = diffaug_op.pack(params) if isinstance(params, dict) else params
+        if table.device != images.device:
+            if images.device.type == "cuda":    # pinned staging buffer: the upload queues behind the running kernels instead of draining the stream
+                table = table.pin_memory()
+            table = table.to(images.device, non_blocking=True)
+        return diffaug_op.diffaug(images.contiguous(), table)
+
+    def forward(self, images):
+        assert isinstance(images, torch.Tensor) and images.ndim == 4
+        n, ch, H, W = images.shape
+        return self.apply(images, self.sample(n, ch, H, W))

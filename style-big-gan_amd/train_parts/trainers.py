@@ -641,8 +641,9 @@ class BaseTrainer:
     def _augment_arguments(config):
         """aug.{aug, p, target, augpipe} -> StepEngine keywords (reference :295-335).  The reference looks `aug.augpipe` ('bgc', ...) up
         in a registry that only holds the class name 'sg2_ada' (:335) and fails; the names mean the subsets of
-        stylegan2ada/train.py:271-283, which is what is resolved here."""
-        from .augmentations import augpipe_specs
+        stylegan2ada/train.py:271-283, which is what is resolved here.  Every registered pipe (`aug.aug_type`) has its own table of
+        policy names: 'sg2_ada' those subsets, 'diffaug' the combinations of color / translation / cutout."""
+        from .augmentations import augmentations, policy_tables
         aug = config.aug
         out = dict(augment_kwargs=None, augment_type=aug.get("aug_type", "sg2_ada"), augment_p=0.0, ada_target=None, ada_interval=4, ada_kimg=500)
         if aug.aug == "ada":
@@ -665,8 +666,11 @@ class BaseTrainer:
                 raise ValueError("--target must be between 0 and 1")
             out["ada_target"] = float(aug.target)
         if aug.aug != "noaug":
+            if out["augment_type"] not in policy_tables:
+                raise ValueError(f"aug.aug_type={out['augment_type']} not in {sorted(augmentations.classes)}")
+            augpipe_specs = policy_tables[out["augment_type"]]
             if aug.augpipe not in augpipe_specs:
-                raise ValueError(f"aug.augpipe={aug.augpipe} not in {sorted(augpipe_specs)}")
+                raise ValueError(f"aug.augpipe={aug.augpipe} not in {sorted(augpipe_specs)} (the policies of aug.aug_type={out['augment_type']})")
             base = config.get("augpipe_specs", {}).get(out["augment_type"], {})        # constructor arguments (std-devs, ranges) from the config
             out["augment_kwargs"] = {**{k: v for k, v in dict(base).items() if k not in ("args", "kwargs")}, **augpipe_specs[aug.augpipe]}
         return out
