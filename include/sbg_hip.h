@@ -501,6 +501,13 @@ int sbg_u8_resample_v(const uint8_t* src, int64_t src_img_stride, int64_t src_pi
  *   sbg_knn_kth_radius:  out[i] (fp16 [R]) = the (k + 1)-th smallest d(rows[i], manifold[j]) over j -- `dist.kthvalue(nhood_size + 1)`;
  *                        when `rows` is a slice of `manifold` the self-distance takes part, as in the reference.
  *   sbg_knn_in_manifold: out[i] (uint8 [P]) = 1 when d(probes[i], manifold[j]) <= radius[j] (fp16 [C]) for some j -- `(dist <= kth).any(dim=1)`.
+ *   sbg_knn_probe:       count[i] (int32 [P]) = the number of j with d(probes[i], manifold[j]) <= radius[j], nearest[i] (fp16 [P]) =
+ *                        min_j d(probes[i], manifold[j]) (the minimum is taken on d2 and rounded once): the pass behind density and
+ *                        coverage (Naeem et al., "Reliable Fidelity and Diversity Metrics for Generative Models", ICML 2020), whose
+ *                        `count > 0` is sbg_knn_in_manifold's flag.  Comparisons are `<=` as above; the published code compares with
+ *                        `<`, which differs on exact ties only.  Argument rules of sbg_knn_in_manifold; workspace of
+ *                        sbg_knn_probe_workspace(P, C) bytes: up16(4 P) + up16(4 C) + (runs > 1 ? 8 P runs : 0), one {int32 count,
+ *                        float d2} pair per (run, row).
  * k + 1 <= 8, C >= k + 1, F a multiple of 8, features and workspace 16-byte aligned; anything else is an error.  The manifold columns
  * are split over workgroups when the rows alone do not fill the chip; partial results go through `workspace`
  * (sbg_knn_workspace(R, C, k, membership) bytes, -1 for unsupported sizes: the norms, R + C floats, and per (row, run) a list of 4 | 8
@@ -510,6 +517,9 @@ int64_t sbg_knn_workspace(int R, int C, int k, int membership);
 int sbg_knn_kth_radius(const void* rows, const void* manifold, int R, int C, int64_t F, int k, void* out, void* workspace, sbg_stream_t stream);
 int sbg_knn_in_manifold(const void* probes, const void* manifold, const void* radius, int P, int C, int64_t F, uint8_t* out, void* workspace,
                         sbg_stream_t stream);
+int64_t sbg_knn_probe_workspace(int P, int C);
+int sbg_knn_probe(const void* probes, const void* manifold, const void* radius, int P, int C, int64_t F, int32_t* count, void* nearest,
+                  void* workspace, sbg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * End of a training phase over a flat fp32 gradient bucket: the reference's per-parameter loop `misc.nan_to_num(param.grad, nan=0,
@@ -588,7 +598,7 @@ enum sbg_kernel_kind {
     SBG_K_RESAMPLE = 21,        /* dims[0] = variant: 0 h (N, rows, in_w, out_w, C, dims[6] = strip), 1 v (N, row_bytes, in_h, out_h, ksize,
                                  * dims[6] = 1 dword / 2 byte loads) */
     SBG_K_PR = 22,              /* dims[0] = variant: 0 single / 1 split (the tile kernel, one / several column runs per row tile), 2 merge,
-                                 * 3 norms; then R, C, F, k, runs, dims[6] = 0 radius / 1 membership */
+                                 * 3 norms; then R, C, F, k, runs, dims[6] = 0 radius / 1 membership / 2 probe */
     SBG_K_GRAD_FINISH = 23,     /* dims[0] = variant: 0 sweep (records, n clipped to INT32_MAX, dims[3] = 1 when the scale is applied),
                                  * 1 merge (records) */
     SBG_K_RESIDENT = 24,        /* dims = B, C, H, W, out_f32, 0, dims[6] = 1 dword path (4 pixels per work-item) / 2 byte path */

@@ -7,7 +7,8 @@ the snapshot (the reference's run-dir rule, :170-176).  Differences:
   the data set options come from that config too (snapshots of this build hold no ``training_set_kwargs``), through the helper the
   trainer itself uses; ``--data`` overrides the path, ``--mirror`` the flips, and the labels follow ``G.c_dim``;
 * detectors are local: ``--detector`` names a TorchScript file or a directory holding the reference's file names; nothing is fetched;
-* on a GPU the precision / recall metrics run on the fused k-NN kernels (metrics/scores.py, ``precision_recall_fused``);
+* on a GPU the precision / recall metrics run on the fused k-NN kernels (metrics/scores.py, ``precision_recall_fused``), and so does
+  ``prdc50k5_full`` (precision / recall / density / coverage, ``prdc_fused``), a metric the reference does not have;
 * ``calc_metrics()`` is a function of a generator for callers that already hold one.
 
     python -m style_big_gan_amd.calc_metrics exp.config_dir=<dir> exp.config=<file.yaml> --snapshot=<network-snapshot-*.pt> \\

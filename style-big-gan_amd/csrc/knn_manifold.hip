@@ -3,21 +3,26 @@
 // matrix never leaves the chip.  Features are fp16 [*, F], dense rows.
 //   kth_radius:   out[i] = (k + 1)-th smallest of d(rows[i], manifold[j]) over j            (fp16)
 //   in_manifold:  out[i] = any_j d(probes[i], manifold[j]) <= radius[j]                      (uint8)
+//   probe:        count[i] = |{ j : d(probes[i], manifold[j]) <= radius[j] }|  (int32),  nearest[i] = min_j d(probes[i], manifold[j])  (fp16)
+//                 -- the pass behind density / coverage (Naeem et al., ICML 2020) and, as count > 0, behind precision / recall
 // Arithmetic: n(x) = sum x_f^2 and s(x, y) = sum x_f y_f are fp32 sums of fp16 products; d2 = max((n(x) + n(y)) - 2 s, 0) in fp32;
-// d = fp16_rn(sqrt_f32(d2)).  Rounding is monotone, so the radius kernel selects on d2 and rounds the selected value once.
+// d = fp16_rn(sqrt_f32(d2)).  Rounding is monotone, so the radius kernel selects on d2 (and the probe pass takes its minimum on d2) and
+// rounds the selected value once.
 //
 // Launches: a norm pass (one wave per row), the tile kernel, and -- when the manifold columns are split over workgroups -- a merge.
 // Tile kernel: workgroup = 256 lanes = 4 waves, tile 128 manifold points (MFMA A operand, rows of the accumulator = registers of a
 // lane) x 128 query rows (B operand, accumulator column = lane & 15), K-step 64, v_mfma_f32_16x16x32_f16.  So a lane holds, for each
 // of 4 query rows, 16 manifold candidates per tile, and reduces them into per-query registers: a sorted list of the KL smallest d2
-// (radius) or a flag (membership).  Staging is global -> VGPR -> LDS in full 128-B lines (8 lanes per row), issue early / write late,
-// two LDS stages, one barrier per K-step.  LDS image per operand: [k-group 0..7][130 cells of 16 B]: the 2-cell pad makes the 16 cells
-// a quarter-wave writes (2 rows x 8 k-groups) distinct mod 16, and a fragment read touches 16 consecutive cells: both conflict-free.
+// (radius), a flag (membership) or a count and a running minimum (probe).  Staging is global -> VGPR -> LDS in full 128-B lines
+// (8 lanes per row), issue early / write late, two LDS stages, one barrier per K-step.  LDS image per operand: [k-group 0..7][130
+// cells of 16 B]: the 2-cell pad makes the 16 cells a quarter-wave writes (2 rows x 8 k-groups) distinct mod 16, and a fragment read
+// touches 16 consecutive cells: both conflict-free.
 // A workgroup owns one query tile and a contiguous run of manifold tiles; at the end the lists of the 8 lane groups that share a query
 // are merged through LDS.  With one run per query tile the result is written directly (variant `single`); otherwise every run writes
-// its partial list / flag to the workspace and a second launch merges the runs in index order (`split` + `merge`).  The k smallest of
-// a multiset and an OR do not depend on the order, and there are no atomics: two runs give the same bits.
-// Launch-log key: kind SBG_K_PR, dims = {variant (0 single, 1 split, 2 merge, 3 norms), R, C, F, k, runs, 0 radius / 1 membership}.
+// its partial list / flag / {count, minimum} pair to the workspace and a second launch merges the runs in index order (`split` +
+// `merge`).  The k smallest of a multiset, an OR, an integer sum and a minimum do not depend on the order, and there are no atomics: two
+// runs give the same bits.
+// Launch-log key: kind SBG_K_PR, dims = {variant (0 single, 1 split, 2 merge, 3 norms), R, C, F, k, runs, 0 radius / 1 membership / 2 probe}.
 #include "conv_common.h"
 #include "reduce.h"
 
@@ -26,6 +31,7 @@ using namespace sbgconv;
 namespace {
 
 constexpr int kPrSingle = 0, kPrSplit = 1, kPrMerge = 2, kPrNorms = 3;
+constexpr int kRadius = 0, kMember = 1, kProbe = 2;       // what the tile kernel reduces a query row's distances to (dims[6] of a record)
 
 constexpr int BT = 128;                     // tile side: manifold points and query rows
 constexpr int BK = 64;                      // K-step
@@ -41,8 +47,8 @@ constexpr int kTargetGroups = 512;          // workgroups to aim for: 256 CUs x 
 struct KnnArgs {
     const unsigned short* q; const unsigned short* m;     // query rows [R, F], manifold [C, F]
     const float* nq; const float* nm;                      // their squared norms
-    const unsigned short* radius;                          // membership: fp16 [C]
-    void* out; void* part;
+    const unsigned short* radius;                          // membership and probe: fp16 [C]
+    void* out; void* nearest = nullptr; void* part;        // nearest: the probe's second output, fp16 [R]
     int R, C, F, k, runs, ctiles, tiles_per_run;
 };
 
@@ -80,9 +86,12 @@ __device__ __forceinline__ float dist2(float nx, float ny, float s)
 
 __device__ __forceinline__ float dist_f16(float d2) { return (float)(_Float16)sqrtf(d2); }
 
-template <int KL, bool MEMBER>
-__global__ __launch_bounds__(256) void knn_tile_kernel(KnnArgs p)
+struct ProbePart { int count; float d2; };                 // a run's share of a probe row: balls that hold it, smallest d2
+
+template <int KL, int MODE>
+__device__ __forceinline__ void knn_tile_body(const KnnArgs& p)
 {
+    constexpr bool MEMBER = MODE == kMember, PROBE = MODE == kProbe;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float* const prm = reinterpret_cast<float*>(smem + PARAM_OFF);          // [parity][0: norm, 1: radius][BT]
 
@@ -110,10 +119,12 @@ __global__ __launch_bounds__(256) void knn_tile_kernel(KnnArgs p)
     for (int j = 0; j < 4; j++) { const int r = q0 + wp + 16 * j + fr; nqv[j] = r < p.R ? p.nq[r] : 0.f; }
 
     float L[4][KL];
-    int inside[4];
+    int inside[4];                      // membership: the flag; probe: the count
+    float nearest[4];
 #pragma unroll
     for (int j = 0; j < 4; j++) {
         inside[j] = 0;
+        nearest[j] = __builtin_inff();
 #pragma unroll
         for (int t = 0; t < KL; t++) L[j][t] = __builtin_inff();
     }
@@ -131,7 +142,7 @@ __global__ __launch_bounds__(256) void knn_tile_kernel(KnnArgs p)
         if (tid < BT) {       // a padded column is at +inf (and has a negative radius): read after the K loop's barriers
             const int c = c0 + tid;
             prm[(par * 2 + 0) * BT + tid] = c < p.C ? p.nm[c] : __builtin_inff();
-            if (MEMBER) prm[(par * 2 + 1) * BT + tid] = c < p.C ? f16_bits_to_f32(p.radius[c]) : -1.f;
+            if (MEMBER || PROBE) prm[(par * 2 + 1) * BT + tid] = c < p.C ? f16_bits_to_f32(p.radius[c]) : -1.f;
         }
 
         short8_t ra[4], rb[4];
@@ -197,11 +208,12 @@ __global__ __launch_bounds__(256) void knn_tile_kernel(KnnArgs p)
             for (int e = 0; e < 4; e++) {
                 const int col = wc + 16 * i + 4 * fg + e;
                 const float nmv = prm[(par * 2 + 0) * BT + col];
-                const float rv = MEMBER ? prm[(par * 2 + 1) * BT + col] : 0.f;
+                const float rv = (MEMBER || PROBE) ? prm[(par * 2 + 1) * BT + col] : 0.f;
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
                     const float d2 = dist2(nqv[j], nmv, acc[i][j][e]);
                     if (MEMBER) inside[j] |= (dist_f16(d2) <= rv) ? 1 : 0;
+                    else if (PROBE) { inside[j] += (dist_f16(d2) <= rv) ? 1 : 0; nearest[j] = fminf(nearest[j], d2); }
                     else list_insert<KL>(L[j], d2);
                 }
             }
@@ -224,6 +236,28 @@ __global__ __launch_bounds__(256) void knn_tile_kernel(KnnArgs p)
             const unsigned char f = (unsigned char)((fl[tid] | fl[BT + tid]) != 0);
             if (p.runs == 1) reinterpret_cast<unsigned char*>(p.out)[q] = f;
             else reinterpret_cast<unsigned char*>(p.part)[(int64_t)run * p.R + q] = f;
+        }
+    } else if (PROBE) {
+        int* cn = reinterpret_cast<int*>(smem);                  // [manifold wave][BT] counts, then [manifold wave][BT] minima
+        float* mn = reinterpret_cast<float*>(smem) + 2 * BT;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            int c = inside[j];
+            float v = nearest[j];
+            c += __shfl_xor(c, 16, 64); v = fminf(v, __shfl_xor(v, 16, 64));
+            c += __shfl_xor(c, 32, 64); v = fminf(v, __shfl_xor(v, 32, 64));
+            if (fg == 0) { cn[(wave >> 1) * BT + wp + 16 * j + fr] = c; mn[(wave >> 1) * BT + wp + 16 * j + fr] = v; }
+        }
+        __syncthreads();
+        if (tid < BT && q < p.R) {
+            const int c = cn[tid] + cn[BT + tid];
+            const float v = fminf(mn[tid], mn[BT + tid]);
+            if (p.runs == 1) {
+                reinterpret_cast<int*>(p.out)[q] = c;
+                reinterpret_cast<unsigned short*>(p.nearest)[q] = f32_to_f16_bits(sqrtf(v));
+            } else {
+                reinterpret_cast<ProbePart*>(p.part)[(int64_t)run * p.R + q] = ProbePart{c, v};
+            }
         }
     } else {
         constexpr int QS = 8 * KL + 1;                           // odd stride: the merging lanes hit distinct banks
@@ -253,6 +287,11 @@ __global__ __launch_bounds__(256) void knn_tile_kernel(KnnArgs p)
     }
 }
 
+template <int KL, bool MEMBER>
+__global__ __launch_bounds__(256) void knn_tile_kernel(KnnArgs p) { knn_tile_body<KL, MEMBER ? kMember : kRadius>(p); }
+
+__global__ __launch_bounds__(256) void knn_probe_tile_kernel(KnnArgs p) { knn_tile_body<4, kProbe>(p); }
+
 // Second stage of the split variant: one work-item per query row walks the runs in index order.
 template <int KL>
 __global__ __launch_bounds__(256) void knn_merge_radius_kernel(const float* __restrict__ part, unsigned short* __restrict__ out, int R, int runs, int k)
@@ -279,13 +318,25 @@ __global__ __launch_bounds__(256) void knn_merge_member_kernel(const unsigned ch
     out[q] = f;
 }
 
+__global__ __launch_bounds__(256) void knn_merge_probe_kernel(const ProbePart* __restrict__ part, int* __restrict__ count, unsigned short* __restrict__ nearest,
+                                                              int R, int runs)
+{
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= R) return;
+    int c = 0;
+    float v = __builtin_inff();
+    for (int s = 0; s < runs; s++) { const ProbePart t = part[(int64_t)s * R + q]; c += t.count; v = fminf(v, t.d2); }
+    count[q] = c;
+    nearest[q] = f32_to_f16_bits(sqrtf(v));
+}
+
 struct KnnPlan { int rtiles, ctiles, tiles_per_run, runs; int64_t nq_off, nm_off, part_off, bytes; };
 
 int list_len(int k) { return k + 1 <= 4 ? 4 : 8; }
 
 // Runs per query tile: enough workgroups to fill the chip twice when the query tiles alone do not.  A function of the shape only, so
 // the workspace query and the launch agree and a result does not depend on the device it ran on.
-bool knn_plan(int R, int C, int k, bool member, KnnPlan& pl)
+bool knn_plan(int R, int C, int k, int mode, KnnPlan& pl)
 {
     if (R < 1 || C < 1 || k < 0 || k + 1 > kMaxK1 || R > (1 << 24) || C > (1 << 24)) return false;
     pl.rtiles = (R + BT - 1) / BT;
@@ -298,12 +349,15 @@ bool knn_plan(int R, int C, int k, bool member, KnnPlan& pl)
     pl.nq_off = 0;
     pl.nm_off = up16(4 * (int64_t)R);
     pl.part_off = pl.nm_off + up16(4 * (int64_t)C);
-    // partial results of the runs: a list of floats per (row, run) for the radius, one byte per (run, row) for the membership
-    pl.bytes = pl.part_off + (pl.runs > 1 ? (member ? up16((int64_t)R * pl.runs) : 4 * (int64_t)R * pl.runs * list_len(k)) : 0);
+    // partial results of the runs: a list of floats per (row, run) for the radius, one byte per (run, row) for the membership, one
+    // ProbePart per (run, row) for the probe
+    const int64_t part = mode == kMember ? up16((int64_t)R * pl.runs) : mode == kProbe ? (int64_t)sizeof(ProbePart) * R * pl.runs
+                                                                                       : 4 * (int64_t)R * pl.runs * list_len(k);
+    pl.bytes = pl.part_off + (pl.runs > 1 ? part : 0);
     return true;
 }
 
-int knn_check(const char* what, const void* q, const void* m, const void* out, const void* ws, int R, int C, int64_t F, int k, bool member, KnnPlan& pl)
+int knn_check(const char* what, const void* q, const void* m, const void* out, const void* ws, int R, int C, int64_t F, int k, int mode, KnnPlan& pl)
 {
     SBG_CHECK(q && m && out && ws, "%s: null pointer", what);
     SBG_CHECK(k >= 0 && k + 1 <= kMaxK1, "%s: k + 1 = %d neighbours, at most %d are supported", what, k + 1, kMaxK1);
@@ -311,7 +365,7 @@ int knn_check(const char* what, const void* q, const void* m, const void* out, c
     SBG_CHECK(C >= k + 1, "%s: the manifold has %d points, the (k + 1)-th neighbour needs %d", what, C, k + 1);
     SBG_CHECK(F >= 8 && F % 8 == 0 && F <= (1 << 24), "%s: the feature width %lld must be a multiple of 8 (16-byte pieces) in [8, 2^24]", what, (long long)F);
     SBG_CHECK(sbg_aligned16(q) && sbg_aligned16(m) && sbg_aligned16(ws), "%s: features and workspace must be 16-byte aligned", what);
-    SBG_CHECK(knn_plan(R, C, k, member, pl), "%s: bad sizes", what);
+    SBG_CHECK(knn_plan(R, C, k, mode, pl), "%s: bad sizes", what);
     return SBG_OK;
 }
 
@@ -323,25 +377,26 @@ int knn_norms(const unsigned short* x, float* n, int rows, int F, hipStream_t s)
     return SBG_OK;
 }
 
-template <int KL, bool MEMBER>
+template <int KL, int MODE>
 int knn_launch_tiles(const KnnArgs& a, const KnnPlan& pl, hipStream_t s)
 {
-    if (!SBG_RAISE_LDS_ONCE((knn_tile_kernel<KL, MEMBER>), LDS_BYTES))
+    constexpr auto kernel = MODE == kProbe ? knn_probe_tile_kernel : knn_tile_kernel<KL, MODE == kMember>;
+    if (!SBG_RAISE_LDS_ONCE(kernel, LDS_BYTES))
         return sbg_fail(SBG_ERR_LAUNCH, "knn_manifold: cannot raise the dynamic LDS limit to %d bytes", LDS_BYTES);
     SbgProfScope prof(s, SBG_K_PR, 2.0 * a.R * (double)a.C * a.F, 2.0 * ((double)a.R + a.C) * a.F,
-                      {pl.runs == 1 ? kPrSingle : kPrSplit, a.R, a.C, a.F, a.k, pl.runs, MEMBER ? 1 : 0});
-    SBG_LAUNCH((knn_tile_kernel<KL, MEMBER>), dim3((unsigned)(pl.rtiles * pl.runs)), dim3(256), LDS_BYTES, s, a);
+                      {pl.runs == 1 ? kPrSingle : kPrSplit, a.R, a.C, a.F, a.k, pl.runs, MODE});
+    SBG_LAUNCH(kernel, dim3((unsigned)(pl.rtiles * pl.runs)), dim3(256), LDS_BYTES, s, a);
     SBG_HIP_LAUNCH_CHECK();
     return SBG_OK;
 }
 
-// What the two entry points share: argument checks, the plan, the norm passes and the tile launch.  On SBG_OK with pl.runs > 1 the
+// What the entry points share: argument checks, the plan, the norm passes and the tile launch.  On SBG_OK with pl.runs > 1 the
 // caller launches its merge over a.part.
-template <bool MEMBER>
+template <int MODE>
 int knn_run(const char* what, const void* q, const void* m, const void* radius, int R, int C, int64_t F, int k, void* out, void* workspace,
             hipStream_t s, KnnArgs& a, KnnPlan& pl)
 {
-    const int rc = knn_check(what, q, m, out, workspace, R, C, F, k, MEMBER, pl);
+    const int rc = knn_check(what, q, m, out, workspace, R, C, F, k, MODE, pl);
     if (rc != SBG_OK) return rc;
     char* ws = (char*)workspace;
     a.q = (const unsigned short*)q; a.m = (const unsigned short*)m;
@@ -352,8 +407,8 @@ int knn_run(const char* what, const void* q, const void* m, const void* radius, 
     if (st != SBG_OK) return st;
     st = knn_norms(a.m, (float*)(ws + pl.nm_off), C, a.F, s);
     if (st != SBG_OK) return st;
-    if (MEMBER) return knn_launch_tiles<4, true>(a, pl, s);
-    return list_len(k) == 4 ? knn_launch_tiles<4, false>(a, pl, s) : knn_launch_tiles<8, false>(a, pl, s);
+    if (MODE != kRadius) return knn_launch_tiles<4, MODE>(a, pl, s);
+    return list_len(k) == 4 ? knn_launch_tiles<4, kRadius>(a, pl, s) : knn_launch_tiles<8, kRadius>(a, pl, s);
 }
 
 } // namespace
@@ -361,7 +416,7 @@ int knn_run(const char* what, const void* q, const void* m, const void* radius, 
 extern "C" int64_t sbg_knn_workspace(int R, int C, int k, int membership)
 {
     KnnPlan pl;
-    if (!knn_plan(R, C, membership ? 0 : k, membership != 0, pl)) return -1;
+    if (!knn_plan(R, C, membership ? 0 : k, membership ? kMember : kRadius, pl)) return -1;
     return pl.bytes;
 }
 
@@ -369,7 +424,7 @@ extern "C" int sbg_knn_kth_radius(const void* rows, const void* manifold, int R,
 {
     hipStream_t s = (hipStream_t)stream;
     KnnArgs a; KnnPlan pl;
-    const int st = knn_run<false>("knn_kth_radius", rows, manifold, nullptr, R, C, F, k, out, workspace, s, a, pl);
+    const int st = knn_run<kRadius>("knn_kth_radius", rows, manifold, nullptr, R, C, F, k, out, workspace, s, a, pl);
     if (st != SBG_OK) return st;
     if (pl.runs > 1) {
         const int KL = list_len(k);
@@ -387,11 +442,36 @@ extern "C" int sbg_knn_in_manifold(const void* probes, const void* manifold, con
     SBG_CHECK(radius, "knn_in_manifold: null pointer");
     hipStream_t s = (hipStream_t)stream;
     KnnArgs a; KnnPlan pl;
-    const int st = knn_run<true>("knn_in_manifold", probes, manifold, radius, P, C, F, 0, out, workspace, s, a, pl);
+    const int st = knn_run<kMember>("knn_in_manifold", probes, manifold, radius, P, C, F, 0, out, workspace, s, a, pl);
     if (st != SBG_OK) return st;
     if (pl.runs > 1) {
         SbgProfScope prof(s, SBG_K_PR, 0.0, (double)P * pl.runs + P, {kPrMerge, P, C, a.F, 0, pl.runs, 1});
         SBG_LAUNCH(knn_merge_member_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, (const unsigned char*)a.part, (unsigned char*)out, P, pl.runs);
+        SBG_HIP_LAUNCH_CHECK();
+    }
+    return SBG_OK;
+}
+
+extern "C" int64_t sbg_knn_probe_workspace(int P, int C)
+{
+    KnnPlan pl;
+    if (!knn_plan(P, C, 0, kProbe, pl)) return -1;
+    return pl.bytes;
+}
+
+extern "C" int sbg_knn_probe(const void* probes, const void* manifold, const void* radius, int P, int C, int64_t F, int32_t* count, void* nearest,
+                             void* workspace, sbg_stream_t stream)
+{
+    SBG_CHECK(radius && nearest, "knn_probe: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    KnnArgs a; KnnPlan pl;
+    a.nearest = nearest;
+    const int st = knn_run<kProbe>("knn_probe", probes, manifold, radius, P, C, F, 0, count, workspace, s, a, pl);
+    if (st != SBG_OK) return st;
+    if (pl.runs > 1) {
+        SbgProfScope prof(s, SBG_K_PR, 0.0, 8.0 * P * (double)pl.runs + 6.0 * P, {kPrMerge, P, C, a.F, 0, pl.runs, kProbe});
+        SBG_LAUNCH(knn_merge_probe_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, (const ProbePart*)a.part, (int*)count, (unsigned short*)nearest,
+                   P, pl.runs);
         SBG_HIP_LAUNCH_CHECK();
     }
     return SBG_OK;

@@ -2,7 +2,8 @@
 ``is_valid_metric``, ``list_valid_metrics``, ``calc_metric(metric, dataset_name, **MetricOptions kwargs)`` (:39-61: compute, broadcast
 rank 0's numbers, wrap with timing metadata) and ``report_metric(result_dict, run_dir, snapshot_pkl)`` (:65-76: one JSON line to stdout
 and to ``metric-<name>.jsonl``).  Metric names and their sample counts are the reference's (:81-150), the perceptual-path-length family
-(:101, :133-150) included: its LPIPS network is the local ``vgg16.pt`` detector (or a callable stand-in), see perceptual_path_length.py."""
+(:101, :133-150) included: its LPIPS network is the local ``vgg16.pt`` detector (or a callable stand-in), see perceptual_path_length.py.
+``prdc50k5_full`` (density / coverage next to precision / recall, scores.prdc_fused) is this build's own."""
 import json
 import os
 import time
@@ -79,6 +80,14 @@ def pr50k3_full(opts, dataset_name='image_folder'):
     _full_dataset(opts)
     precision, recall = scores.compute_pr(opts, dataset_name=dataset_name, max_real=200000, num_gen=50000, nhood_size=3, row_batch_size=10000, col_batch_size=10000)
     return dict(pr50k3_full_precision=precision, pr50k3_full_recall=recall)
+
+
+@register_metric
+def prdc50k5_full(opts, dataset_name='image_folder'):
+    """precision / recall / density / coverage at k = 5, the published setting of Naeem et al. (ICML 2020); not in the reference"""
+    _full_dataset(opts)
+    precision, recall, density, coverage = scores.compute_prdc(opts, dataset_name=dataset_name, max_real=200000, num_gen=50000, nhood_size=5, row_batch_size=10000)
+    return dict(prdc50k5_full_precision=precision, prdc50k5_full_recall=recall, prdc50k5_full_density=density, prdc50k5_full_coverage=coverage)
 
 
 @register_metric

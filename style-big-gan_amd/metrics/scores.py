@@ -1,5 +1,6 @@
-"""The scores computed from feature statistics: Frechet distance (FID), kernel distance (KID), Inception score (IS) and improved
-precision / recall (PR).  Arithmetic of the reference's ``stylegan2ada/metrics/{frechet_inception_distance, kernel_inception_distance,
+"""The scores computed from feature statistics: Frechet distance (FID), kernel distance (KID), Inception score (IS), improved
+precision / recall (PR) and, beyond the reference, density / coverage (PRDC: Naeem et al., "Reliable Fidelity and Diversity Metrics
+for Generative Models", ICML 2020).  Arithmetic of the reference's ``stylegan2ada/metrics/{frechet_inception_distance, kernel_inception_distance,
 inception_score, precision_recall}.py``; each function cites the lines it follows.  Detector names are the reference's file names; the
 files themselves are never fetched (see metric_utils.get_feature_detector)."""
 import numpy as np
@@ -158,3 +159,61 @@ def compute_pr(opts, max_real, num_gen, nhood_size, row_batch_size, col_batch_si
     if torch.device(opts.device).type == 'cuda':      # fused HIP kernels; the CPU keeps the reference's cdist / kthvalue structure
         return precision_recall_fused(real, gen, nhood_size, row_batch_size, opts.num_gpus, opts.rank)
     return precision_recall(real, gen, nhood_size, row_batch_size, col_batch_size, opts.num_gpus, opts.rank)
+
+
+def _radii_fused(features, nhood_size, row_batch_size, num_gpus, rank):
+    """k-NN radii of all rows of `features` on every rank: each computes a contiguous share, one all_gather exchanges them"""
+    n = features.shape[0]
+    lo, hi = _rank_share(n, num_gpus, rank)
+    kth = [knn_manifold.kth_radius(batch, features, nhood_size) for batch in features[lo:hi].split(row_batch_size)]
+    kth = torch.cat(kth) if kth else torch.empty([0], dtype=torch.float16, device=features.device)
+    if num_gpus > 1:        # shares differ by at most one row: pad to the largest, gather once, cut the pads
+        longest = -(-n // num_gpus)
+        parts = [torch.empty([longest], dtype=kth.dtype, device=kth.device) for _ in range(num_gpus)]
+        torch.distributed.all_gather(parts, torch.nn.functional.pad(kth, [0, longest - kth.shape[0]]))
+        kth = torch.cat([part[:b - a] for part, (a, b) in zip(parts, (_rank_share(n, num_gpus, r) for r in range(num_gpus)))])
+    return kth
+
+
+def prdc_fused(real_features, gen_features, nhood_size, row_batch_size, num_gpus=1, rank=0):
+    """(precision, recall, density, coverage) in the four sweeps that `precision_recall_fused` takes for the first two.  With
+    r_X, r_Y the k-NN radii of the real features X [N, F] and the generated ones Y [M, F] (self-distance included), count and nearest
+    of `knn_manifold.probe`, (cA, _) = probe(Y, X, r_X) and (cB, nB) = probe(X, Y, r_Y):
+        precision = mean(cA > 0)         recall   = mean(cB > 0)         as `precision_recall_fused` for this k, bit for bit
+        density   = sum(cA) / (k M)      coverage = mean(nB <= r_X)      the nearest generated point of real i lies within its radius
+    All comparisons are `<=` on the fp16 distances, the convention of `in_manifold`; the published code compares with `<`, which
+    differs on exact ties only.  Ranks as in `precision_recall_fused`: every rank holds all features, computes the radii of a
+    contiguous share (one all_gather per direction) and probes a contiguous share of the rows; the three integer totals of a
+    direction (rows with count > 0, sum of counts, rows covered) are int64 and go through one all_reduce; nothing else reaches the
+    host, and every rank returns the numbers."""
+    assert 0 <= rank < num_gpus
+    radius_real = _radii_fused(real_features, nhood_size, row_batch_size, num_gpus, rank)
+    radius_gen = _radii_fused(gen_features, nhood_size, row_batch_size, num_gpus, rank)
+    totals = []
+    for probes, manifold, radius, own_radius in [(gen_features, real_features, radius_real, None), (real_features, gen_features, radius_gen, radius_real)]:
+        lo, hi = _rank_share(probes.shape[0], num_gpus, rank)
+        total = torch.zeros([3], dtype=torch.int64, device=probes.device)
+        for start in range(lo, hi, row_batch_size):
+            stop = min(start + row_batch_size, hi)
+            count, nearest = knn_manifold.probe(probes[start:stop], manifold, radius)
+            total[0] += (count > 0).sum()
+            total[1] += count.sum(dtype=torch.int64)
+            if own_radius is not None:
+                total[2] += (nearest <= own_radius[start:stop]).sum()
+        if num_gpus > 1:
+            torch.distributed.all_reduce(total)
+        totals.append(total.tolist())
+    (in_real, balls, _), (in_gen, _, covered) = totals
+    num_real, num_gen = real_features.shape[0], gen_features.shape[0]
+    precision, recall = (float(np.float32(hits) / np.float32(n)) for hits, n in [(in_real, num_gen), (in_gen, num_real)])   # the fp32 mean of a 0 / 1 vector
+    return precision, recall, balls / (nhood_size * num_gen), covered / num_real
+
+
+def compute_prdc(opts, max_real, num_gen, nhood_size, row_batch_size, dataset_name='image_folder'):
+    kw = metric_utils.detector_call_kwargs(opts, VGG16, dict(return_features=True))
+    half = torch.float16 if torch.device(opts.device).type == 'cuda' else torch.float32
+    real = metric_utils.compute_feature_stats_for_dataset(opts=opts, dataset_name=dataset_name, detector_url=VGG16, detector_kwargs=kw, rel_lo=0, rel_hi=0,
+                                                          capture_all=True, max_items=max_real).get_all_torch().to(half).to(opts.device)
+    gen = metric_utils.compute_feature_stats_for_generator(opts=opts, dataset_name=dataset_name, detector_url=VGG16, detector_kwargs=kw, rel_lo=0, rel_hi=1,
+                                                           capture_all=True, max_items=num_gen).get_all_torch().to(half).to(opts.device)
+    return prdc_fused(real, gen, nhood_size, row_batch_size, opts.num_gpus, opts.rank)       # the kernels on the device, the op layer's torch path on the CPU

@@ -1,7 +1,9 @@
 """The k-nearest-neighbour arithmetic of the precision / recall metric as fused HIP kernels (csrc/knn_manifold.hip).
 
 ``kth_radius`` is the reference's ``dist.kthvalue(nhood_size + 1)`` and ``in_manifold`` its ``(dist <= kth).any(dim=1)``
-(stylegan2ada/metrics/precision_recall.py:48-60), both without the distance matrix ever being stored.  One definition for both devices:
+(stylegan2ada/metrics/precision_recall.py:48-60), both without the distance matrix ever being stored.  ``probe`` returns, per probe, how
+many balls hold it and how far its nearest manifold point is: the pass behind density / coverage (Naeem et al., ICML 2020), which the
+reference does not have.  One definition for both devices:
 
     n(x) = sum x_f^2,  s(x, y) = sum x_f y_f        products of the fp16 values, summed in fp32 (any order)
     d2   = max((n(x) + n(y)) - 2 s, 0)               fp32, in that association
@@ -88,3 +90,37 @@ def in_manifold(probes, manifold, radius):
     _lib.check(lib.sbg_knn_in_manifold(probes.data_ptr(), manifold.data_ptr(), radius.data_ptr(), P, C, F, out.data_ptr(), ws.data_ptr(),
                                        _lib.stream_ptr(probes.device)), "sbg_knn_in_manifold")
     return out.bool()
+
+
+def probe(probes, manifold, radius):
+    """probes [P, F], manifold [C, F], radius [C] -> (count int32 [P], nearest fp16 [P]): the number of manifold points whose ball holds the
+    probe (`d <= radius[j]`, so `count > 0` is `in_manifold`) and the distance to the nearest manifold point (`kth_radius(probes, manifold, 0)`)"""
+    _check(probes, manifold, 0)
+    P, F = probes.shape
+    C = manifold.shape[0]
+    if radius.shape != (C,) or radius.device != manifold.device:
+        raise RuntimeError(f"knn_manifold.probe: expects one radius per manifold point on its device, got {tuple(radius.shape)} on {radius.device}")
+    if probes.device.type != "cuda":
+        n_manifold = manifold.to(torch.float64).square().sum(1).to(torch.float32)
+        r = radius.to(torch.float16)
+        count, nearest = [], []
+        for b in probes.split(_CPU_ROWS):
+            d = _cpu_distances(b, manifold, n_manifold)
+            count.append((d <= r).sum(dim=1, dtype=torch.int32))
+            nearest.append(d.to(torch.float32).min(dim=1).values.to(torch.float16))
+        if not count:
+            return torch.empty([0], dtype=torch.int32), torch.empty([0], dtype=torch.float16)
+        return torch.cat(count), torch.cat(nearest)
+    probes, manifold, radius = (_lib.require_dtype(t, torch.float16, "knn_manifold.probe").contiguous() for t in (probes, manifold, radius))
+    count = torch.empty([P], dtype=torch.int32, device=probes.device)
+    nearest = torch.empty([P], dtype=torch.float16, device=probes.device)
+    if P == 0:
+        return count, nearest
+    lib = _lib.load()
+    nbytes = lib.sbg_knn_probe_workspace(P, C)
+    if nbytes < 0:
+        raise RuntimeError(f"knn_manifold.probe: unsupported sizes P={P} C={C}")
+    ws = _lib.workspace(nbytes, probes.device, "sbg_knn_probe_workspace")
+    _lib.check(lib.sbg_knn_probe(probes.data_ptr(), manifold.data_ptr(), radius.data_ptr(), P, C, F, count.data_ptr(), nearest.data_ptr(), ws.data_ptr(),
+                                 _lib.stream_ptr(probes.device)), "sbg_knn_probe")
+    return count, nearest
