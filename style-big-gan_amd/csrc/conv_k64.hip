@@ -27,8 +27,9 @@ using namespace sbgconv;
 namespace {
 
 
-// Gather (im2col-on-the-fly) kernel: any tap list and stride; one 128 (or 64) x 256 (or 128) tile per workgroup, 8 waves.
-template <class MF, int BC, int BP, int WGC, int WGP>
+// Gather (im2col-on-the-fly) kernel: any tap list and stride; one 128 (or 64) x 256 (or 128) tile per workgroup, 8 waves, three LDS
+// stages -- or one 256 x 256 tile with two stages (wave tile 128 x 64; the pipeline of that form is derived at its loop below).
+template <class MF, int BC, int BP, int WGC, int WGP, int NSTAGE = 3>
 __global__ __launch_bounds__(512, 2) void conv_k64_kernel(ConvArgs p, unsigned x_bytes, unsigned w_bytes)
 {
     constexpr int NW = 8;
@@ -38,8 +39,8 @@ __global__ __launch_bounds__(512, 2) void conv_k64_kernel(ConvArgs p, unsigned x
     static_assert(WC % 32 == 0 && WP % 16 == 0 && BC % 64 == 0 && BP % 64 == 0, "tile shape");
     constexpr int IA = BC / 64;                        // weight pieces (8 rows x 128 B) per wave per K-step
     constexpr int IB = BP / 64;                        // gathered pixel pieces per wave per K-step
-    constexpr int NSTAGE = 3;                          // LDS stages; the loads of step s + NSTAGE - 1 are issued in step s
-    constexpr int LEAD = NSTAGE - 1;
+    constexpr int LEAD = NSTAGE - 1;                   // LDS stages: NSTAGE; the loads of step s + LEAD are issued in step s
+    static_assert(NSTAGE == 2 || NSTAGE == 3, "gather pipeline: one or two steps of loads in flight");
     constexpr int A_BYTES = BC * 128, B_BYTES = BP * 128, STAGE = A_BYTES + B_BYTES;
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -114,7 +115,8 @@ __global__ __launch_bounds__(512, 2) void conv_k64_kernel(ConvArgs p, unsigned x
 
     // Ping-pong schedule: waves 0-3 (X) and 4-7 (Y) -- one of each per SIMD -- run half a K-step apart, separated by two
     // barriers per step: while one group issues its LDS reads and DMAs the other owns the matrix pipe.  Global barrier index:
-    // X: B_a(s) = 2s, B_b(s) = 2s + 1;  Y: one extra barrier first, B_a(s) = 2s + 1, B_b(s) = 2s + 2.
+    // X: B_a(s) = 2s, B_b(s) = 2s + 1;  Y: one extra barrier first, B_a(s) = 2s + 1, B_b(s) = 2s + 2.  With three stages (two steps of
+    // loads in flight; the two-stage form is derived at its loop):
     //   RAW: every wave's counted vmcnt wait for step s precedes a barrier with index <= 2s (X: before B_a(s); Y: before
     //        B_b(s - 1)), and a stage is read only behind B_a(s).
     //   WAR: reads of step s are retired (lgkmcnt(0)) before B_b(s) <= 2s + 2; stage s % NSTAGE is refilled by the loads of
@@ -165,7 +167,6 @@ __global__ __launch_bounds__(512, 2) void conv_k64_kernel(ConvArgs p, unsigned x
                 for (int j = 0; j < TP; j++) fb[ks][j] = *reinterpret_cast<const short8_t*>(sb + j * 16 * 128 + (foff ^ (ks * 64)));
         };
         constexpr int C = IA + IB;                       // DMA instructions per wave per step
-        static_assert(LEAD == 2, "gather pipeline: two steps of loads in flight");
         // steps are tap-major: step = t * kchunks + chunk; (it, ic) = coordinates of the step whose loads are issued next
         // split K: workgroup blockIdx.y of gridDim.y takes steps [s_begin, s_begin + nsteps)
         int s_begin = 0;
@@ -181,6 +182,7 @@ __global__ __launch_bounds__(512, 2) void conv_k64_kernel(ConvArgs p, unsigned x
             wstage = wstage == NSTAGE - 1 ? 0 : wstage + 1;
             if (++ic == kchunks) { ic = 0; it++; }
         };
+        if constexpr (LEAD == 2) {
         if (nsteps > 0) issue_next();
         if (nsteps > 1) { issue_next(); wait_vmcnt_const<C>(); } else wait_vmcnt_const<0>();
         if (grpY) __builtin_amdgcn_s_barrier();
@@ -199,6 +201,132 @@ __global__ __launch_bounds__(512, 2) void conv_k64_kernel(ConvArgs p, unsigned x
             stage = stage == NSTAGE - 1 ? 0 : stage + 1;
         }
         if (!grpY) __builtin_amdgcn_s_barrier();
+        } else {
+        // Two stages, ONE step of loads in flight.  Barrier indices as above.  Stage s % 2 is read by X between barriers 2s and 2s + 1
+        // and by Y between 2s + 1 and 2s + 2 (each group's reads retired, lgkmcnt(0), before its B_b(s)), so it is free from global
+        // barrier 2s + 2 on and takes the loads of step s + 2; said for step s + 1: they may be issued behind global barrier 2s.
+        //   X: 2s is its B_a(s) -- it issues step s + 1 beside its fragment reads of step s, as the three-stage form does.
+        //   Y: 2s is its B_b(s - 1).  Behind its B_a(s) = 2s + 1 it would have to wait for the same loads before its B_b(s) of that
+        //      iteration (X reads them behind 2s + 2) and would expose the whole load latency, so Y issues step s + 2 behind its
+        //      B_b(s), one piece behind every eighth of the 64 MFMAs of step s.  (All eight pieces in front of the MFMAs: 4-5 % slower on
+        //      every shape; all behind them: the same within 1 %, 1-3 % slower at Cin 512.  DESIGN.md section 4.)
+        //   RAW: a wave's loads of step s + 1 go out behind global barrier 2s and are waited for (vmcnt(0): nothing newer is in
+        //        flight) in front of global barrier 2s + 2 -- X at the top of iteration s + 1, before B_a(s + 1); Y in iteration s,
+        //        before B_b(s) -- a full step later; stage (s + 1) % 2 is first read behind 2s + 2 (X's B_a(s + 1)).
+        //   WAR: stage (s + 1) % 2 held step s - 1, whose reads are retired before X's B_b(s - 1) = 2s - 1 and Y's B_b(s - 1) = 2s.
+        //   Start: everybody issues step 0; Y issues step 1 too (its "B_b(-1)" is the extra barrier 0, the stages are empty) and
+        //   waits for its step 0 in front of barrier 0; X waits for its step 0 in front of its B_a(0) = 0.
+        // Every wait is vmcnt(0) or a compile-time count; the two groups run separate loops, and Y's last two steps (nothing left to
+        // issue) are peeled, so the only branch between its B_b and its MFMAs is the tap change of the step it issues.
+        static_assert(NSTAGE == 2 && LEAD == 1, "two stages");
+        // Registers: 128 accumulators and 96 fragment registers leave 32 of the 256 for everything else, so a pixel piece keeps TWO values
+        // (the three-stage form keeps three): the byte offset of its tap-(0, 0) input pixel and its (row, column) packed in 16 + 16 bits for the
+        // range test (the launcher admits output grids whose rows and columns stay below 32768 only; an invalid pixel has row -16384); the tap's byte shift is a scalar.  The tap
+        // table packs (dy, dx) the same way.  The wave's IA weight pieces are rows of ONE 32-row block: chmap() puts piece k at channel
+        // 16 (k & 1) + 4 (k >> 1) of piece 0's, a scalar that rides in the DMA's scalar offset beside (tap, slab) -- one register for the four
+        // (the block is in range or out as a whole: the launcher admits Cout % 256 == 0 only).
+        static_assert(IA == 4, "weight pieces of a wave = one 32-row block");
+        const int tbl_dyx = tbl_dy * 65536 | (tbl_dx & 0xffff);
+        unsigned b_org[IB]; int b_yx[IB];
+#pragma unroll
+        for (int i = 0; i < IB; i++) {
+            const int pix = p0 + (wave * IB + i) * 8 + lrow;
+            const bool ok = pix < p.P;
+            const int pp = ok ? pix : 0;
+            const int ox = pp % p.OW, t = pp / p.OW, oy = t % p.OH, n = t / p.OH;
+            b_yx[i] = ((ok ? oy * p.stride : -16384) * 65536) | (ox * p.stride);
+            b_org[i] = (unsigned)(n * (int)p.xs_n + oy * p.stride * (int)p.xs_h + ox * p.stride * (int)p.xs_w + src_k) * 2u;
+        }
+        auto tap_prep = [&](int t) {                     // issue_x's per-tap part
+            if (t != x_tap) {                            // (wave-uniform)
+                x_tap = t;
+                const int dyx = __builtin_amdgcn_readlane(tbl_dyx, t), dy = dyx >> 16, dx = (int)(short)(dyx & 0xffff);
+                const unsigned shift = (unsigned)(dy * (int)p.xs_h + dx * (int)p.xs_w) * 2u;
+#pragma unroll
+                for (int i = 0; i < IB; i++) {
+                    const int iy = (b_yx[i] >> 16) + dy, ix = (b_yx[i] & 0xffff) + dx;
+                    const bool ok = ((unsigned)iy < (unsigned)p.IH) & ((unsigned)ix < (unsigned)p.IW);
+                    x_off[i] = ok ? b_org[i] + shift : SBG_OOB_OFFSET;
+                }
+            }
+        };
+        auto issue_piece = [&](auto k_tag, int t, int chunk, int stg) {      // piece k of the wave's C: weight pieces first, then pixel pieces
+            constexpr int k = decltype(k_tag)::value;
+            unsigned char* st = smem + stg * STAGE;
+            const bool ragged = chunk * 64 + 64 > p.Cin;          // (wave-uniform)
+            if constexpr (k < IA) {
+                const int wtap = __builtin_amdgcn_readlane(tbl_wtap, t) + chunk * 128 + (16 * (k & 1) + 4 * (k >> 1)) * (int)p.ws_co * 2;
+                unsigned off = a_base[0];
+                if (ragged) off = (chunk * 64 + src_k < p.Cin) ? off : SBG_OOB_OFFSET;
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(wr, (lds_void_ptr)(st + (wave * IA + k) * 1024), 16, off, wtap, 0, 0);
+            } else {
+                constexpr int i = k - IA;
+                unsigned off = x_off[i];
+                if (ragged) off = (chunk * 64 + src_k < p.Cin) ? off : SBG_OOB_OFFSET;
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(xr, (lds_void_ptr)(st + A_BYTES + (wave * IB + i) * 1024), 16, off, chunk * 128, 0, 0);
+            }
+        };
+        auto issue_advance = [&]() {
+            wstage ^= 1;
+            if (++ic == kchunks) { ic = 0; it++; }
+        };
+        auto issue_all = [&]() {                         // all C pieces of the next step
+            tap_prep(it);
+            sbg_static_for<C>([&](auto k_tag) { issue_piece(k_tag, it, ic, wstage); });
+            issue_advance();
+        };
+        constexpr int NG = 2 * TC, GPP = NG / C;        // MFMA groups (TP MFMAs each) of a step; groups per DMA piece
+        static_assert(NG % C == 0, "pieces spread evenly over the MFMA groups");
+        auto mma_issue = [&]() {                         // Y: the MFMAs of step s with the loads of step s + 2 spread between them
+            tap_prep(it);
+            sbg_static_for<NG>([&](auto q_tag) {
+                constexpr int q = decltype(q_tag)::value, ks = q / TC, i = q % TC;
+#pragma unroll
+                for (int j = 0; j < TP; j++) acc[i][j] = Mfma<MF>::run(fa[ks][i], fb[ks][j], acc[i][j]);
+                if constexpr ((q + 1) % GPP == 0) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    issue_piece(std::integral_constant<int, (q + 1) / GPP - 1>{}, it, ic, wstage);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            });
+            issue_advance();
+        };
+        if (nsteps > 0) issue_all();
+        int stage = 0;
+        if (!grpY) {
+            for (int s = 0; s < nsteps; s++) {
+                wait_vmcnt_const<0>();                       // this wave's loads of step s
+                __builtin_amdgcn_s_barrier();                // B_a
+                read_a(stage); read_b(stage);
+                if (s + 1 < nsteps) issue_all();
+                __builtin_amdgcn_s_waitcnt(0xC07F);          // lgkmcnt(0)
+                __builtin_amdgcn_s_barrier();                // B_b
+                __builtin_amdgcn_sched_barrier(0);
+                mma();
+                __builtin_amdgcn_sched_barrier(0);
+                stage ^= 1;
+            }
+            __builtin_amdgcn_s_barrier();
+        } else {
+            if (nsteps > 1) { issue_all(); wait_vmcnt_const<C>(); } else wait_vmcnt_const<0>();
+            __builtin_amdgcn_s_barrier();                    // 0
+            auto y_step = [&](auto more_tag) {
+                constexpr bool more = decltype(more_tag)::value;      // step s + 2 exists
+                __builtin_amdgcn_s_barrier();                // B_a
+                read_a(stage); read_b(stage);
+                wait_vmcnt_const<0>();                       // this wave's loads of step s + 1
+                __builtin_amdgcn_s_waitcnt(0xC07F);          // lgkmcnt(0)
+                __builtin_amdgcn_s_barrier();                // B_b
+                __builtin_amdgcn_sched_barrier(0);
+                if constexpr (more) mma_issue(); else mma();
+                __builtin_amdgcn_sched_barrier(0);
+                stage ^= 1;
+            };
+            int s = 0;
+            for (; s + 2 < nsteps; s++) y_step(std::true_type{});
+            for (; s < nsteps; s++) y_step(std::false_type{});
+        }
+        }
     }
 
     // ---- epilogue ---------------------------------------------------------------------------------------------------
@@ -752,15 +880,15 @@ static int launch_halo_ld(ConvArgs& a, unsigned x_bytes, unsigned w_bytes, hipSt
                                                         {a.P, a.Cout, a.Cin, a.ntaps, a.stride, a.OH, 3128256}, a, x_bytes, w_bytes);
 }
 
-template <class MF, int BC, int BP, int WGC, int WGP>
+template <class MF, int BC, int BP, int WGC, int WGP, int NSTAGE = 3>
 static int launch_k64(ConvArgs& a, unsigned x_bytes, unsigned w_bytes, hipStream_t stream)
 {
-    constexpr int lds = 3 * (BC * 128 + BP * 128);
+    constexpr int lds = NSTAGE * (BC * 128 + BP * 128);
     static_assert(lds <= 160 * 1024, "LDS budget");
     a.ctiles = (a.Cout + BC - 1) / BC;
     a.ptiles = (a.P + BP - 1) / BP;
     const int64_t nblk = (int64_t)a.ptiles * a.ctiles;
-    return conv_launch<conv_k64_kernel<MF, BC, BP, WGC, WGP>>(nblk, (unsigned)(a.ksplit > 1 ? a.ksplit : 1), 512, lds, stream,
+    return conv_launch<conv_k64_kernel<MF, BC, BP, WGC, WGP, NSTAGE>>(nblk, (unsigned)(a.ksplit > 1 ? a.ksplit : 1), 512, lds, stream,
                                                               2.0 * a.P * a.Cout * (double)a.Cin * a.ntaps, conv_prof_bytes(a, a.P),
                                                               {a.P, a.Cout, a.Cin, a.ntaps, a.stride, a.OH, 1000000 + BC * 1000 + BP}, a, x_bytes, w_bytes);
 }
@@ -824,6 +952,11 @@ static int dispatch_k64(ConvArgs& a, unsigned xb, unsigned wb, hipStream_t strea
     // -5 % at 18+ (the 8-wave kernel's in-wave DMA issue overlaps better there)
     const int ksteps = a.ntaps * ((a.Cin + 63) >> 6);
     if (ksteps >= 2 && ksteps <= 8) return launch_gather_ld<MF>(a, xb, wb, stream);      // 1 step: store-bound, the plain kernel wins
+    // 256 x 256 tiles, two stages: 64 DMA pieces per K-step for twice the flops of the 48 below.  Stride-2 launches (D's conv1, the data
+    // gradient of G's up-sampling layers) whose 256-channel tiles still give every CU one
+    // (the kernel packs a pixel's input row and column into 16 + 16 bits)
+    if (a.stride == 2 && a.Cout % 256 == 0 && (a.OH - 1) * 2 + 8 < 32768 && (a.OW - 1) * 2 + 8 < 32768 && (int64_t)((a.P + 255) / 256) * (a.Cout / 256) >= sbg_cu_count())
+        return launch_k64<MF, 256, 256, 2, 4, 2>(a, xb, wb, stream);
     return launch_k64<MF, 128, 256, 2, 4>(a, xb, wb, stream);
 }
 
