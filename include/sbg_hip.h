@@ -560,6 +560,22 @@ int sbg_u8_gather_images(const uint8_t* store, int64_t S, int C, int H, int W, c
                          int out_f32, const float* lut, sbg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Exact nearest stored images of uint8 queries (the search behind nearest_neighbors.py; the reference has no counterpart).
+ * `queries` uint8 [Q, F], `store` uint8 [M, F], dense 16-byte aligned rows.  For query q: the k rows j with the smallest
+ *   d2(q, j) = sum_f (queries[q, f] - store[j, f])^2,   an exact integer,
+ * sorted ascending by (d2, j), so ties go to the lower j: d2 int64 [Q, k], index int32 [Q, k].  Row exclude[q] (int32 [Q] on the device,
+ * or NULL) is skipped when it lies in [0, M); it is the only row skipped, a duplicate of it elsewhere in the store is a hit.
+ * Arithmetic: bytes are re-centred (a - 128) and multiplied on the i8 matrix cores with i32 accumulators whose upper 16 bits are moved
+ * into a second sum before they can overflow; the norms and d2 = n(q) + n(x) - 2 s are int64.  The result is exact for every input inside the limits:
+ * 1 <= k <= 8; M >= k, and M >= k + 1 when `exclude` is given; Q, M <= 2^24; F a multiple of 16 in [16, 3 * 2^20].  Anything else is an
+ * error, never another path.  The store's tiles are split over workgroups when the queries alone do not fill the chip; the partial
+ * lists go through `workspace` (sbg_u8_nn_workspace(Q, M, k) bytes, 16-byte aligned; -1 for unsupported sizes) and are merged by a
+ * second launch in index order.  The split is a function of the shape alone and there are no atomics: two calls give the same bits. */
+int64_t sbg_u8_nn_workspace(int Q, int M, int k);
+int sbg_u8_nn_topk(const uint8_t* queries, const uint8_t* store, int Q, int M, int64_t F, int k, const int32_t* exclude, int64_t* d2,
+                   int32_t* index, void* workspace, sbg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * DiffAugment (Zhao et al., "Differentiable Augmentation for Data-Efficient GAN Training", NeurIPS 2020: colour, translation, cutout)
  * in front of the discriminator, fused: fp32 dense [N, C, H, W], C = 1..4, rows are axis 2 and columns axis 3.
  * `table` is the packed per-sample parameter table, int32 [N, SBG_DIFFAUG_WORDS] on the device, 4-byte aligned; words of sample n:
@@ -602,8 +618,10 @@ enum sbg_kernel_kind {
     SBG_K_GRAD_FINISH = 23,     /* dims[0] = variant: 0 sweep (records, n clipped to INT32_MAX, dims[3] = 1 when the scale is applied),
                                  * 1 merge (records) */
     SBG_K_RESIDENT = 24,        /* dims = B, C, H, W, out_f32, 0, dims[6] = 1 dword path (4 pixels per work-item) / 2 byte path */
-    SBG_K_DIFFAUG = 25          /* dims[0] = variant: 0 sum / 1 apply / 2 adjoint sum / 3 adjoint apply (the two launches of C H W > 4096),
+    SBG_K_DIFFAUG = 25,         /* dims[0] = variant: 0 sum / 1 apply / 2 adjoint sum / 3 adjoint apply (the two launches of C H W > 4096),
                                  * 4 single-pass forward / 5 single-pass adjoint (C H W <= 4096); then N, C, H, W, dims[5] = 1 16-byte / 2 dword accesses */
+    SBG_K_NN_U8 = 26            /* dims[0] = variant: 0 norms (Q or M rows, the other 0) / 1 single / 2 split (the tile kernel, one / several
+                                 * store runs per query tile) / 3 merge; then Q, M, F clipped to INT32_MAX, k, runs */
 };
 /* Kernel-variant codes in the records of the streaming kernels (which kernel served the launch):
  *   bias_act     dims[4] = 1 vec8 / 2 scalar,  dims[5] = bias mode (0 none, 1 channel-minor vector, 2 one per 8-vector, 3 generic)

@@ -105,7 +105,8 @@ class ProfRecord(ctypes.Structure):
 
 KERNEL_KINDS = {1: "bias_act", 2: "upfirdn2d", 3: "conv_igemm", 4: "conv_wgrad", 5: "wgrad_reduce", 6: "scale_nc", 7: "dot_hw", 9: "sn_power", 10: "attention",
                 11: "grid_sample", 12: "filter1d", 13: "color", 14: "weight_prep", 15: "torgb", 16: "fromrgb", 17: "grouped_gemm", 18: "ppl",
-                19: "projector", 20: "image_export", 21: "resample", 22: "pr", 23: "grad_finish", 24: "resident", 25: "diffaug"}
+                19: "projector", 20: "image_export", 21: "resample", 22: "pr", 23: "grad_finish", 24: "resident", 25: "diffaug", 26: "nn_u8"}
+NN_VARIANTS = {0: "norms", 1: "single", 2: "split", 3: "merge"}    # dims[0] of an "nn_u8" launch record (then Q, M, F clipped to int, k, runs)
 RESIDENT_PATHS = {1: "dword", 2: "byte"}                    # dims[6] of a "resident" launch record
 PPL_VARIANTS = {0: "slerp", 1: "lerp", 2: "prep", 3: "dist"}        # dims[0] of a "ppl" launch record
 PROJ_VARIANTS = {0: "reg", 1: "reg_bwd", 2: "normalize", 3: "sqdist", 4: "sqdist_bwd"}      # dims[0] of a "projector" launch record
@@ -206,6 +207,8 @@ SYMBOLS = [
     ("sbg_grad_finish_merge", _c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_void_p]),
     ("sbg_u8_gather_images", _c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int,
                                         _c.c_void_p, _c.c_void_p]),
+    ("sbg_u8_nn_workspace", _c.c_int64, [_c.c_int] * 3),
+    ("sbg_u8_nn_topk", _c.c_int, [_c.c_void_p] * 2 + [_c.c_int, _c.c_int, _c.c_int64, _c.c_int] + [_c.c_void_p] * 5),
     ("sbg_diffaug_workspace", _c.c_int64, [_c.c_int] * 4),
     ("sbg_diffaug_fwd", _c.c_int, [_c.c_void_p] * 4 + [_c.c_int] * 5 + [_c.c_void_p]),
     ("sbg_diffaug_adj", _c.c_int, [_c.c_void_p] * 4 + [_c.c_int] * 4 + [_c.c_void_p]),

@@ -1,0 +1,265 @@
+"""Nearest training images of generated images: is the generator copying its data?
+
+The reference has no such tool; the ADA, DiffAugment and BigGAN papers answer the question with nearest-neighbour figures in pixel space,
+and so does this one.  The training set is decoded once into the resident loader's uint8 store on the device
+(``train_parts/dataloaders.py``), the queries are exactly the bytes ``generate.py`` would write (``image_export.quantize(..., 'clamp')``),
+and the search is exact integer arithmetic on the i8 matrix cores (``torch_utils/ops/nn_u8.py``): d2 = sum of squared byte differences.
+
+* ``--seeds``: ``neighbors.png`` (one row per seed: the generated image, then its k nearest training images at full resolution, mirrored
+  where the mirrored copy matched) and ``neighbors.json`` (per seed a list of ``{item, file, flip, d2, rmse}``, rmse = sqrt(d2 / F)).
+* ``--num=N``: seeds 0..N-1 in batches; ``nn_stats.npz`` holds the exact int64 nearest d2 of every generated image (``gen_to_train``) and
+  the baseline ``train_to_train``, the nearest *other* stored image of every stored image (its own row is excluded in both
+  orientations); ``nn_stats.json`` holds, for both, min / 1, 5, 25, 50, 75 % quantiles / mean of the rmse, and
+  ``fraction_below_train_p01``: the share of generated images at or below the 1 % quantile of ``train_to_train`` -- the memorisation flag
+  (an exact copy always counts).
+* ``--res=R`` (a power of two, 4 <= R <= the data resolution) compares box-reduced copies (``resample_u8.resize(..., 'box')``) of the
+  store and the queries; the store is reduced once, in chunks.  Without it the search runs at full size.
+* Mirrored data sets (``data.mirror`` / ``--mirror=1``): d2(q, mirrored x) = d2(mirrored q, x), so the search runs twice over the one
+  store, with the queries and with ``queries.flip(3)``, and the two lists are merged by (d2, flip, row).  A mirrored data set lists
+  every image as stored and then every image mirrored, both in the store's order, so this is the order (d2, item): the result equals a
+  brute-force search over ``dataset[i]`` in item order, ties to the lower item.  (A box reduction by a power of two commutes with
+  mirroring, so the same holds under ``--res``.)
+
+Feature-space neighbours (LPIPS / VGG) are out of scope: they need a detector file and an index-returning fp16 kernel.
+
+    python -m style_big_gan_amd.nearest_neighbors exp.config_dir=<dir> exp.config=<file.yaml> --snapshot=<network-snapshot-*.pt> --outdir=<dir> \\
+        [--seeds=0-7] [--num=N] [--k=5] [--res=R] [--data=<folder|zip>] [--mirror=0|1] [--trunc=1] [--class=<idx>] \\
+        [--noise-mode=const|random|none] [--device=auto|cuda|cpu] [--batch=64]
+"""
+import argparse
+import json
+import os
+
+import numpy as np
+import torch
+
+from .calc_metrics import dataset_kwargs_for, resolve_device
+from .generate import NOISE_MODES, num_range
+from .snapshot_io import build_generator, config_overrides, snapshot_generator_state
+from .torch_utils.ops import image_export, nn_u8, resample_u8, resident_set
+
+QUANTILES = (0.01, 0.05, 0.25, 0.50, 0.75)
+STORE_CHUNK_BYTES = 256 << 20           # full-size store bytes reduced (--res) or searched as queries (the baseline) at a time
+_ROW_BITS = 24                          # nn_u8's row limit: (d2, flip, row) as one int64 key
+
+
+def check_res(res, resolution):
+    """--res: a power of two in [4, the data resolution]; None keeps the full size"""
+    if res is None:
+        return None
+    res = int(res)
+    if res < 4 or res & (res - 1) or res > resolution:
+        raise ValueError(f'--res={res}: must be a power of two, at least 4 and at most the data resolution {resolution}')
+    return None if res == resolution else res
+
+
+def reduce_images(images, res):
+    """uint8 [N, C, H, W] -> its box-reduced copy [N, C, res, res] (the exact uint8 box filter of resample_u8)"""
+    if res is None:
+        return images
+    out = resample_u8.resize(images.permute(0, 2, 3, 1).contiguous(), res, res, 'box')
+    return out.permute(0, 3, 1, 2).contiguous()
+
+
+def reduce_store(store, res):
+    """the whole store reduced once, in chunks of at most STORE_CHUNK_BYTES"""
+    if res is None:
+        return store
+    rows = max(1, STORE_CHUNK_BYTES // max(store[0].numel(), 1))
+    return torch.cat([reduce_images(store[lo:lo + rows], res) for lo in range(0, store.shape[0], rows)])
+
+
+def item_table(slot, flip, rows):
+    """-> int64 [2, rows] on the tables' device: the data set item that is store row r as stored ([0, r]) / mirrored ([1, r]), -1 when the
+    data set has no such item"""
+    table = torch.full([2, rows], -1, dtype=torch.int64, device=slot.device)
+    table[flip.to(torch.int64), slot.to(torch.int64)] = torch.arange(slot.numel(), dtype=torch.int64, device=slot.device)
+    return table
+
+
+def search(queries, store, k, mirrored, exclude=None):
+    """the k nearest data set images of every query -> (d2 int64 [Q, k], row int64 [Q, k], flip int64 [Q, k]), ascending by (d2, flip, row).
+    `mirrored`: the data set also holds every stored image mirrored, searched as `queries.flip(3)` against the same store."""
+    d2, row = nn_u8.topk(queries, store, k, exclude)
+    row = row.to(torch.int64)
+    if not mirrored:
+        return d2, row, torch.zeros_like(row)
+    d2f, rowf = nn_u8.topk(queries.flip(3).contiguous(), store, k, exclude)
+    key = torch.cat([(d2 << (_ROW_BITS + 1)) | row, (d2f << (_ROW_BITS + 1)) | (1 << _ROW_BITS) | rowf.to(torch.int64)], dim=1)
+    key = key.sort(dim=1).values[:, :k]
+    return key >> (_ROW_BITS + 1), key & ((1 << _ROW_BITS) - 1), (key >> _ROW_BITS) & 1
+
+
+def generated_queries(G, seeds, label, truncation_psi, noise_mode, device):
+    """the images of `seeds` in one batch, as the bytes generate.py writes -> uint8 [N, C, H, W] on `device`"""
+    z = torch.from_numpy(np.concatenate([np.random.RandomState(seed).randn(1, G.z_dim) for seed in seeds])).to(device)
+    img = G(z, label.expand(len(seeds), -1), truncation_psi=truncation_psi, noise_mode=noise_mode)
+    return image_export.quantize(img.to(torch.float32), 'clamp').permute(0, 3, 1, 2).contiguous()
+
+
+def rmse_summary(d2, F):
+    """min, the QUANTILES and the mean of sqrt(d2 / F)"""
+    rmse = np.sqrt(np.asarray(d2, dtype=np.float64) / F)
+    out = dict(min=float(rmse.min()), mean=float(rmse.mean()))
+    out.update({f'p{round(100 * q):02d}': float(v) for q, v in zip(QUANTILES, np.quantile(rmse, QUANTILES))})
+    return out
+
+
+def train_to_train(store, mirrored, batch):
+    """-> int64 [S] on the store's device: d2 from every stored image to the nearest other image of the data set (its own row is excluded,
+    as stored and mirrored)"""
+    S = store.shape[0]
+    if S < 2:
+        raise ValueError('the train_to_train baseline needs at least two stored images')
+    out = torch.empty([S], dtype=torch.int64, device=store.device)
+    for lo in range(0, S, batch):
+        hi = min(lo + batch, S)
+        own = torch.arange(lo, hi, dtype=torch.int32, device=store.device)
+        out[lo:hi] = search(store[lo:hi], store, 1, mirrored, exclude=own)[0][:, 0]
+    return out
+
+
+@torch.no_grad()
+def nearest_training_images(G, dataset, seeds=None, num=None, k=5, res=None, truncation_psi=1, noise_mode='const', class_idx=None, batch=64,
+                            outdir=None, device=None, max_gib=None):
+    """Nearest training images of G's samples in `dataset` (a train_parts.datasets.Dataset).  -> dict with, for `seeds`, `neighbors`
+    ({seed: [{item, file, flip, d2, rmse} x k]}) and `canvas` (uint8 [rows * H, (k + 1) * W, C]); for `num`, `gen_to_train` and
+    `train_to_train` (int64 ndarrays) and `stats`.  With `outdir` the files of the module docstring are written."""
+    from .train_parts.dataloaders import ResidentDataloader
+    if seeds is None and num is None:
+        raise ValueError('one of --seeds and --num is required')
+    if num is not None and int(num) < 1:
+        raise ValueError(f'--num={num}: must be at least 1')
+    batch = int(batch)
+    if batch < 1:
+        raise ValueError(f'--batch={batch}: must be at least 1')
+    device = torch.device(device) if device is not None else next(iter(G.buffers())).device
+    C, H, W = dataset.image_shape
+    if (G.img_resolution, G.img_resolution) != (H, W) or getattr(G, 'img_channels', C) != C:
+        raise ValueError(f'the generator makes {G.img_resolution} x {G.img_resolution} images, the data set holds {C} x {H} x {W}')
+    res = check_res(res, dataset.resolution)
+    if outdir is not None:
+        os.makedirs(outdir, exist_ok=True)
+
+    label = torch.zeros([1, G.c_dim], device=device)
+    if G.c_dim != 0:
+        if class_idx is None:
+            raise ValueError('Must specify class label with --class when using a conditional network')
+        label[:, class_idx] = 1
+    elif class_idx is not None:
+        print('warn: --class=lbl ignored when running on an unconditional network')
+
+    loader = ResidentDataloader(dataset, sampler=(), batch_size=1, device=device, max_gib=max_gib)
+    raw, slot, flip = resident_set.tables(dataset)
+    store = loader.store
+    S = store.shape[0]
+    mirrored = bool(flip.any())
+    if seeds is not None and S < k:
+        raise ValueError(f'--k={k}: the data set holds {S} stored images')
+    items = item_table(slot.to(device), flip.to(device), S)
+    small = reduce_store(store, res)
+    F = small[0].numel()
+    fnames = getattr(dataset, '_image_fnames', None)
+    result = dict(F=F, res=res if res is not None else dataset.resolution, k=k, mirrored=mirrored)
+
+    def look_up(batch_seeds, kk):
+        q = generated_queries(G, batch_seeds, label, truncation_psi, noise_mode, device)
+        return (q,) + search(reduce_images(q, res), small, kk, mirrored)
+
+    if seeds is not None:
+        seeds = [int(s) for s in seeds]
+        canvas = torch.zeros([len(seeds) * H, (k + 1) * W, C], dtype=torch.uint8, device=device)
+        neighbors = dict()
+        for r, seed in enumerate(seeds):                    # one image per call, as generate.py makes them
+            q, d2, row, fl = look_up([seed], k)
+            near = resident_set.gather(store, row[0].to(torch.int32), fl[0].to(torch.uint8))
+            cells = torch.cat([q, near]).permute(0, 2, 3, 1)
+            canvas[r * H:(r + 1) * H] = cells.permute(1, 0, 2, 3).reshape(H, (k + 1) * W, C)
+            item = items[fl[0], row[0]].cpu().tolist()
+            neighbors[seed] = [dict(item=item[t], file=fnames[int(raw[rw])] if fnames is not None else None, flip=int(f), d2=int(d), rmse=float(np.sqrt(d / F)))
+                               for t, (d, rw, f) in enumerate(zip(d2[0].cpu().tolist(), row[0].cpu().tolist(), fl[0].cpu().tolist()))]
+        result.update(neighbors=neighbors, canvas=canvas.cpu().numpy())
+        if outdir is not None:
+            import PIL.Image
+            img = result['canvas']
+            png = PIL.Image.fromarray(img[:, :, 0], 'L') if C == 1 else PIL.Image.fromarray(np.ascontiguousarray(img), 'RGB')
+            png.save(os.path.join(outdir, 'neighbors.png'))
+            with open(os.path.join(outdir, 'neighbors.json'), 'w') as f:
+                json.dump(dict(F=F, res=result['res'], k=k, seeds={str(s): v for s, v in neighbors.items()}), f, indent=2)
+
+    if num is not None:
+        num = int(num)
+        gen = torch.cat([look_up(list(range(lo, min(lo + batch, num))), 1)[1][:, 0] for lo in range(0, num, batch)])
+        base = train_to_train(small, mirrored, max(1, min(batch, STORE_CHUNK_BYTES // F)))
+        gen, base = gen.cpu().numpy(), base.cpu().numpy()
+        p01 = float(np.quantile(base.astype(np.float64), 0.01))
+        stats = dict(F=F, res=result['res'], num=num, stored_images=S, mirrored=mirrored, gen_to_train=rmse_summary(gen, F),
+                     train_to_train=rmse_summary(base, F), train_p01_d2=p01, fraction_below_train_p01=float(np.mean(gen <= p01)))
+        result.update(gen_to_train=gen, train_to_train=base, stats=stats)
+        if outdir is not None:
+            np.savez(os.path.join(outdir, 'nn_stats.npz'), gen_to_train=gen, train_to_train=base)
+            with open(os.path.join(outdir, 'nn_stats.json'), 'w') as f:
+                json.dump(stats, f, indent=2)
+    return result
+
+
+# ---------------------------------------------------------------------------------------------------------------- CLI
+
+def parse_args(argv=None):
+    """-> (config overrides as `key=value` strings, the tool's options)"""
+    ap = argparse.ArgumentParser(prog='python -m style_big_gan_amd.nearest_neighbors', description=__doc__.split('\n')[0])
+    ap.add_argument('--snapshot', required=True, help='network-snapshot-*.pt of this build (G_ema, or G when there is no EMA)')
+    ap.add_argument('--outdir', required=True, help='where to save neighbors.png / neighbors.json / nn_stats.npz / nn_stats.json')
+    ap.add_argument('--seeds', type=num_range, help='seeds whose images get a row of neighbours')
+    ap.add_argument('--num', type=int, help='distance statistics over the images of seeds 0..N-1')
+    ap.add_argument('--k', type=int, default=5, help=f'neighbours per image, 1 to {nn_u8.MAX_K} (default: 5)')
+    ap.add_argument('--res', type=int, help='compare box-reduced copies of this resolution (a power of two; default: full size)')
+    ap.add_argument('--data', help='data set to search, folder or zip (default: the run\'s data.dataset_path)')
+    ap.add_argument('--mirror', type=int, choices=(0, 1), help='whether the data set holds the x-flips (default: the run\'s data.mirror)')
+    ap.add_argument('--trunc', dest='truncation_psi', type=float, default=1, help='truncation psi (default: 1)')
+    ap.add_argument('--class', dest='class_idx', type=int, help='class label (unconditional if not specified)')
+    ap.add_argument('--noise-mode', choices=NOISE_MODES, default='const', help='noise mode (default: const)')
+    ap.add_argument('--device', choices=('auto', 'cuda', 'cpu'), default='auto', help='where to run (default: auto)')
+    ap.add_argument('--batch', type=int, default=64, help='images generated and searched at a time with --num (default: 64)')
+    args, rest = ap.parse_known_args(argv)
+    if args.seeds is None and args.num is None:
+        ap.error('one of --seeds and --num is required')
+    if args.num is not None and args.num < 1:
+        ap.error('--num must be at least 1')
+    if not 1 <= args.k <= nn_u8.MAX_K:
+        ap.error(f'--k must be between 1 and {nn_u8.MAX_K}')
+    if args.res is not None and (args.res < 4 or args.res & (args.res - 1)):
+        ap.error('--res must be a power of two, at least 4')
+    if args.batch < 1:
+        ap.error('--batch must be at least 1')
+    if not os.path.isfile(args.snapshot):
+        ap.error(f'--snapshot={args.snapshot}: no such file')
+    if args.mirror is not None:
+        args.mirror = bool(args.mirror)
+    return config_overrides(ap, rest), args
+
+
+def run_nearest_neighbors(argv=None):
+    overrides, args = parse_args(argv)
+    from . import arguments
+    from .train_parts.datasets import datasets
+    config = arguments.load_config(overrides)
+    dev_type = resolve_device(args.device)
+    device = torch.device('cuda', torch.cuda.current_device()) if dev_type == 'cuda' else torch.device('cpu')
+    print(f'Loading networks from "{args.snapshot}"...')
+    G = build_generator(config, snapshot_generator_state(args.snapshot), device)
+    kw = dataset_kwargs_for(config, G, data=args.data, mirror=args.mirror)
+    print('Dataset options:', kw)
+    dataset = datasets[config.data.dataset](**kw)
+    try:
+        result = nearest_training_images(G, dataset, seeds=args.seeds, num=args.num, k=args.k, res=args.res, truncation_psi=args.truncation_psi,
+                                         noise_mode=args.noise_mode, class_idx=args.class_idx, batch=args.batch, outdir=args.outdir, device=device)
+    finally:
+        dataset.close()
+    if 'stats' in result:
+        print(json.dumps(result['stats']))
+    return result
+
+
+if __name__ == '__main__':
+    run_nearest_neighbors()
