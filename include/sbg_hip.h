@@ -520,6 +520,17 @@ int sbg_knn_in_manifold(const void* probes, const void* manifold, const void* ra
 int64_t sbg_knn_probe_workspace(int P, int C);
 int sbg_knn_probe(const void* probes, const void* manifold, const void* radius, int P, int C, int64_t F, int32_t* count, void* nearest,
                   void* workspace, sbg_stream_t stream);
+/* Nearest manifold rows in feature space (the --space=vgg16 search of nearest_neighbors.py), same kernels and arithmetic: for query q
+ * the k rows j with the smallest d2(q, j), ascending by (d2, j) so a tie goes to the lower row: d2 fp32 [Q, k] (the fp32 value itself,
+ * nothing is rounded to fp16), index int32 [Q, k].  Row exclude[q] (int32 [Q] on the device, or NULL) is skipped when it lies in
+ * [0, M); it is the only row skipped, a duplicate of it elsewhere is a hit.  1 <= k <= 8; M >= k, and M >= k + 1 when `exclude` is
+ * given; Q, M <= 2^24; F a multiple of 8; dense 16-byte aligned rows and workspace (sbg_knn_topk_workspace(Q, M, k) bytes, -1 for
+ * unsupported sizes: the norms and, when the manifold is split, per (row, run) a list of 1 | 4 | 8 64-bit keys bits(d2) << 32 | row).
+ * Anything else is an error.  Non-finite features are outside the definition (a NaN d2 becomes 0).  No atomics, and keys of distinct
+ * rows are distinct: two calls give the same bits. */
+int64_t sbg_knn_topk_workspace(int Q, int M, int k);
+int sbg_knn_topk(const void* queries, const void* manifold, int Q, int M, int64_t F, int k, const int32_t* exclude, float* d2, int32_t* index,
+                 void* workspace, sbg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * End of a training phase over a flat fp32 gradient bucket: the reference's per-parameter loop `misc.nan_to_num(param.grad, nan=0,

@@ -5,6 +5,8 @@
 //   in_manifold:  out[i] = any_j d(probes[i], manifold[j]) <= radius[j]                      (uint8)
 //   probe:        count[i] = |{ j : d(probes[i], manifold[j]) <= radius[j] }|  (int32),  nearest[i] = min_j d(probes[i], manifold[j])  (fp16)
 //                 -- the pass behind density / coverage (Naeem et al., ICML 2020) and, as count > 0, behind precision / recall
+//   topk:         d2[i, t], index[i, t] = the t-th smallest (d2(queries[i], manifold[j]), j) over j != exclude[i]   (fp32, int32; t < k <= 8)
+//                 -- the feature-space search of nearest_neighbors.py; selection is on d2 itself, nothing is rounded to fp16
 // Arithmetic: n(x) = sum x_f^2 and s(x, y) = sum x_f y_f are fp32 sums of fp16 products; d2 = max((n(x) + n(y)) - 2 s, 0) in fp32;
 // d = fp16_rn(sqrt_f32(d2)).  Rounding is monotone, so the radius kernel selects on d2 (and the probe pass takes its minimum on d2) and
 // rounds the selected value once.
@@ -22,7 +24,12 @@
 // its partial list / flag / {count, minimum} pair to the workspace and a second launch merges the runs in index order (`split` +
 // `merge`).  The k smallest of a multiset, an OR, an integer sum and a minimum do not depend on the order, and there are no atomics: two
 // runs give the same bits.
-// Launch-log key: kind SBG_K_PR, dims = {variant (0 single, 1 split, 2 merge, 3 norms), R, C, F, k, runs, 0 radius / 1 membership / 2 probe}.
+// Top-k candidates are 64-bit keys (uint64(bits(d2)) << 32) | row.  d2 is never negative and never -0: n(x) + n(y) is a sum of squares,
+// so +0 or positive; a - b of two floats is -0 only for a = -0, b = +0 (a - a is +0 under round-to-nearest), so (n(x) + n(y)) - 2 s is
+// +0, positive, or negative and then replaced by the +0 of fmaxf(., 0).  The bits of such floats order as unsigned integers the way the
+// values do, so one unsigned compare orders by (d2, row) and a tie goes to the lower row.  A row past the end, or equal to exclude[q],
+// gets the all-ones key and never enters a list.  Keys of distinct rows are distinct, so the k smallest do not depend on the order.
+// Launch-log key: kind SBG_K_PR, dims = {variant (0 single, 1 split, 2 merge, 3 norms), R, C, F, k, runs, 0 radius / 1 membership / 2 probe / 3 top-k}.
 #include "conv_common.h"
 #include "reduce.h"
 
@@ -31,7 +38,7 @@ using namespace sbgconv;
 namespace {
 
 constexpr int kPrSingle = 0, kPrSplit = 1, kPrMerge = 2, kPrNorms = 3;
-constexpr int kRadius = 0, kMember = 1, kProbe = 2;       // what the tile kernel reduces a query row's distances to (dims[6] of a record)
+constexpr int kRadius = 0, kMember = 1, kProbe = 2, kTopk = 3;       // what the tile kernel reduces a query row's distances to (dims[6] of a record)
 
 constexpr int BT = 128;                     // tile side: manifold points and query rows
 constexpr int BK = 64;                      // K-step
@@ -42,13 +49,16 @@ constexpr int STAGE = 2 * OP_BYTES;
 constexpr int PARAM_OFF = 2 * STAGE;        // behind the two stages: norms and radii of the manifold tile, double-buffered by tile parity
 constexpr int LDS_BYTES = PARAM_OFF + 2 * 2 * BT * 4;
 constexpr int kMaxK1 = 8;                   // k + 1 <= 8
+constexpr int kMaxTopk = 8;                 // top-k: 1 <= k <= 8
+constexpr uint64_t kNoKey = ~(uint64_t)0;   // top-k: no candidate
 constexpr int kTargetGroups = 512;          // workgroups to aim for: 256 CUs x 2 resident
 
 struct KnnArgs {
     const unsigned short* q; const unsigned short* m;     // query rows [R, F], manifold [C, F]
     const float* nq; const float* nm;                      // their squared norms
     const unsigned short* radius;                          // membership and probe: fp16 [C]
-    void* out; void* nearest = nullptr; void* part;        // nearest: the probe's second output, fp16 [R]
+    void* out; void* nearest = nullptr; void* part;        // nearest: the probe's second output, fp16 [R]; top-k: out = d2 fp32 [R, k], nearest = index int32 [R, k]
+    const int32_t* exclude = nullptr;                      // top-k: [R] or null
     int R, C, F, k, runs, ctiles, tiles_per_run;
 };
 
@@ -78,6 +88,24 @@ __device__ __forceinline__ void list_insert(float (&L)[KL], float v)
     }
 }
 
+// top-k: keep the KL smallest keys, ascending; keys of distinct rows are distinct
+template <int KL>
+__device__ __forceinline__ void key_insert(uint64_t (&L)[KL], uint64_t v)
+{
+    if (v < L[KL - 1]) {
+#pragma unroll
+        for (int t = 0; t < KL; t++) { const uint64_t lo = L[t] < v ? L[t] : v; v = L[t] < v ? v : L[t]; L[t] = lo; }
+    }
+}
+
+__device__ __forceinline__ uint64_t topk_key(float d2, int row) { return ((uint64_t)__float_as_uint(d2) << 32) | (uint32_t)row; }
+
+__device__ __forceinline__ void topk_store(uint64_t key, float* d2, int32_t* index)
+{
+    *d2 = __uint_as_float((uint32_t)(key >> 32));
+    *index = (int32_t)(uint32_t)key;
+}
+
 __device__ __forceinline__ float dist2(float nx, float ny, float s)
 {
 #pragma clang fp contract(off)
@@ -91,7 +119,7 @@ struct ProbePart { int count; float d2; };                 // a run's share of a
 template <int KL, int MODE>
 __device__ __forceinline__ void knn_tile_body(const KnnArgs& p)
 {
-    constexpr bool MEMBER = MODE == kMember, PROBE = MODE == kProbe;
+    constexpr bool MEMBER = MODE == kMember, PROBE = MODE == kProbe, TOPK = MODE == kTopk;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float* const prm = reinterpret_cast<float*>(smem + PARAM_OFF);          // [parity][0: norm, 1: radius][BT]
 
@@ -117,6 +145,18 @@ __device__ __forceinline__ void knn_tile_body(const KnnArgs& p)
     float nqv[4];
 #pragma unroll
     for (int j = 0; j < 4; j++) { const int r = q0 + wp + 16 * j + fr; nqv[j] = r < p.R ? p.nq[r] : 0.f; }
+
+    uint64_t T[4][TOPK ? KL : 1];       // top-k: the lists of keys
+    int excl[4];
+    if constexpr (TOPK) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int r = q0 + wp + 16 * j + fr;
+            excl[j] = (r < p.R && p.exclude) ? p.exclude[r] : -1;
+#pragma unroll
+            for (int t = 0; t < KL; t++) T[j][t] = kNoKey;
+        }
+    }
 
     float L[4][KL];
     int inside[4];                      // membership: the flag; probe: the count
@@ -212,7 +252,8 @@ __device__ __forceinline__ void knn_tile_body(const KnnArgs& p)
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
                     const float d2 = dist2(nqv[j], nmv, acc[i][j][e]);
-                    if (MEMBER) inside[j] |= (dist_f16(d2) <= rv) ? 1 : 0;
+                    if constexpr (TOPK) { const int row = c0 + col; key_insert<KL>(T[j], (row < p.C && row != excl[j]) ? topk_key(d2, row) : kNoKey); }
+                    else if (MEMBER) inside[j] |= (dist_f16(d2) <= rv) ? 1 : 0;
                     else if (PROBE) { inside[j] += (dist_f16(d2) <= rv) ? 1 : 0; nearest[j] = fminf(nearest[j], d2); }
                     else list_insert<KL>(L[j], d2);
                 }
@@ -222,7 +263,32 @@ __device__ __forceinline__ void knn_tile_body(const KnnArgs& p)
 
     // merge the lane groups and the two manifold waves that share a query row; the staging area is free after the last barrier
     const int q = q0 + tid;
-    if (MEMBER) {
+    if constexpr (TOPK) {
+        constexpr int QS = 8 * KL + 1;                           // odd stride in 8-byte words
+        uint64_t* ms = reinterpret_cast<uint64_t*>(smem);        // [BT][8 lists][KL]; at KL = 8: 128 * 65 * 8 B = 66560 B, the two stages exactly
+        static_assert(BT * QS * 8 <= PARAM_OFF, "the top-k merge area must fit the staging area");
+        const int slot = (wave >> 1) * 4 + fg;
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+#pragma unroll
+            for (int t = 0; t < KL; t++) ms[(wp + 16 * j + fr) * QS + slot * KL + t] = T[j][t];
+        __syncthreads();
+        if (tid < BT && q < p.R) {
+            uint64_t M[KL];
+#pragma unroll
+            for (int t = 0; t < KL; t++) M[t] = kNoKey;
+            for (int s = 0; s < 8 * KL; s++) key_insert<KL>(M, ms[tid * QS + s]);
+            if (p.runs == 1) {
+#pragma unroll
+                for (int t = 0; t < KL; t++)
+                    if (t < p.k) topk_store(M[t], reinterpret_cast<float*>(p.out) + (int64_t)q * p.k + t, reinterpret_cast<int32_t*>(p.nearest) + (int64_t)q * p.k + t);
+            } else {
+                uint64_t* dst = reinterpret_cast<uint64_t*>(p.part) + ((int64_t)q * p.runs + run) * KL;
+#pragma unroll
+                for (int t = 0; t < KL; t++) dst[t] = M[t];
+            }
+        }
+    } else if (MEMBER) {
         int* fl = reinterpret_cast<int*>(smem);                  // [manifold wave][BT]
 #pragma unroll
         for (int j = 0; j < 4; j++) {
@@ -292,6 +358,10 @@ __global__ __launch_bounds__(256) void knn_tile_kernel(KnnArgs p) { knn_tile_bod
 
 __global__ __launch_bounds__(256) void knn_probe_tile_kernel(KnnArgs p) { knn_tile_body<4, kProbe>(p); }
 
+// two waves per SIMD: without the bound KL = 8 takes 198 + 64 registers and a CU holds one workgroup; with it 254, no scratch
+template <int KL>
+__global__ __launch_bounds__(256, 2) void knn_topk_tile_kernel(KnnArgs p) { knn_tile_body<KL, kTopk>(p); }
+
 // Second stage of the split variant: one work-item per query row walks the runs in index order.
 template <int KL>
 __global__ __launch_bounds__(256) void knn_merge_radius_kernel(const float* __restrict__ part, unsigned short* __restrict__ out, int R, int runs, int k)
@@ -330,15 +400,32 @@ __global__ __launch_bounds__(256) void knn_merge_probe_kernel(const ProbePart* _
     nearest[q] = f32_to_f16_bits(sqrtf(v));
 }
 
+template <int KL>
+__global__ __launch_bounds__(256) void knn_merge_topk_kernel(const uint64_t* __restrict__ part, float* __restrict__ d2, int32_t* __restrict__ index, int R, int runs, int k)
+{
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= R) return;
+    uint64_t M[KL];
+#pragma unroll
+    for (int t = 0; t < KL; t++) M[t] = kNoKey;
+    const uint64_t* src = part + (int64_t)q * runs * KL;
+    for (int s = 0; s < runs * KL; s++) key_insert<KL>(M, src[s]);
+#pragma unroll
+    for (int t = 0; t < KL; t++)
+        if (t < k) topk_store(M[t], d2 + (int64_t)q * k + t, index + (int64_t)q * k + t);
+}
+
 struct KnnPlan { int rtiles, ctiles, tiles_per_run, runs; int64_t nq_off, nm_off, part_off, bytes; };
 
 int list_len(int k) { return k + 1 <= 4 ? 4 : 8; }
+int topk_list_len(int k) { return k == 1 ? 1 : k <= 4 ? 4 : 8; }
 
 // Runs per query tile: enough workgroups to fill the chip twice when the query tiles alone do not.  A function of the shape only, so
 // the workspace query and the launch agree and a result does not depend on the device it ran on.
 bool knn_plan(int R, int C, int k, int mode, KnnPlan& pl)
 {
-    if (R < 1 || C < 1 || k < 0 || k + 1 > kMaxK1 || R > (1 << 24) || C > (1 << 24)) return false;
+    if (R < 1 || C < 1 || R > (1 << 24) || C > (1 << 24)) return false;
+    if (mode == kTopk ? (k < 1 || k > kMaxTopk) : (k < 0 || k + 1 > kMaxK1)) return false;
     pl.rtiles = (R + BT - 1) / BT;
     pl.ctiles = (C + BT - 1) / BT;
     int want = kTargetGroups / pl.rtiles;
@@ -350,9 +437,9 @@ bool knn_plan(int R, int C, int k, int mode, KnnPlan& pl)
     pl.nm_off = up16(4 * (int64_t)R);
     pl.part_off = pl.nm_off + up16(4 * (int64_t)C);
     // partial results of the runs: a list of floats per (row, run) for the radius, one byte per (run, row) for the membership, one
-    // ProbePart per (run, row) for the probe
+    // ProbePart per (run, row) for the probe, a list of 64-bit keys per (row, run) for the top-k
     const int64_t part = mode == kMember ? up16((int64_t)R * pl.runs) : mode == kProbe ? (int64_t)sizeof(ProbePart) * R * pl.runs
-                                                                                       : 4 * (int64_t)R * pl.runs * list_len(k);
+                         : mode == kTopk ? 8 * (int64_t)R * pl.runs * topk_list_len(k) : 4 * (int64_t)R * pl.runs * list_len(k);
     pl.bytes = pl.part_off + (pl.runs > 1 ? part : 0);
     return true;
 }
@@ -378,9 +465,17 @@ int knn_norms(const unsigned short* x, float* n, int rows, int F, hipStream_t s)
 }
 
 template <int KL, int MODE>
+constexpr auto knn_tile_kernel_of()
+{
+    if constexpr (MODE == kTopk) return knn_topk_tile_kernel<KL>;
+    else if constexpr (MODE == kProbe) return knn_probe_tile_kernel;
+    else return knn_tile_kernel<KL, MODE == kMember>;
+}
+
+template <int KL, int MODE>
 int knn_launch_tiles(const KnnArgs& a, const KnnPlan& pl, hipStream_t s)
 {
-    constexpr auto kernel = MODE == kProbe ? knn_probe_tile_kernel : knn_tile_kernel<KL, MODE == kMember>;
+    constexpr auto kernel = knn_tile_kernel_of<KL, MODE>();
     if (!SBG_RAISE_LDS_ONCE(kernel, LDS_BYTES))
         return sbg_fail(SBG_ERR_LAUNCH, "knn_manifold: cannot raise the dynamic LDS limit to %d bytes", LDS_BYTES);
     SbgProfScope prof(s, SBG_K_PR, 2.0 * a.R * (double)a.C * a.F, 2.0 * ((double)a.R + a.C) * a.F,
@@ -472,6 +567,52 @@ extern "C" int sbg_knn_probe(const void* probes, const void* manifold, const voi
         SbgProfScope prof(s, SBG_K_PR, 0.0, 8.0 * P * (double)pl.runs + 6.0 * P, {kPrMerge, P, C, a.F, 0, pl.runs, kProbe});
         SBG_LAUNCH(knn_merge_probe_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, (const ProbePart*)a.part, (int*)count, (unsigned short*)nearest,
                    P, pl.runs);
+        SBG_HIP_LAUNCH_CHECK();
+    }
+    return SBG_OK;
+}
+
+extern "C" int64_t sbg_knn_topk_workspace(int Q, int M, int k)
+{
+    KnnPlan pl;
+    if (!knn_plan(Q, M, k, kTopk, pl)) return -1;
+    return pl.bytes;
+}
+
+extern "C" int sbg_knn_topk(const void* queries, const void* manifold, int Q, int M, int64_t F, int k, const int32_t* exclude, float* d2, int32_t* index,
+                            void* workspace, sbg_stream_t stream)
+{
+    const char* what = "knn_topk";
+    hipStream_t s = (hipStream_t)stream;
+    SBG_CHECK(queries && manifold && d2 && index && workspace, "%s: null pointer", what);
+    SBG_CHECK(k >= 1 && k <= kMaxTopk, "%s: k = %d neighbours, 1 to %d are supported", what, k, kMaxTopk);
+    SBG_CHECK(Q >= 1 && M >= 1 && Q <= (1 << 24) && M <= (1 << 24), "%s: bad sizes Q=%d M=%d (1 to 2^24 each)", what, Q, M);
+    SBG_CHECK(M - (exclude ? 1 : 0) >= k, "%s: the manifold has %d rows%s, %d neighbours need %d", what, M, exclude ? " and one may be excluded" : "", k,
+              k + (exclude ? 1 : 0));
+    SBG_CHECK(F >= 8 && F % 8 == 0 && F <= (1 << 24), "%s: the feature width %lld must be a multiple of 8 (16-byte pieces) in [8, 2^24]", what, (long long)F);
+    SBG_CHECK(sbg_aligned16(queries) && sbg_aligned16(manifold) && sbg_aligned16(workspace), "%s: features and workspace must be 16-byte aligned", what);
+    KnnPlan pl;
+    SBG_CHECK(knn_plan(Q, M, k, kTopk, pl), "%s: bad sizes", what);
+
+    char* ws = (char*)workspace;
+    KnnArgs a;
+    a.q = (const unsigned short*)queries; a.m = (const unsigned short*)manifold;
+    a.nq = (const float*)(ws + pl.nq_off); a.nm = (const float*)(ws + pl.nm_off); a.radius = nullptr;
+    a.out = d2; a.nearest = index; a.part = ws + pl.part_off; a.exclude = exclude;
+    a.R = Q; a.C = M; a.F = (int)F; a.k = k; a.runs = pl.runs; a.ctiles = pl.ctiles; a.tiles_per_run = pl.tiles_per_run;
+    int st = knn_norms(a.q, (float*)(ws + pl.nq_off), Q, a.F, s);
+    if (st != SBG_OK) return st;
+    st = knn_norms(a.m, (float*)(ws + pl.nm_off), M, a.F, s);
+    if (st != SBG_OK) return st;
+    const int KL = topk_list_len(k);
+    st = KL == 1 ? knn_launch_tiles<1, kTopk>(a, pl, s) : KL == 4 ? knn_launch_tiles<4, kTopk>(a, pl, s) : knn_launch_tiles<8, kTopk>(a, pl, s);
+    if (st != SBG_OK) return st;
+    if (pl.runs > 1) {
+        SbgProfScope prof(s, SBG_K_PR, 0.0, 8.0 * Q * (double)pl.runs * KL + 8.0 * Q * k, {kPrMerge, Q, M, a.F, k, pl.runs, kTopk});
+        const dim3 grid((unsigned)((Q + 255) / 256));
+        if (KL == 1)      SBG_LAUNCH(knn_merge_topk_kernel<1>, grid, dim3(256), 0, s, (const uint64_t*)a.part, d2, index, Q, pl.runs, k);
+        else if (KL == 4) SBG_LAUNCH(knn_merge_topk_kernel<4>, grid, dim3(256), 0, s, (const uint64_t*)a.part, d2, index, Q, pl.runs, k);
+        else              SBG_LAUNCH(knn_merge_topk_kernel<8>, grid, dim3(256), 0, s, (const uint64_t*)a.part, d2, index, Q, pl.runs, k);
         SBG_HIP_LAUNCH_CHECK();
     }
     return SBG_OK;

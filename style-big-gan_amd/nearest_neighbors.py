@@ -1,7 +1,7 @@
 """Nearest training images of generated images: is the generator copying its data?
 
-The reference has no such tool; the ADA, DiffAugment and BigGAN papers answer the question with nearest-neighbour figures in pixel space,
-and so does this one.  The training set is decoded once into the resident loader's uint8 store on the device
+The reference has no such tool; the ADA, DiffAugment and BigGAN papers answer the question with nearest-neighbour figures in pixel space
+(``--space=pixel``, the default), the BigGAN paper in VGG-16 feature space as well (``--space=vgg16``).  In pixel space the training set is decoded once into the resident loader's uint8 store on the device
 (``train_parts/dataloaders.py``), the queries are exactly the bytes ``generate.py`` would write (``image_export.quantize(..., 'clamp')``),
 and the search is exact integer arithmetic on the i8 matrix cores (``torch_utils/ops/nn_u8.py``): d2 = sum of squared byte differences.
 
@@ -20,10 +20,23 @@ and the search is exact integer arithmetic on the i8 matrix cores (``torch_utils
   brute-force search over ``dataset[i]`` in item order, ties to the lower item.  (A box reduction by a power of two commutes with
   mirroring, so the same holds under ``--res``.)
 
-Feature-space neighbours (LPIPS / VGG) are out of scope: they need a detector file and an index-returning fp16 kernel.
+``--space=vgg16 --detector=<TorchScript file | directory holding vgg16.pt>`` searches in the feature space of the ``vgg16.pt`` detector that
+``pr50k3_full`` uses (``return_features=True``): a shifted or re-coloured copy is far from its source in bytes and stays close there.
+* The manifold is the feature of every data set item in item order (``metric_utils.compute_feature_stats_for_dataset(...,
+  capture_all=True)``, cached as ``.npz`` when the detector is a file; a cached array whose row count is not ``len(dataset)`` is not used),
+  the queries are the bytes ``generate.py`` writes, through the same detector.  Both are rounded to fp16, so ``--device=cpu`` and ``cuda``
+  search the same numbers, with ``knn_manifold.topk``: d2 = max((n(x) + n(y)) - 2 s, 0) in fp32, ascending by (d2, item) (DESIGN
+  section 19).  Features must be finite and their width a multiple of 8; ``--res`` is refused (the detector sees full-size images).
+* A mirrored data set lists its mirrored items as rows of their own -- feature(mirror x) is not mirror(feature x) -- so there is one
+  search, item = row, and ``flip`` / ``file`` come from the data set's tables.
+* ``neighbors.json``: ``{space, F, k, seeds}`` with entries ``{item, file, flip, d2, dist}``, dist = sqrt(d2); ``neighbors.png`` as above.
+  ``nn_stats.npz``: float32 d2; ``train_to_train`` has one entry per stored image: from its unmirrored item to the nearest item that is
+  neither itself nor its mirrored twin.  ``nn_stats.json``: the fields above with quantiles of dist in place of the rmse, plus ``space``.
+LPIPS space is out of scope: the reference's ``return_lpips=True`` features are about 8 M values per 256 x 256 image, and a training set of
+them does not fit on the device.
 
     python -m style_big_gan_amd.nearest_neighbors exp.config_dir=<dir> exp.config=<file.yaml> --snapshot=<network-snapshot-*.pt> --outdir=<dir> \\
-        [--seeds=0-7] [--num=N] [--k=5] [--res=R] [--data=<folder|zip>] [--mirror=0|1] [--trunc=1] [--class=<idx>] \\
+        [--seeds=0-7] [--num=N] [--k=5] [--space=pixel|vgg16] [--detector=<file|dir>] [--res=R] [--data=<folder|zip>] [--mirror=0|1] [--trunc=1] [--class=<idx>] \\
         [--noise-mode=const|random|none] [--device=auto|cuda|cpu] [--batch=64]
 """
 import argparse
@@ -33,11 +46,12 @@ import os
 import numpy as np
 import torch
 
-from .calc_metrics import dataset_kwargs_for, resolve_device
+from .calc_metrics import dataset_kwargs_for, detector_kwargs, resolve_device
 from .generate import NOISE_MODES, num_range
 from .snapshot_io import build_generator, config_overrides, snapshot_generator_state
-from .torch_utils.ops import image_export, nn_u8, resample_u8, resident_set
+from .torch_utils.ops import image_export, knn_manifold, nn_u8, resample_u8, resident_set
 
+SPACES = ('pixel', 'vgg16')
 QUANTILES = (0.01, 0.05, 0.25, 0.50, 0.75)
 STORE_CHUNK_BYTES = 256 << 20           # full-size store bytes reduced (--res) or searched as queries (the baseline) at a time
 _ROW_BITS = 24                          # nn_u8's row limit: (d2, flip, row) as one int64 key
@@ -119,13 +133,135 @@ def train_to_train(store, mirrored, batch):
     return out
 
 
+def dist_summary(d2):
+    """min, the QUANTILES and the mean of sqrt(d2)"""
+    dist = np.sqrt(np.asarray(d2, dtype=np.float64))
+    out = dict(min=float(dist.min()), mean=float(dist.mean()))
+    out.update({f'p{round(100 * q):02d}': float(v) for q, v in zip(QUANTILES, np.quantile(dist, QUANTILES))})
+    return out
+
+
+def checked_features(features, what):
+    """float features [N, F] -> fp16 on their device, finite and of a width the kernel takes"""
+    features = features.to(torch.float16)
+    if features.ndim != 2 or features.shape[1] % 8 != 0:
+        raise ValueError(f'--space=vgg16: the detector returns features of shape {list(features.shape[1:])} for {what}; the search needs a vector per '
+                         'image whose width is a multiple of 8')
+    if not bool(torch.isfinite(features).all()):
+        raise ValueError(f'--space=vgg16: the features of {what} are not all finite in fp16')
+    return features.contiguous()
+
+
+def dataset_features(opts, dataset, dataset_name):
+    """the detector's feature of every item of `dataset`, in item order -> float32 tensor [len(dataset), F] on the host"""
+    from .metrics import metric_utils, scores
+    kw = metric_utils.detector_call_kwargs(opts, scores.VGG16, dict(return_features=True))
+    stats = metric_utils.compute_feature_stats_for_dataset(opts, scores.VGG16, kw, dataset_name=dataset_name, capture_all=True)
+    if opts.cache and stats.num_items != len(dataset):      # a stale cache file (its name does not key on the row count): not used
+        opts.cache = False
+        stats = metric_utils.compute_feature_stats_for_dataset(opts, scores.VGG16, kw, dataset_name=dataset_name, capture_all=True)
+    if stats.num_items != len(dataset):
+        raise ValueError(f'--space=vgg16: dataset_kwargs describe a data set of {stats.num_items} items, the data set searched holds {len(dataset)}')
+    return stats.get_all_torch()
+
+
+def _feature_space(G, dataset, label, seeds, num, k, truncation_psi, noise_mode, batch, outdir, device, max_gib, detector, dataset_kwargs, dataset_name,
+                   cache_dir):
+    """the --space=vgg16 half of `nearest_training_images`"""
+    from .metrics import metric_utils, scores
+    from .train_parts.dataloaders import ResidentDataloader
+    C, H, W = dataset.image_shape
+    if isinstance(detector, str) and os.path.isdir(detector):
+        # a directory is resolved to the file here: the process-wide detector cache and the feature cache key on what they are given, and
+        # the bare name `vgg16.pt` would stand for whichever directory was loaded first
+        if not os.path.isfile(os.path.join(detector, scores.VGG16)):
+            raise ValueError(f'--detector={detector}: the directory does not hold {scores.VGG16}')
+        detector = os.path.join(detector, scores.VGG16)
+    opts = metric_utils.MetricOptions(dataset_kwargs=dataset_kwargs, device=device, cache_dir=cache_dir, **detector_kwargs(detector))
+    opts.cache = not callable(metric_utils.detector_source(opts, scores.VGG16))        # cache only when the detector is a file
+    call_kw = metric_utils.detector_call_kwargs(opts, scores.VGG16, dict(return_features=True))
+    detect = metric_utils._detector(opts, scores.VGG16)
+    manifold = checked_features(dataset_features(opts, dataset, dataset_name).to(device), 'the data set')
+    M, F = manifold.shape
+    raw, slot, flip = resident_set.tables(dataset)
+    S = len(raw)
+    mirrored = bool(flip.any())
+    if seeds is not None and M < k:
+        raise ValueError(f'--k={k}: the data set holds {M} items')
+    fnames = getattr(dataset, '_image_fnames', None)
+    result = dict(space='vgg16', F=F, res=dataset.resolution, k=k, mirrored=mirrored)
+
+    def features_of(batch_seeds):
+        q = generated_queries(G, batch_seeds, label, truncation_psi, noise_mode, device)
+        return q, detect(metric_utils._as_rgb(q), **call_kw).to(torch.float32)
+
+    if seeds is not None:
+        seeds = [int(s) for s in seeds]
+        store = ResidentDataloader(dataset, sampler=(), batch_size=1, device=device, max_gib=max_gib).store
+        images, feats = zip(*[features_of([seed]) for seed in seeds])          # one image per call, as generate.py makes them
+        d2, item = knn_manifold.topk(checked_features(torch.cat(feats), 'the generated images'), manifold, k)
+        d2, item = d2.cpu(), item.cpu().to(torch.int64)
+        canvas = torch.zeros([len(seeds) * H, (k + 1) * W, C], dtype=torch.uint8, device=device)
+        neighbors = dict()
+        for r, seed in enumerate(seeds):
+            near = resident_set.gather(store, slot[item[r]].to(device), flip[item[r]].to(device))
+            cells = torch.cat([images[r], near]).permute(0, 2, 3, 1)
+            canvas[r * H:(r + 1) * H] = cells.permute(1, 0, 2, 3).reshape(H, (k + 1) * W, C)
+            neighbors[seed] = [dict(item=i, file=fnames[int(raw[int(slot[i])])] if fnames is not None else None, flip=int(flip[i]), d2=float(d),
+                                    dist=float(np.sqrt(d))) for d, i in zip(d2[r].tolist(), item[r].tolist())]
+        result.update(neighbors=neighbors, canvas=canvas.cpu().numpy())
+        if outdir is not None:
+            import PIL.Image
+            img = result['canvas']
+            png = PIL.Image.fromarray(img[:, :, 0], 'L') if C == 1 else PIL.Image.fromarray(np.ascontiguousarray(img), 'RGB')
+            png.save(os.path.join(outdir, 'neighbors.png'))
+            with open(os.path.join(outdir, 'neighbors.json'), 'w') as f:
+                json.dump(dict(space='vgg16', F=F, k=k, seeds={str(s): v for s, v in neighbors.items()}), f, indent=2)
+
+    if num is not None:
+        num = int(num)
+        if S < 2:
+            raise ValueError('the train_to_train baseline needs at least two stored images')
+        feats = torch.cat([features_of(list(range(lo, min(lo + batch, num))))[1] for lo in range(0, num, batch)])
+        gen = knn_manifold.topk(checked_features(feats, 'the generated images'), manifold, 1)[0][:, 0].cpu().numpy()
+        # the baseline: the unmirrored item of every stored image against all items but itself; its mirrored twin is dropped here
+        own = item_table(slot, flip, S)
+        assert bool((own[0] >= 0).all())
+        d2, item = knn_manifold.topk(manifold[own[0].to(device)], manifold, 2 if mirrored else 1, exclude=own[0].to(torch.int32).to(device))
+        first = (item[:, 0].cpu().to(torch.int64) == own[1]).to(torch.int64)            # 1 where the nearest is the twin: take the second
+        base = d2.cpu().gather(1, first[:, None])[:, 0].numpy()
+        p01 = float(np.quantile(base.astype(np.float64), 0.01))
+        stats = dict(space='vgg16', F=F, res=dataset.resolution, num=num, stored_images=S, mirrored=mirrored, gen_to_train=dist_summary(gen),
+                     train_to_train=dist_summary(base), train_p01_d2=p01, fraction_below_train_p01=float(np.mean(gen <= p01)))
+        result.update(gen_to_train=gen, train_to_train=base, stats=stats)
+        if outdir is not None:
+            np.savez(os.path.join(outdir, 'nn_stats.npz'), gen_to_train=gen, train_to_train=base)
+            with open(os.path.join(outdir, 'nn_stats.json'), 'w') as f:
+                json.dump(stats, f, indent=2)
+    return result
+
+
 @torch.no_grad()
 def nearest_training_images(G, dataset, seeds=None, num=None, k=5, res=None, truncation_psi=1, noise_mode='const', class_idx=None, batch=64,
-                            outdir=None, device=None, max_gib=None):
+                            outdir=None, device=None, max_gib=None, space='pixel', detector=None, dataset_kwargs=None, dataset_name='image_folder',
+                            cache_dir=None):
     """Nearest training images of G's samples in `dataset` (a train_parts.datasets.Dataset).  -> dict with, for `seeds`, `neighbors`
     ({seed: [{item, file, flip, d2, rmse} x k]}) and `canvas` (uint8 [rows * H, (k + 1) * W, C]); for `num`, `gen_to_train` and
-    `train_to_train` (int64 ndarrays) and `stats`.  With `outdir` the files of the module docstring are written."""
+    `train_to_train` (int64 ndarrays) and `stats`.  With `outdir` the files of the module docstring are written.
+    `space='vgg16'` searches in the detector's feature space (entries {item, file, flip, d2, dist}, float32 d2 arrays).  `detector` is what
+    `MetricOptions.detector` takes -- a callable, a TorchScript file, a dict -- or a directory holding vgg16.pt; `dataset_kwargs` /
+    `dataset_name` are what `dataset` was built from (the feature pass builds its own loader from them and keys its cache on them);
+    `cache_dir` overrides where features are cached."""
     from .train_parts.dataloaders import ResidentDataloader
+    if space not in SPACES:
+        raise ValueError(f'--space={space}: must be one of {", ".join(SPACES)}')
+    if space == 'vgg16':
+        if detector is None:
+            raise ValueError('--space=vgg16 needs --detector: a TorchScript vgg16.pt, a directory holding it, or a callable')
+        if res is not None:
+            raise ValueError('--res cannot be combined with --space=vgg16: the detector sees full-size images')
+        if dataset_kwargs is None:
+            raise ValueError('--space=vgg16 needs dataset_kwargs: the feature pass builds its own loader of the data set')
     if seeds is None and num is None:
         raise ValueError('one of --seeds and --num is required')
     if num is not None and int(num) < 1:
@@ -148,6 +284,9 @@ def nearest_training_images(G, dataset, seeds=None, num=None, k=5, res=None, tru
         label[:, class_idx] = 1
     elif class_idx is not None:
         print('warn: --class=lbl ignored when running on an unconditional network')
+    if space == 'vgg16':
+        return _feature_space(G, dataset, label, seeds, num, k, truncation_psi, noise_mode, batch, outdir, device, max_gib, detector, dataset_kwargs,
+                              dataset_name, cache_dir)
 
     loader = ResidentDataloader(dataset, sampler=(), batch_size=1, device=device, max_gib=max_gib)
     raw, slot, flip = resident_set.tables(dataset)
@@ -213,6 +352,8 @@ def parse_args(argv=None):
     ap.add_argument('--seeds', type=num_range, help='seeds whose images get a row of neighbours')
     ap.add_argument('--num', type=int, help='distance statistics over the images of seeds 0..N-1')
     ap.add_argument('--k', type=int, default=5, help=f'neighbours per image, 1 to {nn_u8.MAX_K} (default: 5)')
+    ap.add_argument('--space', choices=SPACES, default='pixel', help='where distances are taken: pixel bytes, or vgg16.pt features (default: pixel)')
+    ap.add_argument('--detector', help='with --space=vgg16: the local TorchScript vgg16.pt, or a directory holding it')
     ap.add_argument('--res', type=int, help='compare box-reduced copies of this resolution (a power of two; default: full size)')
     ap.add_argument('--data', help='data set to search, folder or zip (default: the run\'s data.dataset_path)')
     ap.add_argument('--mirror', type=int, choices=(0, 1), help='whether the data set holds the x-flips (default: the run\'s data.mirror)')
@@ -232,6 +373,13 @@ def parse_args(argv=None):
         ap.error('--res must be a power of two, at least 4')
     if args.batch < 1:
         ap.error('--batch must be at least 1')
+    if args.space == 'vgg16':
+        if args.detector is None:
+            ap.error('--space=vgg16 needs --detector: the TorchScript vgg16.pt, or a directory holding it')
+        if not os.path.exists(args.detector):
+            ap.error(f'--detector={args.detector}: no such TorchScript file or directory (detectors are not downloaded in this build)')
+        if args.res is not None:
+            ap.error('--res cannot be combined with --space=vgg16: the detector sees full-size images')
     if not os.path.isfile(args.snapshot):
         ap.error(f'--snapshot={args.snapshot}: no such file')
     if args.mirror is not None:
@@ -252,8 +400,10 @@ def run_nearest_neighbors(argv=None):
     print('Dataset options:', kw)
     dataset = datasets[config.data.dataset](**kw)
     try:
+        feature = dict(space=args.space, detector=args.detector, dataset_kwargs=kw, dataset_name=config.data.dataset) if args.space == 'vgg16' else {}
         result = nearest_training_images(G, dataset, seeds=args.seeds, num=args.num, k=args.k, res=args.res, truncation_psi=args.truncation_psi,
-                                         noise_mode=args.noise_mode, class_idx=args.class_idx, batch=args.batch, outdir=args.outdir, device=device)
+                                         noise_mode=args.noise_mode, class_idx=args.class_idx, batch=args.batch, outdir=args.outdir, device=device,
+                                         **feature)
     finally:
         dataset.close()
     if 'stats' in result:
