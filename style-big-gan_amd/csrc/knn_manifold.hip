@@ -19,28 +19,27 @@
 // (8 lanes per row), issue early / write late, two LDS stages, one barrier per K-step.  LDS image per operand: [k-group 0..7][130
 // cells of 16 B]: the 2-cell pad makes the 16 cells a quarter-wave writes (2 rows x 8 k-groups) distinct mod 16, and a fragment read
 // touches 16 consecutive cells: both conflict-free.
-// A workgroup owns one query tile and a contiguous run of manifold tiles; at the end the lists of the 8 lane groups that share a query
-// are merged through LDS.  With one run per query tile the result is written directly (variant `single`); otherwise every run writes
-// its partial list / flag / {count, minimum} pair to the workspace and a second launch merges the runs in index order (`split` +
-// `merge`).  The k smallest of a multiset, an OR, an integer sum and a minimum do not depend on the order, and there are no atomics: two
-// runs give the same bits.
-// Top-k candidates are 64-bit keys (uint64(bits(d2)) << 32) | row.  d2 is never negative and never -0: n(x) + n(y) is a sum of squares,
-// so +0 or positive; a - b of two floats is -0 only for a = -0, b = +0 (a - a is +0 under round-to-nearest), so (n(x) + n(y)) - 2 s is
-// +0, positive, or negative and then replaced by the +0 of fmaxf(., 0).  The bits of such floats order as unsigned integers the way the
-// values do, so one unsigned compare orders by (d2, row) and a tie goes to the lower row.  A row past the end, or equal to exclude[q],
-// gets the all-ones key and never enters a list.  Keys of distinct rows are distinct, so the k smallest do not depend on the order.
+// A workgroup owns one query tile and a contiguous run of manifold tiles.  With one run per query tile the result is written directly
+// (variant `single`); otherwise every run writes its partial list / flag / {count, minimum} pair to the workspace and a second launch
+// merges the runs in index order (`split` + `merge`).  The lists, their keys, the split and the merge of lists are knn_select.h's, with
+// its order and tie rules; an OR, an integer sum and a minimum do not depend on the order either, and there are no atomics: two runs
+// give the same bits.
+// Top-k candidates are knn_select.h's KeyF32, which needs d2 never negative and never -0: n(x) + n(y) is a sum of squares, so +0 or
+// positive; a - b of two floats is -0 only for a = -0, b = +0 (a - a is +0 under round-to-nearest), so (n(x) + n(y)) - 2 s is +0,
+// positive, or negative and then replaced by the +0 of fmaxf(., 0).  A row past the end, or equal to exclude[q], gets the sentinel.
 // Launch-log key: kind SBG_K_PR, dims = {variant (0 single, 1 split, 2 merge, 3 norms), R, C, F, k, runs, 0 radius / 1 membership / 2 probe / 3 top-k}.
 #include "conv_common.h"
+#include "knn_select.h"
 #include "reduce.h"
 
 using namespace sbgconv;
+using namespace knnsel;
 
 namespace {
 
 constexpr int kPrSingle = 0, kPrSplit = 1, kPrMerge = 2, kPrNorms = 3;
 constexpr int kRadius = 0, kMember = 1, kProbe = 2, kTopk = 3;       // what the tile kernel reduces a query row's distances to (dims[6] of a record)
 
-constexpr int BT = 128;                     // tile side: manifold points and query rows
 constexpr int BK = 64;                      // K-step
 constexpr int KG = BK / 8;                  // 16-B k-groups per K-step
 constexpr int KGS = BT + 2;                 // cells per k-group (padded, see above)
@@ -50,14 +49,14 @@ constexpr int PARAM_OFF = 2 * STAGE;        // behind the two stages: norms and 
 constexpr int LDS_BYTES = PARAM_OFF + 2 * 2 * BT * 4;
 constexpr int kMaxK1 = 8;                   // k + 1 <= 8
 constexpr int kMaxTopk = 8;                 // top-k: 1 <= k <= 8
-constexpr uint64_t kNoKey = ~(uint64_t)0;   // top-k: no candidate
-constexpr int kTargetGroups = 512;          // workgroups to aim for: 256 CUs x 2 resident
 
 struct KnnArgs {
     const unsigned short* q; const unsigned short* m;     // query rows [R, F], manifold [C, F]
     const float* nq; const float* nm;                      // their squared norms
     const unsigned short* radius;                          // membership and probe: fp16 [C]
-    void* out; void* nearest = nullptr; void* part;        // nearest: the probe's second output, fp16 [R]; top-k: out = d2 fp32 [R, k], nearest = index int32 [R, k]
+    union { void* out; float* d2; };                       // radius fp16 [R], membership uint8 [R], probe count int32 [R]; top-k: d2 [R, k]
+    union { void* nearest = nullptr; int32_t* index; };    // the probe's second output, fp16 [R]; top-k: index [R, k]
+    void* part;
     const int32_t* exclude = nullptr;                      // top-k: [R] or null
     int R, C, F, k, runs, ctiles, tiles_per_run;
 };
@@ -78,34 +77,6 @@ __global__ __launch_bounds__(256) void knn_norms_kernel(const unsigned short* __
     if (lane == 0) n[row] = s;
 }
 
-// keep the KL smallest, ascending; equal values are kept as often as they occur (kthvalue counts duplicates)
-template <int KL>
-__device__ __forceinline__ void list_insert(float (&L)[KL], float v)
-{
-    if (v < L[KL - 1]) {
-#pragma unroll
-        for (int t = 0; t < KL; t++) { const float lo = fminf(L[t], v); v = fmaxf(L[t], v); L[t] = lo; }
-    }
-}
-
-// top-k: keep the KL smallest keys, ascending; keys of distinct rows are distinct
-template <int KL>
-__device__ __forceinline__ void key_insert(uint64_t (&L)[KL], uint64_t v)
-{
-    if (v < L[KL - 1]) {
-#pragma unroll
-        for (int t = 0; t < KL; t++) { const uint64_t lo = L[t] < v ? L[t] : v; v = L[t] < v ? v : L[t]; L[t] = lo; }
-    }
-}
-
-__device__ __forceinline__ uint64_t topk_key(float d2, int row) { return ((uint64_t)__float_as_uint(d2) << 32) | (uint32_t)row; }
-
-__device__ __forceinline__ void topk_store(uint64_t key, float* d2, int32_t* index)
-{
-    *d2 = __uint_as_float((uint32_t)(key >> 32));
-    *index = (int32_t)(uint32_t)key;
-}
-
 __device__ __forceinline__ float dist2(float nx, float ny, float s)
 {
 #pragma clang fp contract(off)
@@ -115,6 +86,21 @@ __device__ __forceinline__ float dist2(float nx, float ny, float s)
 __device__ __forceinline__ float dist_f16(float d2) { return (float)(_Float16)sqrtf(d2); }
 
 struct ProbePart { int count; float d2; };                 // a run's share of a probe row: balls that hold it, smallest d2
+
+// What the radius mode writes for row q from its merged list of d2 (a multiset: kthvalue counts duplicates): the k-th entry, as fp16
+struct RadiusFinish {
+    using type = float;
+    static constexpr float none = __builtin_inff();
+    unsigned short* out; int k;
+    template <int KL>
+    __device__ __forceinline__ void operator()(int q, const float (&M)[KL]) const
+    {
+        float r = M[0];         // a select of loaded values: written `(t == k) ? M[t] : r` it compiles to one load at a computed address and M goes to scratch
+#pragma unroll
+        for (int t = 1; t < KL; t++) { const float m = M[t]; r = (t == k) ? m : r; }
+        out[q] = f32_to_f16_bits(sqrtf(r));
+    }
+};
 
 template <int KL, int MODE>
 __device__ __forceinline__ void knn_tile_body(const KnnArgs& p)
@@ -154,7 +140,7 @@ __device__ __forceinline__ void knn_tile_body(const KnnArgs& p)
             const int r = q0 + wp + 16 * j + fr;
             excl[j] = (r < p.R && p.exclude) ? p.exclude[r] : -1;
 #pragma unroll
-            for (int t = 0; t < KL; t++) T[j][t] = kNoKey;
+            for (int t = 0; t < KL; t++) T[j][t] = KeyF32::none;
         }
     }
 
@@ -252,10 +238,10 @@ __device__ __forceinline__ void knn_tile_body(const KnnArgs& p)
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
                     const float d2 = dist2(nqv[j], nmv, acc[i][j][e]);
-                    if constexpr (TOPK) { const int row = c0 + col; key_insert<KL>(T[j], (row < p.C && row != excl[j]) ? topk_key(d2, row) : kNoKey); }
+                    if constexpr (TOPK) { const int row = c0 + col; keep_smallest<KL>(T[j], (row < p.C && row != excl[j]) ? KeyF32::make(d2, row) : KeyF32::none); }
                     else if (MEMBER) inside[j] |= (dist_f16(d2) <= rv) ? 1 : 0;
                     else if (PROBE) { inside[j] += (dist_f16(d2) <= rv) ? 1 : 0; nearest[j] = fminf(nearest[j], d2); }
-                    else list_insert<KL>(L[j], d2);
+                    else keep_smallest<KL>(L[j], d2);
                 }
             }
         }
@@ -263,31 +249,8 @@ __device__ __forceinline__ void knn_tile_body(const KnnArgs& p)
 
     // merge the lane groups and the two manifold waves that share a query row; the staging area is free after the last barrier
     const int q = q0 + tid;
-    if constexpr (TOPK) {
-        constexpr int QS = 8 * KL + 1;                           // odd stride in 8-byte words
-        uint64_t* ms = reinterpret_cast<uint64_t*>(smem);        // [BT][8 lists][KL]; at KL = 8: 128 * 65 * 8 B = 66560 B, the two stages exactly
-        static_assert(BT * QS * 8 <= PARAM_OFF, "the top-k merge area must fit the staging area");
-        const int slot = (wave >> 1) * 4 + fg;
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-#pragma unroll
-            for (int t = 0; t < KL; t++) ms[(wp + 16 * j + fr) * QS + slot * KL + t] = T[j][t];
-        __syncthreads();
-        if (tid < BT && q < p.R) {
-            uint64_t M[KL];
-#pragma unroll
-            for (int t = 0; t < KL; t++) M[t] = kNoKey;
-            for (int s = 0; s < 8 * KL; s++) key_insert<KL>(M, ms[tid * QS + s]);
-            if (p.runs == 1) {
-#pragma unroll
-                for (int t = 0; t < KL; t++)
-                    if (t < p.k) topk_store(M[t], reinterpret_cast<float*>(p.out) + (int64_t)q * p.k + t, reinterpret_cast<int32_t*>(p.nearest) + (int64_t)q * p.k + t);
-            } else {
-                uint64_t* dst = reinterpret_cast<uint64_t*>(p.part) + ((int64_t)q * p.runs + run) * KL;
-#pragma unroll
-                for (int t = 0; t < KL; t++) dst[t] = M[t];
-            }
-        }
+    if constexpr (TOPK) {       // at KL = 8 the image is 128 * 65 * 8 B = 66560 B, the two stages exactly
+        finish_run<KL, PARAM_OFF>(smem, T, q0, p.R, p.runs, run, reinterpret_cast<uint64_t*>(p.part), KeyFinish<KeyF32>{p.d2, p.index, p.k});
     } else if (MEMBER) {
         int* fl = reinterpret_cast<int*>(smem);                  // [manifold wave][BT]
 #pragma unroll
@@ -326,30 +289,7 @@ __device__ __forceinline__ void knn_tile_body(const KnnArgs& p)
             }
         }
     } else {
-        constexpr int QS = 8 * KL + 1;                           // odd stride: the merging lanes hit distinct banks
-        float* ms = reinterpret_cast<float*>(smem);              // [BT][8 lists][KL]
-        const int slot = (wave >> 1) * 4 + fg;
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-#pragma unroll
-            for (int t = 0; t < KL; t++) ms[(wp + 16 * j + fr) * QS + slot * KL + t] = L[j][t];
-        __syncthreads();
-        if (tid < BT && q < p.R) {
-            float M[KL];
-#pragma unroll
-            for (int t = 0; t < KL; t++) M[t] = __builtin_inff();
-            for (int s = 0; s < 8 * KL; s++) list_insert<KL>(M, ms[tid * QS + s]);
-            if (p.runs == 1) {
-                float r = M[0];
-#pragma unroll
-                for (int t = 1; t < KL; t++) r = (t == p.k) ? M[t] : r;
-                reinterpret_cast<unsigned short*>(p.out)[q] = f32_to_f16_bits(sqrtf(r));
-            } else {
-                float* dst = reinterpret_cast<float*>(p.part) + ((int64_t)q * p.runs + run) * KL;
-#pragma unroll
-                for (int t = 0; t < KL; t++) dst[t] = M[t];
-            }
-        }
+        finish_run<KL, PARAM_OFF>(smem, L, q0, p.R, p.runs, run, reinterpret_cast<float*>(p.part), RadiusFinish{reinterpret_cast<unsigned short*>(p.out), p.k});
     }
 }
 
@@ -362,23 +302,7 @@ __global__ __launch_bounds__(256) void knn_probe_tile_kernel(KnnArgs p) { knn_ti
 template <int KL>
 __global__ __launch_bounds__(256, 2) void knn_topk_tile_kernel(KnnArgs p) { knn_tile_body<KL, kTopk>(p); }
 
-// Second stage of the split variant: one work-item per query row walks the runs in index order.
-template <int KL>
-__global__ __launch_bounds__(256) void knn_merge_radius_kernel(const float* __restrict__ part, unsigned short* __restrict__ out, int R, int runs, int k)
-{
-    const int q = blockIdx.x * 256 + threadIdx.x;
-    if (q >= R) return;
-    float M[KL];
-#pragma unroll
-    for (int t = 0; t < KL; t++) M[t] = __builtin_inff();
-    const float* src = part + (int64_t)q * runs * KL;
-    for (int s = 0; s < runs * KL; s++) list_insert<KL>(M, src[s]);
-    float r = M[0];
-#pragma unroll
-    for (int t = 1; t < KL; t++) r = (t == k) ? M[t] : r;
-    out[q] = f32_to_f16_bits(sqrtf(r));
-}
-
+// Second stage of the split variant: one work-item per query row walks the runs in index order (the lists: knn_select.h's merge_runs).
 __global__ __launch_bounds__(256) void knn_merge_member_kernel(const unsigned char* __restrict__ part, unsigned char* __restrict__ out, int R, int runs)
 {
     const int q = blockIdx.x * 256 + threadIdx.x;
@@ -400,56 +324,34 @@ __global__ __launch_bounds__(256) void knn_merge_probe_kernel(const ProbePart* _
     nearest[q] = f32_to_f16_bits(sqrtf(v));
 }
 
-template <int KL>
-__global__ __launch_bounds__(256) void knn_merge_topk_kernel(const uint64_t* __restrict__ part, float* __restrict__ d2, int32_t* __restrict__ index, int R, int runs, int k)
+int list_len(int k) { return k + 1 <= 4 ? 4 : 8; }         // radius: the (k + 1)-th neighbour
+
+// The plan of a mode: its k limits, and what a run leaves per query row -- a list of floats (radius), one byte (membership; the bytes
+// of all rows together are rounded up to 16), a ProbePart (probe), a list of 64-bit keys (top-k).
+bool knn_plan(int R, int C, int k, int mode, RunPlan& pl)
 {
-    const int q = blockIdx.x * 256 + threadIdx.x;
-    if (q >= R) return;
-    uint64_t M[KL];
-#pragma unroll
-    for (int t = 0; t < KL; t++) M[t] = kNoKey;
-    const uint64_t* src = part + (int64_t)q * runs * KL;
-    for (int s = 0; s < runs * KL; s++) key_insert<KL>(M, src[s]);
-#pragma unroll
-    for (int t = 0; t < KL; t++)
-        if (t < k) topk_store(M[t], d2 + (int64_t)q * k + t, index + (int64_t)q * k + t);
-}
-
-struct KnnPlan { int rtiles, ctiles, tiles_per_run, runs; int64_t nq_off, nm_off, part_off, bytes; };
-
-int list_len(int k) { return k + 1 <= 4 ? 4 : 8; }
-int topk_list_len(int k) { return k == 1 ? 1 : k <= 4 ? 4 : 8; }
-
-// Runs per query tile: enough workgroups to fill the chip twice when the query tiles alone do not.  A function of the shape only, so
-// the workspace query and the launch agree and a result does not depend on the device it ran on.
-bool knn_plan(int R, int C, int k, int mode, KnnPlan& pl)
-{
-    if (R < 1 || C < 1 || R > (1 << 24) || C > (1 << 24)) return false;
     if (mode == kTopk ? (k < 1 || k > kMaxTopk) : (k < 0 || k + 1 > kMaxK1)) return false;
-    pl.rtiles = (R + BT - 1) / BT;
-    pl.ctiles = (C + BT - 1) / BT;
-    int want = kTargetGroups / pl.rtiles;
-    want = want < 1 ? 1 : (want > pl.ctiles ? pl.ctiles : want);
-    pl.tiles_per_run = (pl.ctiles + want - 1) / want;
-    pl.runs = (pl.ctiles + pl.tiles_per_run - 1) / pl.tiles_per_run;
-    auto up16 = [](int64_t v) { return (v + 15) & ~(int64_t)15; };
-    pl.nq_off = 0;
-    pl.nm_off = up16(4 * (int64_t)R);
-    pl.part_off = pl.nm_off + up16(4 * (int64_t)C);
-    // partial results of the runs: a list of floats per (row, run) for the radius, one byte per (run, row) for the membership, one
-    // ProbePart per (run, row) for the probe, a list of 64-bit keys per (row, run) for the top-k
-    const int64_t part = mode == kMember ? up16((int64_t)R * pl.runs) : mode == kProbe ? (int64_t)sizeof(ProbePart) * R * pl.runs
-                         : mode == kTopk ? 8 * (int64_t)R * pl.runs * topk_list_len(k) : 4 * (int64_t)R * pl.runs * list_len(k);
-    pl.bytes = pl.part_off + (pl.runs > 1 ? part : 0);
+    const int64_t part = mode == kMember ? 1 : mode == kProbe ? (int64_t)sizeof(ProbePart) : mode == kTopk ? 8 * topk_list_len(k) : 4 * list_len(k);
+    if (!plan_runs(R, C, 4, part, pl)) return false;
+    if (mode == kMember) pl.bytes = up16(pl.bytes);
     return true;
 }
 
-int knn_check(const char* what, const void* q, const void* m, const void* out, const void* ws, int R, int C, int64_t F, int k, int mode, KnnPlan& pl)
+// one_excluded: a top-k search that may skip one manifold row per query
+int knn_check(const char* what, const void* q, const void* m, const void* out, const void* ws, int R, int C, int64_t F, int k, int mode, bool one_excluded,
+              RunPlan& pl)
 {
     SBG_CHECK(q && m && out && ws, "%s: null pointer", what);
-    SBG_CHECK(k >= 0 && k + 1 <= kMaxK1, "%s: k + 1 = %d neighbours, at most %d are supported", what, k + 1, kMaxK1);
-    SBG_CHECK(R >= 1 && C >= 1 && R <= (1 << 24) && C <= (1 << 24), "%s: bad sizes R=%d C=%d", what, R, C);
-    SBG_CHECK(C >= k + 1, "%s: the manifold has %d points, the (k + 1)-th neighbour needs %d", what, C, k + 1);
+    if (mode == kTopk) {
+        SBG_CHECK(k >= 1 && k <= kMaxTopk, "%s: k = %d neighbours, 1 to %d are supported", what, k, kMaxTopk);
+        SBG_CHECK(R >= 1 && C >= 1 && R <= kMaxRows && C <= kMaxRows, "%s: bad sizes Q=%d M=%d (1 to 2^24 each)", what, R, C);
+        SBG_CHECK(C - (one_excluded ? 1 : 0) >= k, "%s: the manifold has %d rows%s, %d neighbours need %d", what, C, one_excluded ? " and one may be excluded" : "", k,
+                  k + (one_excluded ? 1 : 0));
+    } else {
+        SBG_CHECK(k >= 0 && k + 1 <= kMaxK1, "%s: k + 1 = %d neighbours, at most %d are supported", what, k + 1, kMaxK1);
+        SBG_CHECK(R >= 1 && C >= 1 && R <= kMaxRows && C <= kMaxRows, "%s: bad sizes R=%d C=%d", what, R, C);
+        SBG_CHECK(C >= k + 1, "%s: the manifold has %d points, the (k + 1)-th neighbour needs %d", what, C, k + 1);
+    }
     SBG_CHECK(F >= 8 && F % 8 == 0 && F <= (1 << 24), "%s: the feature width %lld must be a multiple of 8 (16-byte pieces) in [8, 2^24]", what, (long long)F);
     SBG_CHECK(sbg_aligned16(q) && sbg_aligned16(m) && sbg_aligned16(ws), "%s: features and workspace must be 16-byte aligned", what);
     SBG_CHECK(knn_plan(R, C, k, mode, pl), "%s: bad sizes", what);
@@ -473,7 +375,7 @@ constexpr auto knn_tile_kernel_of()
 }
 
 template <int KL, int MODE>
-int knn_launch_tiles(const KnnArgs& a, const KnnPlan& pl, hipStream_t s)
+int knn_launch_tiles(const KnnArgs& a, const RunPlan& pl, hipStream_t s)
 {
     constexpr auto kernel = knn_tile_kernel_of<KL, MODE>();
     if (!SBG_RAISE_LDS_ONCE(kernel, LDS_BYTES))
@@ -486,12 +388,12 @@ int knn_launch_tiles(const KnnArgs& a, const KnnPlan& pl, hipStream_t s)
 }
 
 // What the entry points share: argument checks, the plan, the norm passes and the tile launch.  On SBG_OK with pl.runs > 1 the
-// caller launches its merge over a.part.
+// caller launches its merge over a.part.  The caller has set the fields of `a` that only its mode has (nearest | index, exclude).
 template <int MODE>
 int knn_run(const char* what, const void* q, const void* m, const void* radius, int R, int C, int64_t F, int k, void* out, void* workspace,
-            hipStream_t s, KnnArgs& a, KnnPlan& pl)
+            hipStream_t s, KnnArgs& a, RunPlan& pl)
 {
-    const int rc = knn_check(what, q, m, out, workspace, R, C, F, k, MODE, pl);
+    const int rc = knn_check(what, q, m, out, workspace, R, C, F, k, MODE, a.exclude != nullptr, pl);
     if (rc != SBG_OK) return rc;
     char* ws = (char*)workspace;
     a.q = (const unsigned short*)q; a.m = (const unsigned short*)m;
@@ -502,15 +404,16 @@ int knn_run(const char* what, const void* q, const void* m, const void* radius, 
     if (st != SBG_OK) return st;
     st = knn_norms(a.m, (float*)(ws + pl.nm_off), C, a.F, s);
     if (st != SBG_OK) return st;
-    if (MODE != kRadius) return knn_launch_tiles<4, MODE>(a, pl, s);
-    return list_len(k) == 4 ? knn_launch_tiles<4, kRadius>(a, pl, s) : knn_launch_tiles<8, kRadius>(a, pl, s);
+    if constexpr (MODE == kTopk) return with_list_len(topk_list_len(k), [&](auto kl) { return knn_launch_tiles<decltype(kl)::value, kTopk>(a, pl, s); });
+    else if constexpr (MODE != kRadius) return knn_launch_tiles<4, MODE>(a, pl, s);
+    else return list_len(k) == 4 ? knn_launch_tiles<4, kRadius>(a, pl, s) : knn_launch_tiles<8, kRadius>(a, pl, s);
 }
 
 } // namespace
 
 extern "C" int64_t sbg_knn_workspace(int R, int C, int k, int membership)
 {
-    KnnPlan pl;
+    RunPlan pl;
     if (!knn_plan(R, C, membership ? 0 : k, membership ? kMember : kRadius, pl)) return -1;
     return pl.bytes;
 }
@@ -518,15 +421,13 @@ extern "C" int64_t sbg_knn_workspace(int R, int C, int k, int membership)
 extern "C" int sbg_knn_kth_radius(const void* rows, const void* manifold, int R, int C, int64_t F, int k, void* out, void* workspace, sbg_stream_t stream)
 {
     hipStream_t s = (hipStream_t)stream;
-    KnnArgs a; KnnPlan pl;
+    KnnArgs a; RunPlan pl;
     const int st = knn_run<kRadius>("knn_kth_radius", rows, manifold, nullptr, R, C, F, k, out, workspace, s, a, pl);
     if (st != SBG_OK) return st;
     if (pl.runs > 1) {
         const int KL = list_len(k);
         SbgProfScope prof(s, SBG_K_PR, 0.0, 4.0 * R * (double)pl.runs * KL + 2.0 * R, {kPrMerge, R, C, a.F, k, pl.runs, 0});
-        if (KL == 4) SBG_LAUNCH(knn_merge_radius_kernel<4>, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, s, (const float*)a.part, (unsigned short*)out, R, pl.runs, k);
-        else         SBG_LAUNCH(knn_merge_radius_kernel<8>, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, s, (const float*)a.part, (unsigned short*)out, R, pl.runs, k);
-        SBG_HIP_LAUNCH_CHECK();
+        return merge_runs(KL, a.part, R, pl.runs, RadiusFinish{(unsigned short*)out, k}, s);       // KL = 1 is built and never taken here
     }
     return SBG_OK;
 }
@@ -536,7 +437,7 @@ extern "C" int sbg_knn_in_manifold(const void* probes, const void* manifold, con
 {
     SBG_CHECK(radius, "knn_in_manifold: null pointer");
     hipStream_t s = (hipStream_t)stream;
-    KnnArgs a; KnnPlan pl;
+    KnnArgs a; RunPlan pl;
     const int st = knn_run<kMember>("knn_in_manifold", probes, manifold, radius, P, C, F, 0, out, workspace, s, a, pl);
     if (st != SBG_OK) return st;
     if (pl.runs > 1) {
@@ -549,7 +450,7 @@ extern "C" int sbg_knn_in_manifold(const void* probes, const void* manifold, con
 
 extern "C" int64_t sbg_knn_probe_workspace(int P, int C)
 {
-    KnnPlan pl;
+    RunPlan pl;
     if (!knn_plan(P, C, 0, kProbe, pl)) return -1;
     return pl.bytes;
 }
@@ -559,7 +460,7 @@ extern "C" int sbg_knn_probe(const void* probes, const void* manifold, const voi
 {
     SBG_CHECK(radius && nearest, "knn_probe: null pointer");
     hipStream_t s = (hipStream_t)stream;
-    KnnArgs a; KnnPlan pl;
+    KnnArgs a; RunPlan pl;
     a.nearest = nearest;
     const int st = knn_run<kProbe>("knn_probe", probes, manifold, radius, P, C, F, 0, count, workspace, s, a, pl);
     if (st != SBG_OK) return st;
@@ -574,7 +475,7 @@ extern "C" int sbg_knn_probe(const void* probes, const void* manifold, const voi
 
 extern "C" int64_t sbg_knn_topk_workspace(int Q, int M, int k)
 {
-    KnnPlan pl;
+    RunPlan pl;
     if (!knn_plan(Q, M, k, kTopk, pl)) return -1;
     return pl.bytes;
 }
@@ -582,38 +483,16 @@ extern "C" int64_t sbg_knn_topk_workspace(int Q, int M, int k)
 extern "C" int sbg_knn_topk(const void* queries, const void* manifold, int Q, int M, int64_t F, int k, const int32_t* exclude, float* d2, int32_t* index,
                             void* workspace, sbg_stream_t stream)
 {
-    const char* what = "knn_topk";
+    SBG_CHECK(index, "knn_topk: null pointer");
     hipStream_t s = (hipStream_t)stream;
-    SBG_CHECK(queries && manifold && d2 && index && workspace, "%s: null pointer", what);
-    SBG_CHECK(k >= 1 && k <= kMaxTopk, "%s: k = %d neighbours, 1 to %d are supported", what, k, kMaxTopk);
-    SBG_CHECK(Q >= 1 && M >= 1 && Q <= (1 << 24) && M <= (1 << 24), "%s: bad sizes Q=%d M=%d (1 to 2^24 each)", what, Q, M);
-    SBG_CHECK(M - (exclude ? 1 : 0) >= k, "%s: the manifold has %d rows%s, %d neighbours need %d", what, M, exclude ? " and one may be excluded" : "", k,
-              k + (exclude ? 1 : 0));
-    SBG_CHECK(F >= 8 && F % 8 == 0 && F <= (1 << 24), "%s: the feature width %lld must be a multiple of 8 (16-byte pieces) in [8, 2^24]", what, (long long)F);
-    SBG_CHECK(sbg_aligned16(queries) && sbg_aligned16(manifold) && sbg_aligned16(workspace), "%s: features and workspace must be 16-byte aligned", what);
-    KnnPlan pl;
-    SBG_CHECK(knn_plan(Q, M, k, kTopk, pl), "%s: bad sizes", what);
-
-    char* ws = (char*)workspace;
-    KnnArgs a;
-    a.q = (const unsigned short*)queries; a.m = (const unsigned short*)manifold;
-    a.nq = (const float*)(ws + pl.nq_off); a.nm = (const float*)(ws + pl.nm_off); a.radius = nullptr;
-    a.out = d2; a.nearest = index; a.part = ws + pl.part_off; a.exclude = exclude;
-    a.R = Q; a.C = M; a.F = (int)F; a.k = k; a.runs = pl.runs; a.ctiles = pl.ctiles; a.tiles_per_run = pl.tiles_per_run;
-    int st = knn_norms(a.q, (float*)(ws + pl.nq_off), Q, a.F, s);
-    if (st != SBG_OK) return st;
-    st = knn_norms(a.m, (float*)(ws + pl.nm_off), M, a.F, s);
-    if (st != SBG_OK) return st;
-    const int KL = topk_list_len(k);
-    st = KL == 1 ? knn_launch_tiles<1, kTopk>(a, pl, s) : KL == 4 ? knn_launch_tiles<4, kTopk>(a, pl, s) : knn_launch_tiles<8, kTopk>(a, pl, s);
+    KnnArgs a; RunPlan pl;
+    a.index = index; a.exclude = exclude;
+    const int st = knn_run<kTopk>("knn_topk", queries, manifold, nullptr, Q, M, F, k, d2, workspace, s, a, pl);
     if (st != SBG_OK) return st;
     if (pl.runs > 1) {
+        const int KL = topk_list_len(k);
         SbgProfScope prof(s, SBG_K_PR, 0.0, 8.0 * Q * (double)pl.runs * KL + 8.0 * Q * k, {kPrMerge, Q, M, a.F, k, pl.runs, kTopk});
-        const dim3 grid((unsigned)((Q + 255) / 256));
-        if (KL == 1)      SBG_LAUNCH(knn_merge_topk_kernel<1>, grid, dim3(256), 0, s, (const uint64_t*)a.part, d2, index, Q, pl.runs, k);
-        else if (KL == 4) SBG_LAUNCH(knn_merge_topk_kernel<4>, grid, dim3(256), 0, s, (const uint64_t*)a.part, d2, index, Q, pl.runs, k);
-        else              SBG_LAUNCH(knn_merge_topk_kernel<8>, grid, dim3(256), 0, s, (const uint64_t*)a.part, d2, index, Q, pl.runs, k);
-        SBG_HIP_LAUNCH_CHECK();
+        return merge_runs(KL, a.part, Q, pl.runs, KeyFinish<KeyF32>{d2, index, k}, s);
     }
     return SBG_OK;
 }

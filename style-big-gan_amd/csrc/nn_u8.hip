@@ -10,7 +10,7 @@
 // (variant WIDE = false).
 //
 // Launches: a norm pass per operand (one wave per row), the tile kernel, and -- when the stored rows are split over workgroups -- a
-// merge.  The tile kernel is knn_manifold.hip's: workgroup = 256 lanes = 4 waves, tile 128 stored rows (MFMA A operand, rows of the
+// merge.  The tile kernel has knn_manifold.hip's frame: workgroup = 256 lanes = 4 waves, tile 128 stored rows (MFMA A operand, rows of the
 // accumulator = registers of a lane) x 128 queries (B operand, accumulator column = lane & 15), K-step 256 bytes = 4 MFMA steps
 // (the kernel waits on memory, not on the matrix cores: a long K-step keeps 64 KB in flight per workgroup and halves the barriers).
 // Both operands are staged by one rule (lane group g of MFMA step ks takes bytes [64 ks + 16 g, +16) of the K-step of its row), so the
@@ -18,22 +18,19 @@
 // issue early / write late, two LDS stages, one barrier per K-step; LDS image per operand [k-group 0..15][129 cells of 16 B]: the
 // 1-cell pad makes the 16 cells a quarter-wave writes (one row x 16 k-groups) distinct mod 16, and a fragment read touches 16
 // consecutive cells: both conflict-free.
-// A candidate is the pair (d2, j) packed into one int64 key d2 << 24 | j (d2 < 2^38, j < 2^24), so one signed compare orders by
-// (d2, j) and ties go to the lower row.  A lane keeps, per query, an ascending list of the KL smallest keys in registers; a row that
-// does not exist or is the query's excluded row never enters.  A workgroup owns one query tile and a contiguous run of store tiles; at
-// the end the lists of the 8 lane groups that share a query are merged through LDS.  With one run per query tile the result is
-// written directly (`single`); otherwise every run writes its list to the workspace and a second launch merges the runs in index
-// order (`split` + `merge`).  The k smallest of a set of distinct keys do not depend on the order, the split is a function of the
-// shape alone and there are no atomics: two calls give the same bits.
+// A candidate is the pair (d2, j) as knn_select.h's KeyU8 (d2 < 2^38, j < 2^24); a row that does not exist or is the query's excluded
+// row gets the sentinel.  The lists a lane keeps per query, the split of the store tiles into runs and the merges (`single`, or
+// `split` + `merge`) are knn_select.h's, with its order and tie rules: two calls give the same bits.
 // Launch-log key: kind SBG_K_NN_U8, dims = {variant (0 norms, 1 single, 2 split, 3 merge), Q, M, F clipped to int, k, runs}.
-#include "sbg_common.h"
+#include "knn_select.h"
+
+using namespace knnsel;
 
 namespace {
 
 constexpr int kNnNorms = 0, kNnSingle = 1, kNnSplit = 2, kNnMerge = 3;
 
-constexpr int BT = 128;                     // tile side: stored rows and queries
-constexpr int BK = 256;                     // K-step in bytes: four MFMA steps of 64
+constexpr int BK = 256;                    // K-step in bytes: four MFMA steps of 64
 constexpr int KG = BK / 16;                 // 16-B k-groups per K-step
 constexpr int KGS = BT + 1;                 // cells per k-group (padded)
 constexpr int OP_BYTES = KG * KGS * 16;     // one operand of one stage
@@ -41,11 +38,8 @@ constexpr int STAGE = 2 * OP_BYTES;
 constexpr int PARAM_OFF = 2 * STAGE;        // behind the two stages: norms of the store tile, double-buffered by tile parity
 constexpr int LDS_BYTES = PARAM_OFF + 2 * BT * 8;
 constexpr int kMaxK = 8;
-constexpr int kTargetGroups = 512;          // workgroups to aim for: 256 CUs x 2
 constexpr int kFlushSteps = 256;            // K-steps between two flushes: 256 * 256 = 65536 products <= 131071
 constexpr int64_t kMaxF = 3 * 1024 * 1024;
-constexpr int kIndexBits = 24;
-constexpr int64_t kNoKey = INT64_MAX;
 
 static_assert((int64_t)kFlushSteps * BK <= 131071, "an i32 accumulator holds at most 131071 products of 128 * 128");
 static_assert(kMaxF * 65025 < ((int64_t)1 << (63 - kIndexBits)), "d2 must fit the key above the row index");
@@ -88,16 +82,6 @@ __global__ __launch_bounds__(256) void nn_norms_kernel(const uint8_t* __restrict
     if (lane == 0) n[row] = a2 - 256 * a1 + 16384 * F;
 }
 
-// keep the KL smallest keys, ascending; keys of distinct rows are distinct
-template <int KL>
-__device__ __forceinline__ void list_insert(int64_t (&L)[KL], int64_t v)
-{
-    if (v < L[KL - 1]) {
-#pragma unroll
-        for (int t = 0; t < KL; t++) { const int64_t lo = L[t] < v ? L[t] : v; v = L[t] < v ? v : L[t]; L[t] = lo; }
-    }
-}
-
 template <int KL, bool WIDE>
 __global__ __launch_bounds__(256) void nn_tile_kernel(NnArgs p)
 {
@@ -128,7 +112,7 @@ __global__ __launch_bounds__(256) void nn_tile_kernel(NnArgs p)
 #pragma unroll
     for (int j = 0; j < 4; j++)
 #pragma unroll
-        for (int t = 0; t < KL; t++) L[j][t] = kNoKey;
+        for (int t = 0; t < KL; t++) L[j][t] = KeyU8::none;
 
     const int nsteps = (int)((p.F + BK - 1) / BK);
     for (int tile = t_begin; tile < t_end; tile++) {
@@ -226,85 +210,20 @@ __global__ __launch_bounds__(256) void nn_tile_kernel(NnArgs p)
                     int64_t s = (int64_t)acc[i][j][e];
                     if (WIDE) s += (int64_t)wide[WIDE ? i : 0][WIDE ? j : 0][WIDE ? e : 0] << 16;
                     const int64_t d2 = nqv[j] + nmv - 2 * s;
-                    const int64_t key = (row < p.M && row != excl[j]) ? ((d2 << kIndexBits) | (int64_t)row) : kNoKey;
-                    list_insert<KL>(L[j], key);
+                    keep_smallest<KL>(L[j], (row < p.M && row != excl[j]) ? KeyU8::make(d2, row) : KeyU8::none);
                 }
             }
         }
     }
 
     // merge the lane groups and the two store waves that share a query; the staging area is free after the last barrier
-    constexpr int QS = 8 * KL + 1;                           // odd stride in 8-byte words
-    int64_t* ms = reinterpret_cast<int64_t*>(smem);          // [BT][8 lists][KL]
-    static_assert(BT * QS * 8 <= PARAM_OFF, "the merge area must fit the staging area");
-    const int slot = (wave >> 1) * 4 + fg;
-#pragma unroll
-    for (int j = 0; j < 4; j++)
-#pragma unroll
-        for (int t = 0; t < KL; t++) ms[(wp + 16 * j + fr) * QS + slot * KL + t] = L[j][t];
-    __syncthreads();
-    const int q = q0 + tid;
-    if (tid < BT && q < p.Q) {
-        int64_t T[KL];
-#pragma unroll
-        for (int t = 0; t < KL; t++) T[t] = kNoKey;
-        for (int s = 0; s < 8 * KL; s++) list_insert<KL>(T, ms[tid * QS + s]);
-        if (p.runs == 1) {
-#pragma unroll
-            for (int t = 0; t < KL; t++)
-                if (t < p.k) {
-                    p.d2[(int64_t)q * p.k + t] = T[t] >> kIndexBits;
-                    p.index[(int64_t)q * p.k + t] = (int32_t)(T[t] & ((1 << kIndexBits) - 1));
-                }
-        } else {
-            int64_t* dst = p.part + ((int64_t)q * p.runs + run) * KL;
-#pragma unroll
-            for (int t = 0; t < KL; t++) dst[t] = T[t];
-        }
-    }
+    finish_run<KL, PARAM_OFF>(smem, L, q0, p.Q, p.runs, run, p.part, KeyFinish<KeyU8>{p.d2, p.index, p.k});
 }
 
-// Second stage of the split variant: one work-item per query walks the runs in index order.
-template <int KL>
-__global__ __launch_bounds__(256) void nn_merge_kernel(const int64_t* __restrict__ part, int64_t* __restrict__ d2, int32_t* __restrict__ index, int Q, int runs, int k)
+// int64 norms; a run leaves a list of KL keys per query
+bool nn_plan(int Q, int M, int k, RunPlan& pl)
 {
-    const int q = blockIdx.x * 256 + threadIdx.x;
-    if (q >= Q) return;
-    int64_t T[KL];
-#pragma unroll
-    for (int t = 0; t < KL; t++) T[t] = kNoKey;
-    const int64_t* src = part + (int64_t)q * runs * KL;
-    for (int s = 0; s < runs * KL; s++) list_insert<KL>(T, src[s]);
-#pragma unroll
-    for (int t = 0; t < KL; t++)
-        if (t < k) {
-            d2[(int64_t)q * k + t] = T[t] >> kIndexBits;
-            index[(int64_t)q * k + t] = (int32_t)(T[t] & ((1 << kIndexBits) - 1));
-        }
-}
-
-struct NnPlan { int rtiles, ctiles, tiles_per_run, runs, KL; int64_t nq_off, nm_off, part_off, bytes; };
-
-int list_len(int k) { return k == 1 ? 1 : k <= 4 ? 4 : 8; }
-
-// Runs per query tile: enough workgroups to fill the chip twice when the query tiles alone do not.  A function of the shape only, so
-// the workspace query and the launch agree and a result does not depend on the device it ran on.
-bool nn_plan(int Q, int M, int k, NnPlan& pl)
-{
-    if (Q < 1 || M < 1 || k < 1 || k > kMaxK || Q > (1 << kIndexBits) || M > (1 << kIndexBits)) return false;
-    pl.KL = list_len(k);
-    pl.rtiles = (Q + BT - 1) / BT;
-    pl.ctiles = (M + BT - 1) / BT;
-    int want = kTargetGroups / pl.rtiles;
-    want = want < 1 ? 1 : (want > pl.ctiles ? pl.ctiles : want);
-    pl.tiles_per_run = (pl.ctiles + want - 1) / want;
-    pl.runs = (pl.ctiles + pl.tiles_per_run - 1) / pl.tiles_per_run;
-    auto up16 = [](int64_t v) { return (v + 15) & ~(int64_t)15; };
-    pl.nq_off = 0;
-    pl.nm_off = up16(8 * (int64_t)Q);
-    pl.part_off = pl.nm_off + up16(8 * (int64_t)M);
-    pl.bytes = pl.part_off + (pl.runs > 1 ? 8 * (int64_t)Q * pl.runs * pl.KL : 0);
-    return true;
+    return k >= 1 && k <= kMaxK && plan_runs(Q, M, 8, 8 * topk_list_len(k), pl);
 }
 
 int nn_norms(const uint8_t* x, int64_t* n, int rows, int64_t F, int as_q, hipStream_t s)
@@ -318,7 +237,7 @@ int nn_norms(const uint8_t* x, int64_t* n, int rows, int64_t F, int as_q, hipStr
 }
 
 template <int KL, bool WIDE>
-int nn_launch_tiles(const NnArgs& a, const NnPlan& pl, hipStream_t s)
+int nn_launch_tiles(const NnArgs& a, const RunPlan& pl, hipStream_t s)
 {
     if (!SBG_RAISE_LDS_ONCE((nn_tile_kernel<KL, WIDE>), LDS_BYTES))
         return sbg_fail(SBG_ERR_LAUNCH, "u8_nn_topk: cannot raise the dynamic LDS limit to %d bytes", LDS_BYTES);
@@ -330,18 +249,11 @@ int nn_launch_tiles(const NnArgs& a, const NnPlan& pl, hipStream_t s)
     return SBG_OK;
 }
 
-template <int KL>
-int nn_launch_tiles_kl(const NnArgs& a, const NnPlan& pl, hipStream_t s)
-{
-    const bool wide = a.F > (int64_t)kFlushSteps * BK;
-    return wide ? nn_launch_tiles<KL, true>(a, pl, s) : nn_launch_tiles<KL, false>(a, pl, s);
-}
-
 } // namespace
 
 extern "C" int64_t sbg_u8_nn_workspace(int Q, int M, int k)
 {
-    NnPlan pl;
+    RunPlan pl;
     if (!nn_plan(Q, M, k, pl)) return -1;
     return pl.bytes;
 }
@@ -353,12 +265,12 @@ extern "C" int sbg_u8_nn_topk(const uint8_t* queries, const uint8_t* store, int 
     hipStream_t s = (hipStream_t)stream;
     SBG_CHECK(queries && store && d2 && index && workspace, "%s: null pointer", what);
     SBG_CHECK(k >= 1 && k <= kMaxK, "%s: k = %d neighbours, 1 to %d are supported", what, k, kMaxK);
-    SBG_CHECK(Q >= 1 && M >= 1 && Q <= (1 << kIndexBits) && M <= (1 << kIndexBits), "%s: bad sizes Q=%d M=%d (1 to 2^%d each)", what, Q, M, kIndexBits);
+    SBG_CHECK(Q >= 1 && M >= 1 && Q <= kMaxRows && M <= kMaxRows, "%s: bad sizes Q=%d M=%d (1 to 2^%d each)", what, Q, M, kIndexBits);
     SBG_CHECK(M - (exclude ? 1 : 0) >= k, "%s: the store has %d rows%s, %d neighbours need %d", what, M, exclude ? " and one may be excluded" : "", k,
               k + (exclude ? 1 : 0));
     SBG_CHECK(F >= 16 && F % 16 == 0 && F <= kMaxF, "%s: the row length %lld must be a multiple of 16 in [16, %lld]", what, (long long)F, (long long)kMaxF);
     SBG_CHECK(sbg_aligned16(queries) && sbg_aligned16(store) && sbg_aligned16(workspace), "%s: queries, store and workspace must be 16-byte aligned", what);
-    NnPlan pl;
+    RunPlan pl;
     SBG_CHECK(nn_plan(Q, M, k, pl), "%s: bad sizes", what);
 
     char* ws = (char*)workspace;
@@ -371,16 +283,16 @@ extern "C" int sbg_u8_nn_topk(const uint8_t* queries, const uint8_t* store, int 
     if (st != SBG_OK) return st;
     st = nn_norms(store, (int64_t*)(ws + pl.nm_off), M, F, 0, s);
     if (st != SBG_OK) return st;
-    st = pl.KL == 1 ? nn_launch_tiles_kl<1>(a, pl, s) : pl.KL == 4 ? nn_launch_tiles_kl<4>(a, pl, s) : nn_launch_tiles_kl<8>(a, pl, s);
+    const int KL = topk_list_len(k);
+    const bool wide = F > (int64_t)kFlushSteps * BK;
+    st = with_list_len(KL, [&](auto kl) {
+        return wide ? nn_launch_tiles<decltype(kl)::value, true>(a, pl, s) : nn_launch_tiles<decltype(kl)::value, false>(a, pl, s);
+    });
     if (st != SBG_OK) return st;
     if (pl.runs > 1) {
         const int Fc = (int)(F > INT32_MAX ? INT32_MAX : F);
-        SbgProfScope prof(s, SBG_K_NN_U8, 0.0, 8.0 * Q * (double)pl.runs * pl.KL + 12.0 * Q * k, {kNnMerge, Q, M, Fc, k, pl.runs});
-        const dim3 grid((unsigned)((Q + 255) / 256));
-        if (pl.KL == 1)      SBG_LAUNCH(nn_merge_kernel<1>, grid, dim3(256), 0, s, (const int64_t*)a.part, d2, index, Q, pl.runs, k);
-        else if (pl.KL == 4) SBG_LAUNCH(nn_merge_kernel<4>, grid, dim3(256), 0, s, (const int64_t*)a.part, d2, index, Q, pl.runs, k);
-        else                 SBG_LAUNCH(nn_merge_kernel<8>, grid, dim3(256), 0, s, (const int64_t*)a.part, d2, index, Q, pl.runs, k);
-        SBG_HIP_LAUNCH_CHECK();
+        SbgProfScope prof(s, SBG_K_NN_U8, 0.0, 8.0 * Q * (double)pl.runs * KL + 12.0 * Q * k, {kNnMerge, Q, M, Fc, k, pl.runs});
+        return merge_runs(KL, a.part, Q, pl.runs, KeyFinish<KeyU8>{d2, index, k}, s);
     }
     return SBG_OK;
 }

@@ -16,14 +16,19 @@ Device tensors must be fp16 and run the kernels; a missing kernel or an unsuppor
 CPU tensors run the same definition in torch (float64 sums rounded to fp32, then the steps above), so the metric's plumbing is testable
 without a GPU.
 """
+import types
+
 import torch
 
 from ... import _lib
+from . import _topk_common
 
 MAX_NEIGHBOURS = 8          # k + 1 <= 8 (csrc/knn_manifold.hip)
 MAX_TOPK = 8                # topk: 1 <= k <= 8
 MAX_ROWS = 1 << 24
 _CPU_ROWS = 1024            # rows per block of the CPU path
+_TOPK = types.SimpleNamespace(noun="manifold", rows="manifold rows", dtype=torch.float16, d2_dtype=torch.float32, max_k=MAX_TOPK, max_rows=MAX_ROWS,
+                              flatten=False, entry="sbg_knn_topk", workspace="sbg_knn_topk_workspace")
 
 
 def _check(rows, manifold, k):
@@ -131,38 +136,6 @@ def probe(probes, manifold, radius):
     return count, nearest
 
 
-def _check_topk(queries, manifold, k, exclude):
-    what = "knn_manifold.topk"
-    for name, t in (("queries", queries), ("manifold", manifold)):
-        if not isinstance(t, torch.Tensor):
-            raise RuntimeError(f"{what}: {name} must be a torch tensor, got {type(t).__name__}")
-    if queries.ndim != 2 or manifold.ndim != 2 or queries.shape[1] != manifold.shape[1]:
-        raise RuntimeError(f"{what}: expects [Q, F] and [M, F], got {tuple(queries.shape)} and {tuple(manifold.shape)}")
-    if queries.device != manifold.device:
-        raise RuntimeError(f"{what}: tensors on different devices ({queries.device}, {manifold.device})")
-    if queries.dtype != torch.float16 or manifold.dtype != torch.float16:
-        raise RuntimeError(f"{what}: expects float16, got {queries.dtype} and {manifold.dtype}")
-    if not isinstance(k, int) or not 1 <= k <= MAX_TOPK:
-        raise RuntimeError(f"{what}: k = {k} neighbours, 1 to {MAX_TOPK} are supported")
-    Q, F = queries.shape
-    M = manifold.shape[0]
-    if Q < 1 or F < 1:
-        raise RuntimeError(f"{what}: empty queries {tuple(queries.shape)}")
-    if exclude is not None:
-        if not isinstance(exclude, torch.Tensor) or exclude.dtype != torch.int32 or list(exclude.shape) != [Q]:
-            raise RuntimeError(f"{what}: exclude must be an int32 tensor {[Q]}, got {getattr(exclude, 'dtype', type(exclude).__name__)} "
-                               f"{list(getattr(exclude, 'shape', []))}")
-        if exclude.device != manifold.device:
-            raise RuntimeError(f"{what}: exclude is on {exclude.device}, the manifold on {manifold.device}")
-        if not exclude.is_contiguous():
-            raise RuntimeError(f"{what}: exclude must be dense; call .contiguous() first")
-    if M < k:
-        raise RuntimeError(f"{what}: the manifold has {M} rows, {k} neighbours need {k}")
-    if exclude is not None and M == k and bool(((exclude >= 0) & (exclude < M)).any()):
-        raise RuntimeError(f"{what}: the manifold has {M} rows and one is excluded, {k} neighbours need {k + 1}")
-    return Q, M, F
-
-
 def topk(queries, manifold, k, exclude=None):
     """queries fp16 [Q, F], manifold fp16 [M, F], exclude int32 [Q] or None -> (d2 float32 [Q, k], index int32 [Q, k]): the k manifold rows
     nearest to every query by the module's d2 (the fp32 value; nothing is rounded to fp16), ascending by (d2, row), so a tie goes to the
@@ -172,7 +145,7 @@ def topk(queries, manifold, k, exclude=None):
     Non-finite features are outside the definition: on the device ``fmaxf(NaN, 0)`` is 0, so a NaN distance would rank first; callers
     check their features (``nearest_neighbors.py`` does, once per matrix)."""
     what = "knn_manifold.topk"
-    Q, M, F = _check_topk(queries, manifold, k, exclude)
+    Q, M, F = _topk_common.check(what, _TOPK, queries, manifold, k, exclude)
     if queries.device.type != "cuda":
         n_manifold = manifold.to(torch.float64).square().sum(1).to(torch.float32)
         y = manifold.to(torch.float64).T
@@ -183,29 +156,9 @@ def topk(queries, manifold, k, exclude=None):
             x = queries[lo:lo + _CPU_ROWS].to(torch.float64)
             n_rows = x.square().sum(1).to(torch.float32)
             d2 = ((n_rows[:, None] + n_manifold[None, :]) - 2 * (x @ y).to(torch.float32)).clamp_(min=0)
-            key = d2 if exclude is None else torch.where(cols[None, :] == exclude[lo:lo + _CPU_ROWS, None].to(torch.int64), float("inf"), d2)
-            order = torch.sort(key, dim=1, stable=True).indices[:, :k]          # stable: ties go to the lower row
-            d2_out[lo:lo + _CPU_ROWS] = d2.gather(1, order)
-            idx_out[lo:lo + _CPU_ROWS] = order.to(torch.int32)
+            d2_out[lo:lo + _CPU_ROWS], idx_out[lo:lo + _CPU_ROWS] = _topk_common.select(
+                d2, k, None if exclude is None else exclude[lo:lo + _CPU_ROWS], cols, float("inf"))
         return d2_out, idx_out
     if F % 8 != 0:
         raise RuntimeError(f"{what}: the feature width {F} must be a multiple of 8 (16-byte pieces) for the device path")
-    if Q > MAX_ROWS or M > MAX_ROWS:
-        raise RuntimeError(f"{what}: {Q} queries / {M} manifold rows, at most {MAX_ROWS} each for the device path")
-    for name, t in (("queries", queries), ("manifold", manifold)):
-        if not t.is_contiguous():
-            raise RuntimeError(f"{what}: {name} must be dense (shape {list(t.shape)}, strides {list(t.stride())}); call .contiguous() first")
-        if t.data_ptr() % 16:
-            raise RuntimeError(f"{what}: {name} must be 16-byte aligned for the device path")
-    if exclude is not None and M == k:
-        exclude = None          # _check_topk has seen that no entry lies in [0, M)
-    lib = _lib.load()
-    nbytes = lib.sbg_knn_topk_workspace(Q, M, k)
-    if nbytes < 0:
-        raise RuntimeError(f"{what}: unsupported sizes Q={Q} M={M} k={k}")
-    ws = _lib.workspace(nbytes, queries.device, "sbg_knn_topk_workspace")
-    d2 = torch.empty([Q, k], dtype=torch.float32, device=queries.device)
-    index = torch.empty([Q, k], dtype=torch.int32, device=queries.device)
-    _lib.check(lib.sbg_knn_topk(queries.data_ptr(), manifold.data_ptr(), Q, M, F, k, _lib.ptr(exclude), d2.data_ptr(), index.data_ptr(), ws.data_ptr(),
-                                _lib.stream_ptr(queries.device)), "sbg_knn_topk")
-    return d2, index
+    return _topk_common.run_device(what, _TOPK, queries, manifold, Q, M, F, k, exclude)

@@ -12,53 +12,23 @@ Device tensors run the kernels (i8 matrix cores, int64 norms and distances); an 
 torch fallback.  ``topk_reference`` is the same semantics in torch int64 arithmetic, in row blocks; CPU tensors take it, so the tool's
 plumbing is testable without a GPU.
 """
+import types
+
 import torch
 
-from ... import _lib
+from . import _topk_common
 
 MAX_K = 8                       # csrc/nn_u8.hip
 MAX_F = 3 * 1024 * 1024
 MAX_ROWS = 1 << 24
 _REF_BYTES = 1 << 27            # int64 work set of one block of topk_reference
-
-
-def _check(queries, store, k, exclude, what):
-    for name, t in (("queries", queries), ("store", store)):
-        if not isinstance(t, torch.Tensor):
-            raise RuntimeError(f"{what}: {name} must be a torch tensor, got {type(t).__name__}")
-        if t.dtype != torch.uint8 or t.ndim < 2:
-            raise RuntimeError(f"{what}: {name} must be uint8 with at least 2 dimensions, got {t.dtype} {list(t.shape)}")
-        if not t.is_contiguous():
-            raise RuntimeError(f"{what}: {name} must be dense (shape {list(t.shape)}, strides {list(t.stride())}); call .contiguous() first")
-    if queries.device != store.device:
-        raise RuntimeError(f"{what}: queries are on {queries.device}, the store on {store.device}")
-    Q, M = queries.shape[0], store.shape[0]
-    if queries.shape[1:].numel() != store.shape[1:].numel():
-        raise RuntimeError(f"{what}: queries {list(queries.shape)} and store {list(store.shape)} differ in the row length")
-    F = store.shape[1:].numel()
-    if not isinstance(k, int) or not 1 <= k <= MAX_K:
-        raise RuntimeError(f"{what}: k = {k} neighbours, 1 to {MAX_K} are supported")
-    if Q < 1 or M < 1 or F < 1:
-        raise RuntimeError(f"{what}: empty queries {list(queries.shape)} or store {list(store.shape)}")
-    if exclude is not None:
-        if not isinstance(exclude, torch.Tensor):
-            raise RuntimeError(f"{what}: exclude must be a torch tensor, got {type(exclude).__name__}")
-        if exclude.dtype != torch.int32 or list(exclude.shape) != [Q]:
-            raise RuntimeError(f"{what}: exclude must be int32 {[Q]}, got {exclude.dtype} {list(exclude.shape)}")
-        if exclude.device != store.device:
-            raise RuntimeError(f"{what}: exclude is on {exclude.device}, the store on {store.device}")
-        if not exclude.is_contiguous():
-            raise RuntimeError(f"{what}: exclude must be dense; call .contiguous() first")
-    if M < k:
-        raise RuntimeError(f"{what}: the store has {M} rows, {k} neighbours need {k}")
-    if exclude is not None and M == k and bool(((exclude >= 0) & (exclude < M)).any()):
-        raise RuntimeError(f"{what}: the store has {M} rows and one is excluded, {k} neighbours need {k + 1}")
-    return Q, M, F
+_KIND = types.SimpleNamespace(noun="store", rows="stored rows", dtype=torch.uint8, d2_dtype=torch.int64, max_k=MAX_K, max_rows=MAX_ROWS,
+                              flatten=True, entry="sbg_u8_nn_topk", workspace="sbg_u8_nn_workspace")
 
 
 def topk_reference(queries, store, k, exclude=None):
     """the semantics of `topk` in torch int64 arithmetic on the tensors' own device, in row blocks -> (d2 int64 [Q, k], index int32 [Q, k])"""
-    Q, M, F = _check(queries, store, k, exclude, "nn_u8 topk_reference")
+    Q, M, F = _topk_common.check("nn_u8 topk_reference", _KIND, queries, store, k, exclude)
     q = queries.reshape(Q, F)
     s = store.reshape(M, F)
     cols = torch.arange(M, device=store.device)
@@ -74,11 +44,8 @@ def topk_reference(queries, store, k, exclude=None):
                 a = q[q0:q0 + qb, None, f0:f0 + fb].to(torch.int64)
                 b = s[None, m0:m0 + mb, f0:f0 + fb].to(torch.int64)
                 d2[:, m0:m0 + mb] += (a - b).square_().sum(2)
-        if exclude is not None:
-            d2 = torch.where(cols[None, :] == exclude[q0:q0 + qb, None].to(torch.int64), torch.iinfo(torch.int64).max, d2)
-        order = torch.sort(d2, dim=1, stable=True).indices[:, :k]           # stable: ties go to the lower row
-        d2_out[q0:q0 + qb] = d2.gather(1, order)
-        idx_out[q0:q0 + qb] = order.to(torch.int32)
+        d2_out[q0:q0 + qb], idx_out[q0:q0 + qb] = _topk_common.select(
+            d2, k, None if exclude is None else exclude[q0:q0 + qb], cols, torch.iinfo(torch.int64).max)
     return d2_out, idx_out
 
 
@@ -87,24 +54,9 @@ def topk(queries, store, k, exclude=None):
     the k nearest rows of every query, ascending by (d2, row).  Device tensors run the kernels on the current stream (F a multiple of 16,
     at most 3 * 2^20; 16-byte aligned; Q, M <= 2^24 -- anything else raises); CPU tensors take `topk_reference`."""
     what = "nn_u8 topk"
-    Q, M, F = _check(queries, store, k, exclude, what)
+    Q, M, F = _topk_common.check(what, _KIND, queries, store, k, exclude)
     if store.device.type != "cuda":
         return topk_reference(queries, store, k, exclude)
     if F % 16 != 0 or F > MAX_F:
         raise RuntimeError(f"{what}: the row length {F} must be a multiple of 16, at most {MAX_F}, for the device path")
-    if Q > MAX_ROWS or M > MAX_ROWS:
-        raise RuntimeError(f"{what}: {Q} queries / {M} stored rows, at most {MAX_ROWS} each for the device path")
-    if queries.data_ptr() % 16 or store.data_ptr() % 16:
-        raise RuntimeError(f"{what}: queries and store must be 16-byte aligned for the device path")
-    if exclude is not None and M == k:
-        exclude = None          # _check has seen that no entry lies in [0, M)
-    lib = _lib.load()
-    nbytes = lib.sbg_u8_nn_workspace(Q, M, k)
-    if nbytes < 0:
-        raise RuntimeError(f"{what}: unsupported sizes Q={Q} M={M} k={k}")
-    ws = _lib.workspace(nbytes, store.device, "sbg_u8_nn_workspace")
-    d2 = torch.empty([Q, k], dtype=torch.int64, device=store.device)
-    index = torch.empty([Q, k], dtype=torch.int32, device=store.device)
-    _lib.check(lib.sbg_u8_nn_topk(queries.data_ptr(), store.data_ptr(), Q, M, F, k, _lib.ptr(exclude), d2.data_ptr(), index.data_ptr(), ws.data_ptr(),
-                                  _lib.stream_ptr(store.device)), "sbg_u8_nn_topk")
-    return d2, index
+    return _topk_common.run_device(what, _KIND, queries, store, Q, M, F, k, exclude)

@@ -66,7 +66,7 @@ def exact_case(R, C, F, k, offset):
 
 
 def plan(R, C):
-    """(column tiles, runs per row tile, tiles per run) of a launch: the split rule of csrc/knn_manifold.hip, restated"""
+    """(column tiles, runs per row tile, tiles per run) of a launch: the split rule of csrc/knn_select.h (`plan_runs`), restated"""
     rtiles, ctiles = -(-R // 128), -(-C // 128)
     want = min(max(512 // rtiles, 1), ctiles)
     tiles_per_run = -(-ctiles // want)

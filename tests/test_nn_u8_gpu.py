@@ -16,6 +16,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import style_big_gan_amd  # noqa: E401,F401
 from style_big_gan_amd import _lib
 from style_big_gan_amd.torch_utils.ops import nn_u8
+import knn_manifold_util
 import nn_u8_util as U
 
 pytestmark = pytest.mark.gpu
@@ -88,10 +89,13 @@ def test_largest_row_length(dev):
 
 @pytest.mark.parametrize("Q,M,F,k,plan", [(37, 200000, 48, 5, "split"), (2100, 13000, 48, 8, "split"), (33000, 300, 48, 3, "single")])
 def test_several_tiles_and_runs(dev, Q, M, F, k, plan):
-    """the same rows planted in different runs (j and j + 4100; j and j + 150 where the store is one run of three tiles)"""
+    """one query tile x 391 runs of 4 tiles; 17 query tiles x 26 runs of 4 tiles; 258 query tiles, so one run of 3 tiles.  The same rows
+    are planted in different runs (j and j + 4100; j and j + 150 where the store is one run of three tiles)"""
     far = 4100 if M > 8200 else 150
     queries, store, planted = U.make_case(Q, M, F, seed=Q + M, far=far)
     assert any(b - a == far for a, b in planted)
+    _, plan_runs, plan_tiles_per_run = knn_manifold_util.plan(Q, M)
+    assert plan_runs == {37: 391, 2100: 26, 33000: 1}[Q] and plan_tiles_per_run == (4 if plan == "split" else 3)
     got, log = _logged(lambda: nn_u8.topk(_dev(queries, dev), _dev(store, dev), k))
     want = U.oracle_topk(queries, store, k)
     assert U.same(got, want)
@@ -102,9 +106,11 @@ def test_several_tiles_and_runs(dev, Q, M, F, k, plan):
     dims = log[2][1]
     assert dims[1:5] == (Q, M, F, k)
     runs, tiles = dims[5], (M + 127) // 128
+    assert runs == plan_runs and all(d[5] == plan_runs for _, d in log[2:]), log
     assert (runs > 1) == (plan == "split") and (tiles + runs - 1) // runs >= 3, (runs, tiles)
     if plan == "split":
         tiles_per_run = (tiles + runs - 1) // runs
+        assert tiles_per_run == plan_tiles_per_run
         assert any(a // (128 * tiles_per_run) != b // (128 * tiles_per_run) for a, b in planted), "no planted pair straddles two runs"
 
 
