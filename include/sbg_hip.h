@@ -610,6 +610,35 @@ int sbg_diffaug_fwd(const float* x, const int32_t* table, float* y, float* works
 int sbg_diffaug_adj(const float* g, const int32_t* table, float* dx, float* workspace, int N, int C, int H, int W, sbg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Sliced Wasserstein distance on Laplacian-pyramid patches (Karras et al., "Progressive Growing of GANs", ICLR 2018, section 5: `swd-16k`
+ * of their metrics/sliced_wasserstein.py; the reference has no counterpart).  The definition and every fixed order are stated in
+ * csrc/swd.hip and DESIGN.md section 21.  fp32 dense tensors, 4-byte aligned (float64 outputs and workspaces 8-byte aligned); no atomics:
+ * two calls give the same bits.
+ *   sbg_swd_pyr_down: x [B, C, S, S] -> y [B, C, S/2, S/2]: the separable [1,4,6,4,1]/16 filter, mirrored boundaries (no repeat of the edge
+ *                     sample), even rows and columns kept.  S a power of two in [4, 16384].
+ *   sbg_swd_pyr_lap:  out = fine [B, C, S, S] - up(coarse [B, C, S/2, S/2]), up = zero insertion (samples at even positions) and the
+ *                     separable [1,4,6,4,1]/8 filter with the same boundaries.  `out` may be `fine`.
+ *   sbg_swd_gather:   rows row_offset + b P + p of desc [M, 49 C] = the 7 x 7 x C patch of level [B, C, S, S] around centres[b, p] = (y, x)
+ *                     (int32 [B, P, 2] on the device), in (c, dy, dx) order; a centre outside [3, S - 4] writes a row of NaN.  C = 1..4.
+ *   sbg_swd_moments:  out (float64 [C, 2]) = sum and sum of squares of every channel of desc [M, 49 C], float64 accumulation in an order fixed
+ *                     by M alone; sbg_swd_moments_workspace(M, C) bytes of workspace (-1: unsupported sizes).  Two launches.
+ *   sbg_swd_project:  out[d, m] (fp32 [D, M], direction-major) = the fp32 chain over k = 0 .. 49 C - 1 from 0 of
+ *                     acc = fmaf(fmaf(desc[m, k], s[k / 49], t[k / 49]), dirs[k * dirs_ld + d], acc)  on v_mfma_f32_32x32x2_f32 (that chain bit
+ *                     for bit).  s, t: fp32 [C] on the device; dirs: fp32 [49 C, >= D] with row pitch dirs_ld (a column slice costs nothing).
+ *   sbg_swd_l1:       out[d] (float64 [D]) = sum_m |a[d, m] - b[d, m]| of two fp32 [D, M] arrays, the difference and the sum in float64 in an
+ *                     order fixed by M alone; sbg_swd_l1_workspace(D, M) bytes of workspace (-1: unsupported sizes).  Two launches. */
+int sbg_swd_pyr_down(const float* x, float* y, int B, int C, int S, sbg_stream_t stream);
+int sbg_swd_pyr_lap(const float* fine, const float* coarse, float* out, int B, int C, int S, sbg_stream_t stream);
+int sbg_swd_gather(const float* level, const int32_t* centres, float* desc, int B, int C, int S, int P, int64_t row_offset, int64_t M,
+                   sbg_stream_t stream);
+int64_t sbg_swd_moments_workspace(int64_t M, int C);
+int sbg_swd_moments(const float* desc, double* out, void* workspace, int64_t M, int C, sbg_stream_t stream);
+int sbg_swd_project(const float* desc, const float* s, const float* t, const float* dirs, float* out, int64_t M, int C, int D, int64_t dirs_ld,
+                    sbg_stream_t stream);
+int64_t sbg_swd_l1_workspace(int D, int64_t M);
+int sbg_swd_l1(const float* a, const float* b, double* out, void* workspace, int D, int64_t M, sbg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * In-process launch timing (measurement only; bench.py's roofline figures come from here).
  * While enabled, every kernel launch of this library is bracketed by two hipEvents recorded on the launch stream
  * and logged with its algorithmic flops / bytes.  sbg_prof_fetch() synchronises the logged events, writes up to `max`
@@ -631,8 +660,10 @@ enum sbg_kernel_kind {
     SBG_K_RESIDENT = 24,        /* dims = B, C, H, W, out_f32, 0, dims[6] = 1 dword path (4 pixels per work-item) / 2 byte path */
     SBG_K_DIFFAUG = 25,         /* dims[0] = variant: 0 sum / 1 apply / 2 adjoint sum / 3 adjoint apply (the two launches of C H W > 4096),
                                  * 4 single-pass forward / 5 single-pass adjoint (C H W <= 4096); then N, C, H, W, dims[5] = 1 16-byte / 2 dword accesses */
-    SBG_K_NN_U8 = 26            /* dims[0] = variant: 0 norms (Q or M rows, the other 0) / 1 single / 2 split (the tile kernel, one / several
+    SBG_K_NN_U8 = 26,           /* dims[0] = variant: 0 norms (Q or M rows, the other 0) / 1 single / 2 split (the tile kernel, one / several
                                  * store runs per query tile) / 3 merge; then Q, M, F clipped to INT32_MAX, k, runs */
+    SBG_K_SWD = 27              /* dims[0] = variant: 0 pyr_down (B, C, S) / 1 pyr_lap (B, C, S) / 2 gather (B, C, S, P) / 3 moments (M, C, chunks) /
+                                 * 4 project (M, K, D) / 5 l1 (D, M, chunks) / 6 merge of the float64 partials (values, chunks); M clipped to INT32_MAX */
 };
 /* Kernel-variant codes in the records of the streaming kernels (which kernel served the launch):
  *   bias_act     dims[4] = 1 vec8 / 2 scalar,  dims[5] = bias mode (0 none, 1 channel-minor vector, 2 one per 8-vector, 3 generic)

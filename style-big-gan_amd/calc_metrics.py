@@ -7,12 +7,13 @@ the snapshot (the reference's run-dir rule, :170-176).  Differences:
   the data set options come from that config too (snapshots of this build hold no ``training_set_kwargs``), through the helper the
   trainer itself uses; ``--data`` overrides the path, ``--mirror`` the flips, and the labels follow ``G.c_dim``;
 * detectors are local: ``--detector`` names a TorchScript file or a directory holding the reference's file names; nothing is fetched;
+  it may be left out when no metric asked for needs one (``swd16k``, the sliced Wasserstein distance on Laplacian-pyramid patches);
 * on a GPU the precision / recall metrics run on the fused k-NN kernels (metrics/scores.py, ``precision_recall_fused``), and so does
   ``prdc50k5_full`` (precision / recall / density / coverage, ``prdc_fused``), a metric the reference does not have;
 * ``calc_metrics()`` is a function of a generator for callers that already hold one.
 
     python -m style_big_gan_amd.calc_metrics exp.config_dir=<dir> exp.config=<file.yaml> --snapshot=<network-snapshot-*.pt> \\
-        [--metrics=fid50k_full,pr50k3_full | none] [--data=<folder|zip>] [--mirror=0|1] [--gpus=1] --detector=<TorchScript file | directory> \\
+        [--metrics=fid50k_full,pr50k3_full | none] [--data=<folder|zip>] [--mirror=0|1] [--gpus=1] [--detector=<TorchScript file | directory>] \\
         [--verbose=1] [--device=auto|cuda|cpu]
 """
 import argparse
@@ -43,6 +44,11 @@ def detector_kwargs(detector):
     raise ValueError(f'--detector={detector}: no such TorchScript file or directory (detectors are not downloaded in this build)')
 
 
+def needs_detector(metrics):
+    """whether any of `metrics` computes on detector features (metric_main.needs_detector); unknown names count: they fail on their own"""
+    return any(metric_main.needs_detector(m) for m in metrics)
+
+
 def check_metrics(metrics, G=None, detector=None):
     """unknown names fail with the list of valid ones; the perceptual-path-length metrics keep the checks the trainer makes at setup:
     the LPIPS detector must be present and G needs `mapping` / `synthesis`"""
@@ -69,7 +75,7 @@ def calc_metrics(G, metrics, dataset_kwargs, detector, num_gpus=1, rank=0, devic
     With num_gpus > 1 the caller has initialised torch.distributed.  -> {metric: result dict}"""
     device = torch.device(device) if device is not None else next(iter(G.parameters())).device
     check_metrics(metrics, G, detector)
-    kw = detector_kwargs(detector)
+    kw = detector_kwargs(detector) if detector is not None or needs_detector(metrics) else dict(detector=None, detector_dir=None)
     out = dict()
     for metric in metrics:
         if rank == 0 and verbose:
@@ -139,7 +145,8 @@ def parse_args(argv=None):
     ap.add_argument('--data', help='data set to evaluate against, folder or zip (default: the run\'s data.dataset_path)')
     ap.add_argument('--mirror', type=int, choices=(0, 1), help='whether the data set was augmented with x-flips during training (default: the run\'s data.mirror)')
     ap.add_argument('--gpus', type=int, default=1, help='number of GPUs to use (default: 1)')
-    ap.add_argument('--detector', required=True, help='local TorchScript detector, or a directory holding inception-2015-12-05.pt / vgg16.pt')
+    ap.add_argument('--detector', help='local TorchScript detector, or a directory holding inception-2015-12-05.pt / vgg16.pt; required unless no '
+                    'metric of --metrics needs one (swd16k)')
     ap.add_argument('--verbose', type=int, choices=(0, 1), default=1, help='print optional information (default: 1)')
     ap.add_argument('--device', choices=('auto', 'cuda', 'cpu'), default='auto', help='where to run (default: auto)')
     args, rest = ap.parse_known_args(argv)
@@ -153,7 +160,10 @@ def parse_args(argv=None):
         ap.error(f'--gpus must be at most {MAX_GPUS}')
     if not os.path.isfile(args.snapshot):
         ap.error(f'--snapshot={args.snapshot}: no such file')
-    if not os.path.exists(args.detector):
+    if args.detector is None:
+        if needs_detector(args.metrics):
+            ap.error('the following arguments are required: --detector')
+    elif not os.path.exists(args.detector):
         ap.error(f'--detector={args.detector}: no such TorchScript file or directory (detectors are not downloaded in this build)')
     if args.mirror is not None:
         args.mirror = bool(args.mirror)

@@ -3,7 +3,8 @@
 rank 0's numbers, wrap with timing metadata) and ``report_metric(result_dict, run_dir, snapshot_pkl)`` (:65-76: one JSON line to stdout
 and to ``metric-<name>.jsonl``).  Metric names and their sample counts are the reference's (:81-150), the perceptual-path-length family
 (:101, :133-150) included: its LPIPS network is the local ``vgg16.pt`` detector (or a callable stand-in), see perceptual_path_length.py.
-``prdc50k5_full`` (density / coverage next to precision / recall, scores.prdc_fused) is this build's own."""
+``prdc50k5_full`` (density / coverage next to precision / recall, scores.prdc_fused) and ``swd16k`` (the detector-free sliced Wasserstein
+distance on Laplacian-pyramid patches, scores.compute_swd) are this build's own."""
 import json
 import os
 import time
@@ -28,6 +29,11 @@ def is_valid_metric(metric):
 
 def list_valid_metrics():
     return list(_metric_dict.keys())
+
+
+def needs_detector(metric):
+    """whether `metric` computes on the features of a TorchScript detector file; the sliced Wasserstein metrics need the data set alone"""
+    return not str(metric).startswith('swd')
 
 
 def calc_metric(metric, dataset_name='image_folder', **kwargs):
@@ -95,6 +101,17 @@ def is50k(opts, dataset_name='image_folder'):
     _full_dataset(opts)
     mean, std = scores.compute_is(opts, dataset_name=dataset_name, num_gen=50000, num_splits=10)
     return dict(is50k_mean=mean, is50k_std=std)
+
+
+@register_metric
+def swd16k(opts, dataset_name='image_folder'):
+    """sliced Wasserstein distance on 7 x 7 Laplacian-pyramid patches, 16384 images, one score per level and their mean (Karras et al.,
+    ICLR 2018, `swd-16k`); needs no detector; not in the reference"""
+    _full_dataset(opts)
+    levels = scores.compute_swd(opts, num_images=16384, dataset_name=dataset_name)
+    results = {f'swd16k_{res}': value for res, value in levels.items()}
+    results['swd16k_avg'] = sum(levels.values()) / len(levels)
+    return results
 
 
 # -- legacy metrics (reference :114-130): 50k reals, data-set flips kept

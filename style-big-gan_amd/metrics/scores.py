@@ -1,6 +1,7 @@
 """The scores computed from feature statistics: Frechet distance (FID), kernel distance (KID), Inception score (IS), improved
 precision / recall (PR) and, beyond the reference, density / coverage (PRDC: Naeem et al., "Reliable Fidelity and Diversity Metrics
-for Generative Models", ICML 2020).  Arithmetic of the reference's ``stylegan2ada/metrics/{frechet_inception_distance, kernel_inception_distance,
+for Generative Models", ICML 2020) and the detector-free sliced Wasserstein distance on Laplacian-pyramid patches (SWD: Karras et al.,
+"Progressive Growing of GANs", ICLR 2018, section 5; the last part of this file).  Arithmetic of the reference's ``stylegan2ada/metrics/{frechet_inception_distance, kernel_inception_distance,
 inception_score, precision_recall}.py``; each function cites the lines it follows.  Detector names are the reference's file names; the
 files themselves are never fetched (see metric_utils.get_feature_detector)."""
 import numpy as np
@@ -8,6 +9,7 @@ import scipy.linalg
 import torch
 
 from ..torch_utils.ops import knn_manifold
+from ..torch_utils.ops import swd as swd_ops
 from . import metric_utils
 
 INCEPTION = 'inception-2015-12-05.pt'      # reference: nvlabs-fi-cdn URL / './inception-2015-12-05.pt' (frechet_inception_distance.py:22-23)
@@ -217,3 +219,185 @@ def compute_prdc(opts, max_real, num_gen, nhood_size, row_batch_size, dataset_na
     gen = metric_utils.compute_feature_stats_for_generator(opts=opts, dataset_name=dataset_name, detector_url=VGG16, detector_kwargs=kw, rel_lo=0, rel_hi=1,
                                                            capture_all=True, max_items=num_gen).get_all_torch().to(half).to(opts.device)
     return prdc_fused(real, gen, nhood_size, row_batch_size, opts.num_gpus, opts.rank)       # the kernels on the device, the op layer's torch path on the CPU
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# Sliced Wasserstein distance on Laplacian-pyramid patches.  Constants of the published `swd-16k`.
+
+SWD_NHOOD_SIZE = 7
+SWD_NHOODS_PER_IMAGE = 128
+SWD_DIR_REPEATS = 4
+SWD_DIRS_PER_REPEAT = 128
+SWD_MIN_RES = 16
+SWD_DIR_CHUNK = 32          # directions projected, sorted and compared at a time: bounds the sort's index tensor at 8 bytes * 32 * M
+
+
+def swd_resolutions(resolution):
+    """level sides R, R/2, ..., 16; a resolution that is not a power of two >= 16 is refused"""
+    resolution = int(resolution)
+    if resolution < SWD_MIN_RES or resolution & (resolution - 1):
+        raise ValueError(f'swd: resolution {resolution} is not a power of two >= {SWD_MIN_RES}')
+    return [resolution >> i for i in range(resolution.bit_length() - SWD_MIN_RES.bit_length() + 1)]
+
+
+def swd_tables(seed, num_images, resolution, channels, nhoods_per_image=SWD_NHOODS_PER_IMAGE, num_dirs=SWD_DIR_REPEATS * SWD_DIRS_PER_REPEAT,
+               z_dim=None, num_labels=None):
+    """every random number of one evaluation, drawn on the host from ONE numpy.random.RandomState(seed) in this order:
+      1. directions   randn(49 C, num_dirs) float64, each column divided by its l2 norm, cast to float32 (columns 128 r .. of repeat r)
+      2. centres      per level, largest first: randint(3, S - 3, [N, nhoods_per_image, 2]) = (y, x); image i of BOTH sets uses row i
+      3. latents      randn(N, z_dim)                  (when z_dim is given)
+      4. label items  randint(num_labels, size=N)      (when num_labels is given): generated image i takes the label of that data-set item
+    so nothing depends on the image batch size or on the number of ranks."""
+    rs = np.random.RandomState(seed)
+    dirs = rs.randn(channels * swd_ops.PP, num_dirs)
+    dirs /= np.sqrt(np.sum(np.square(dirs), axis=0, keepdims=True))
+    tables = dict(dirs=dirs.astype(np.float32),
+                  centres=[rs.randint(3, s - 3, size=[num_images, nhoods_per_image, 2]).astype(np.int32) for s in swd_resolutions(resolution)])
+    if z_dim is not None:
+        tables['z'] = rs.randn(num_images, z_dim).astype(np.float32)
+    if num_labels is not None:
+        tables['label_items'] = rs.randint(num_labels, size=num_images)
+    return tables
+
+
+class SwdDescriptors:
+    """the descriptor matrices [128 N, 49 C] of one image set, one per pyramid level, filled batch by batch: only they persist"""
+
+    def __init__(self, num_images, resolution, channels, centres, device):
+        self.resolutions = swd_resolutions(resolution)
+        assert len(centres) == len(self.resolutions) and all(c.shape[0] == num_images and c.shape[2] == 2 for c in centres)
+        self.num_images, self.channels, self.device = num_images, channels, torch.device(device)
+        self.centres = [torch.as_tensor(c, dtype=torch.int32).to(self.device) for c in centres]
+        self.desc = [torch.zeros([num_images * c.shape[1], channels * swd_ops.PP], dtype=torch.float32, device=self.device) for c in self.centres]
+
+    def add(self, start, images):
+        """images [B, C, R, R], byte values (uint8 or float), are images start .. start + B - 1 of the set"""
+        b = images.shape[0]
+        assert 0 <= start and start + b <= self.num_images and tuple(images.shape[1:]) == (self.channels, self.resolutions[0], self.resolutions[0])
+        x = images.to(self.device).to(torch.float32).contiguous()
+        for level, centres, desc in zip(swd_ops.laplacian_pyramid(x, len(self.resolutions)), self.centres, self.desc):
+            swd_ops.gather_descriptors(level, centres[start:start + b].contiguous(), desc, row_offset=start * centres.shape[1])
+
+    def exchange(self, num_gpus):
+        """every rank filled the rows of its own images into zeros: one sum per level completes all of them (x + 0 is exact)"""
+        if num_gpus > 1:
+            for desc in self.desc:
+                torch.distributed.all_reduce(desc)
+        return self.desc
+
+
+def swd_normalisation(desc, channels, what='descriptors'):
+    """(s, t) fp32 [C] on desc's device with x_hat = fmaf(x, s_c, t_c): s_c = float32(1 / std), t_c = float32(-mean / std), mean and
+    population std of channel c over all M * 49 values from the float64 sum and sum of squares of `channel_moments`"""
+    sums = swd_ops.channel_moments(desc, channels).cpu().numpy()
+    n = float(desc.shape[0] * swd_ops.PP)
+    s, t = np.zeros([channels], dtype=np.float32), np.zeros([channels], dtype=np.float32)
+    for c in range(channels):
+        mean = sums[c, 0] / n
+        with np.errstate(all='ignore'):
+            std = np.sqrt(sums[c, 1] / n - mean * mean)
+        if not np.isfinite(std) or not std > 0 or not np.isfinite(mean):
+            raise ValueError(f'swd: {what}, channel {c}: standard deviation {std} (a constant or non-finite channel has no normalised descriptors)')
+        s[c], t[c] = np.float32(1.0 / std), np.float32(-mean / std)
+    return torch.from_numpy(s).to(desc.device), torch.from_numpy(t).to(desc.device)
+
+
+def swd_direction_distances(real_desc, fake_desc, dirs, lo=0, hi=None, what='level', dir_chunk=SWD_DIR_CHUNK):
+    """D_d = sum_m |sort(p_real[:, d])_m - sort(p_fake[:, d])_m| for the directions lo <= d < hi of dirs fp32 [K, D] -> float64 [hi - lo]
+    on the host.  Projection, sort (torch.sort along the contiguous axis of the direction-major projections) and the fixed-order float64
+    sum (`sorted_l1`) run in chunks of `dir_chunk` directions; a direction's D_d does not depend on the chunking."""
+    assert real_desc.shape == fake_desc.shape and real_desc.device == fake_desc.device
+    channels = real_desc.shape[1] // swd_ops.PP
+    dirs = torch.as_tensor(dirs, dtype=torch.float32).to(real_desc.device)
+    hi = dirs.shape[1] if hi is None else hi
+    norm = [swd_normalisation(desc, channels, f'{name} set, {what}') for name, desc in (('real', real_desc), ('generated', fake_desc))]
+    out = []
+    for a in range(lo, hi, dir_chunk):
+        b = min(a + dir_chunk, hi)
+        proj = [torch.sort(swd_ops.project(desc, s, t, dirs[:, a:b]), dim=1).values for desc, (s, t) in zip((real_desc, fake_desc), norm)]
+        out.append(swd_ops.sorted_l1(proj[0], proj[1]).cpu())
+    return torch.cat(out) if out else torch.zeros([0], dtype=torch.float64)
+
+
+def swd_score(dists, rows, dir_repeats, dirs_per_repeat):
+    """1e3 * mean_r(mean_{d in r}(D_d / M)) in float64, the directions of a repeat added left to right, then the repeats left to right"""
+    dists = [float(v) for v in dists]
+    assert len(dists) == dir_repeats * dirs_per_repeat
+    total = 0.0
+    for r in range(dir_repeats):
+        acc = 0.0
+        for d in range(r * dirs_per_repeat, (r + 1) * dirs_per_repeat):
+            acc += dists[d] / rows
+        total += acc / dirs_per_repeat
+    return 1e3 * (total / dir_repeats)
+
+
+def sliced_wasserstein(real_desc, fake_desc, dirs, dir_repeats=SWD_DIR_REPEATS, dirs_per_repeat=SWD_DIRS_PER_REPEAT, what='level', num_gpus=1, rank=0,
+                       dir_chunk=SWD_DIR_CHUNK):
+    """the score of one level from its two descriptor matrices [M, 49 C] (every rank holds both).  The directions are dealt to the ranks in
+    contiguous shares (`_rank_share`), the D_d exchanged with one all_gather and added in direction order; every rank returns the number."""
+    assert 0 <= rank < num_gpus
+    num_dirs = dir_repeats * dirs_per_repeat
+    lo, hi = _rank_share(num_dirs, num_gpus, rank)
+    dists = swd_direction_distances(real_desc, fake_desc, dirs, lo, hi, what=what, dir_chunk=dir_chunk)
+    if num_gpus > 1:        # shares differ by at most one direction: pad to the largest, gather once, cut the pads
+        longest = -(-num_dirs // num_gpus)
+        mine = torch.nn.functional.pad(dists, [0, longest - dists.shape[0]]).to(real_desc.device)
+        parts = [torch.empty_like(mine) for _ in range(num_gpus)]
+        torch.distributed.all_gather(parts, mine)
+        dists = torch.cat([part[:b - a].cpu() for part, (a, b) in zip(parts, (_rank_share(num_dirs, num_gpus, r) for r in range(num_gpus)))])
+    return swd_score(dists, real_desc.shape[0], dir_repeats, dirs_per_repeat)
+
+
+def compute_swd(opts, num_images, dataset_name='image_folder', seed=0, batch_size=64, batch_gen=None, data_loader_kwargs=None,
+                nhoods_per_image=SWD_NHOODS_PER_IMAGE, dir_repeats=SWD_DIR_REPEATS, dirs_per_repeat=SWD_DIRS_PER_REPEAT):
+    """-> {level side: score}.  N = min(num_images, len(dataset)) real images (items 0 .. N - 1) against N generated ones, quantised to
+    uint8 as `compute_feature_stats_for_generator` does, latents and labels from `swd_tables`.  Images stream through in batches; rank r
+    renders and reads the images of its contiguous share and the descriptor rows are exchanged once per set."""
+    import copy
+    from ..train_parts.datasets import datasets
+    dataset = datasets[dataset_name](**opts.dataset_kwargs)
+    resolution, channels = int(dataset.resolution), int(dataset.num_channels)
+    resolutions = swd_resolutions(resolution)
+    if channels not in (1, 3):
+        raise ValueError(f'swd: {channels} image channels; 1 or 3 are supported')
+    n = min(int(num_images), len(dataset))
+    if n < 1:
+        raise ValueError('swd: the data set is empty')
+    G = copy.deepcopy(opts.G).eval().requires_grad_(False).to(opts.device)
+    c_dim = G.c_dim or 0
+    tables = swd_tables(seed, n, resolution, channels, nhoods_per_image, dir_repeats * dirs_per_repeat, z_dim=G.z_dim, num_labels=len(dataset))
+    lo, hi = _rank_share(n, opts.num_gpus, opts.rank)
+    if batch_gen is None:
+        batch_gen = min(batch_size, 4)
+    if data_loader_kwargs is None:
+        data_loader_kwargs = dict(pin_memory=(torch.device(opts.device).type == 'cuda'), num_workers=3, prefetch_factor=2)
+
+    real = SwdDescriptors(n, resolution, channels, tables['centres'], opts.device)
+    progress = opts.progress.sub(tag='dataset patches', num_items=n, rel_lo=0, rel_hi=0.3)
+    start = lo
+    if hi > lo:
+        for images, _labels in torch.utils.data.DataLoader(dataset=dataset, sampler=range(lo, hi), batch_size=batch_size, **data_loader_kwargs):
+            real.add(start, images)
+            start += images.shape[0]
+            progress.update(start - lo)
+    fake = SwdDescriptors(n, resolution, channels, tables['centres'], opts.device)
+    progress = opts.progress.sub(tag='generator patches', num_items=n, rel_lo=0.3, rel_hi=0.6)
+    with torch.no_grad():
+        for start in range(lo, hi, batch_gen):
+            stop = min(start + batch_gen, hi)
+            z = torch.from_numpy(tables['z'][start:stop]).to(opts.device)
+            if c_dim:
+                c = torch.from_numpy(np.stack([dataset.get_label(int(i)) for i in tables['label_items'][start:stop]])).to(opts.device)
+            else:
+                c = torch.zeros([stop - start, 0], device=opts.device)
+            img = G(z, c, **opts.G_kwargs)
+            fake.add(start, (img * 127.5 + 128).clamp(0, 255).to(torch.uint8))
+            progress.update(stop - lo)
+    real_desc, fake_desc = real.exchange(opts.num_gpus), fake.exchange(opts.num_gpus)
+    results = dict()
+    for i, res in enumerate(resolutions):
+        results[res] = sliced_wasserstein(real_desc[i], fake_desc[i], tables['dirs'], dir_repeats, dirs_per_repeat, what=f'level {res}x{res}',
+                                          num_gpus=opts.num_gpus, rank=opts.rank)
+        real_desc[i] = fake_desc[i] = None      # a level's matrices are dropped once it is scored
+    return results

@@ -610,12 +610,15 @@ class BaseTrainer:
             # the reference fetches its detectors from a URL at the first snapshot; this build never downloads.  A run on a real data set that
             # is configured with metrics (the reference's DEFAULT is [fid50k_full, is50k]) and has nothing to compute them with would train
             # for hours and report nothing: refuse at setup.  Synthetic data has no data set to score against: the metrics are dropped, loudly.
+            # Metrics that compute on the data set alone (metric_main.needs_detector: swd16k) run without a detector.
             if self.real_data:
-                raise ValueError(f"log.metrics={self.metrics} needs log.metric_detector=<local TorchScript file or directory holding "
-                                 "inception-2015-12-05.pt / vgg16.pt> (detectors are not downloaded in this build); log.metrics=[] turns them off")
-            import warnings
-            warnings.warn(f"log.metrics={self.metrics} ignored: data.dataset=synthetic has no data set to score against")
-            self.metrics = []
+                if any(metric_main.needs_detector(m) for m in self.metrics):
+                    raise ValueError(f"log.metrics={self.metrics} needs log.metric_detector=<local TorchScript file or directory holding "
+                                     "inception-2015-12-05.pt / vgg16.pt> (detectors are not downloaded in this build); log.metrics=[] turns them off")
+            else:
+                import warnings
+                warnings.warn(f"log.metrics={self.metrics} ignored: data.dataset=synthetic has no data set to score against")
+                self.metrics = []
         self._check_ppl_metrics(gen.generator)
         return self
 
@@ -830,8 +833,8 @@ class BaseTrainer:
         return path
 
     def evaluate_metrics(self, snapshot_path=None, detector=None, metrics=None):
-        """every configured metric on G_ema (G when the average is off) against the training set (reference :659-674).  The feature
-        detector must be local (`log.metric_detector=<TorchScript file | directory>` or the `detector` argument: a path or a callable);
+        """every configured metric on G_ema (G when the average is off) against the training set (reference :659-674).  Unless none of the
+        metrics needs one (metric_main.needs_detector), the feature detector must be local (`log.metric_detector=<TorchScript file | directory>` or the `detector` argument: a path or a callable);
         the reference's URL fetch does not exist here, so without one this raises instead of silently skipping."""
         from ..metrics import metric_main
         detector = detector if detector is not None else self.metric_detector
@@ -845,7 +848,7 @@ class BaseTrainer:
             kw["detector"] = detector
         elif isinstance(detector, str) and os.path.isdir(detector):
             kw["detector_dir"] = detector
-        else:
+        elif any(metric_main.needs_detector(m) for m in names):
             raise ValueError("no local feature detector: set log.metric_detector=<TorchScript file or directory> (detectors are not downloaded)")
         G = self.engine.G_ema if self.engine.G_ema is not None else self.engine.G
         self.metrics_time = 0.0
