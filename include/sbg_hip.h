@@ -639,6 +639,22 @@ int64_t sbg_swd_l1_workspace(int D, int64_t M);
 int sbg_swd_l1(const float* a, const float* b, double* out, void* workspace, int D, int64_t M, sbg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Average 2-D power spectrum of an image set (avg_spectra.py of Karras et al., "Alias-Free Generative Adversarial Networks", NeurIPS 2021;
+ * the reference has no counterpart).  The definition -- a windowed, zero-padded fp32 radix-2 transform whose every rounding is stated, and a
+ * float64 power accumulator with one sequential chain per entry -- is in csrc/spectrum.hip and DESIGN.md section 22; torch_utils/ops/spectrum.py
+ * evaluates it for CPU tensors to the same bits.  R: image side, a power of two in [16, 1024]; S = R, 2 R or 4 R: spectrum side; BC image-channels.
+ *   window:  fp32 [R].   stages: fp32 [S - 1, 2], the twiddles stage-major: entry h - 1 + j = twiddle[j S / (2 h)] = (cos, -sin)(2 pi j / (2 h)) for
+ *            the half-spans h = 1, 2, .., S/2 and j < h (the op layer gathers it from twiddle[S/2]).   s, t: the normalisation v = fmaf(x, s, t).
+ *   sbg_spectrum_workspace: bytes of the intermediate [BC, S/2 + 1, R] float2 (its R axis in bit-reversed row order), -1 for unsupported sizes.
+ *   sbg_spectrum_rows: images (uint8 when is_u8, else fp32) [BC, R, R] -> the windowed row transforms, kx = 0 .. S/2, into the workspace.
+ *   sbg_spectrum_cols: acc[kx, ky] (float64 [S/2 + 1, S], read and written in place) += the power of the windowed column transforms of the
+ *                      BC image-channels, in ascending order; one workgroup per kx, no atomics: two runs give the same bits. */
+int64_t sbg_spectrum_workspace(int64_t BC, int R, int S);
+int sbg_spectrum_rows(const void* images, int is_u8, const float* window, const float* stages, float s, float t, void* workspace, int64_t BC, int R, int S,
+                      sbg_stream_t stream);
+int sbg_spectrum_cols(const void* workspace, const float* window, const float* stages, double* acc, int64_t BC, int R, int S, sbg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * In-process launch timing (measurement only; bench.py's roofline figures come from here).
  * While enabled, every kernel launch of this library is bracketed by two hipEvents recorded on the launch stream
  * and logged with its algorithmic flops / bytes.  sbg_prof_fetch() synchronises the logged events, writes up to `max`
@@ -662,8 +678,9 @@ enum sbg_kernel_kind {
                                  * 4 single-pass forward / 5 single-pass adjoint (C H W <= 4096); then N, C, H, W, dims[5] = 1 16-byte / 2 dword accesses */
     SBG_K_NN_U8 = 26,           /* dims[0] = variant: 0 norms (Q or M rows, the other 0) / 1 single / 2 split (the tile kernel, one / several
                                  * store runs per query tile) / 3 merge; then Q, M, F clipped to INT32_MAX, k, runs */
-    SBG_K_SWD = 27              /* dims[0] = variant: 0 pyr_down (B, C, S) / 1 pyr_lap (B, C, S) / 2 gather (B, C, S, P) / 3 moments (M, C, chunks) /
+    SBG_K_SWD = 27,             /* dims[0] = variant: 0 pyr_down (B, C, S) / 1 pyr_lap (B, C, S) / 2 gather (B, C, S, P) / 3 moments (M, C, chunks) /
                                  * 4 project (M, K, D) / 5 l1 (D, M, chunks) / 6 merge of the float64 partials (values, chunks); M clipped to INT32_MAX */
+    SBG_K_SPECTRUM = 28         /* dims[0] = variant: 0 rows / 1 cols; then BC (image-channels of the call), R, S */
 };
 /* Kernel-variant codes in the records of the streaming kernels (which kernel served the launch):
  *   bias_act     dims[4] = 1 vec8 / 2 scalar,  dims[5] = bias mode (0 none, 1 channel-minor vector, 2 one per 8-vector, 3 generic)

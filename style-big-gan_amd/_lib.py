@@ -105,8 +105,9 @@ class ProfRecord(ctypes.Structure):
 
 KERNEL_KINDS = {1: "bias_act", 2: "upfirdn2d", 3: "conv_igemm", 4: "conv_wgrad", 5: "wgrad_reduce", 6: "scale_nc", 7: "dot_hw", 9: "sn_power", 10: "attention",
                 11: "grid_sample", 12: "filter1d", 13: "color", 14: "weight_prep", 15: "torgb", 16: "fromrgb", 17: "grouped_gemm", 18: "ppl",
-                19: "projector", 20: "image_export", 21: "resample", 22: "pr", 23: "grad_finish", 24: "resident", 25: "diffaug", 26: "nn_u8", 27: "swd"}
+                19: "projector", 20: "image_export", 21: "resample", 22: "pr", 23: "grad_finish", 24: "resident", 25: "diffaug", 26: "nn_u8", 27: "swd", 28: "spectrum"}
 SWD_VARIANTS = {0: "pyr_down", 1: "pyr_lap", 2: "gather", 3: "moments", 4: "project", 5: "l1", 6: "merge"}      # dims[0] of an "swd" launch record
+SPECTRUM_VARIANTS = {0: "rows", 1: "cols"}                 # dims[0] of a "spectrum" launch record (then BC, R, S)
 NN_VARIANTS = {0: "norms", 1: "single", 2: "split", 3: "merge"}    # dims[0] of an "nn_u8" launch record (then Q, M, F clipped to int, k, runs)
 RESIDENT_PATHS = {1: "dword", 2: "byte"}                    # dims[6] of a "resident" launch record
 PPL_VARIANTS = {0: "slerp", 1: "lerp", 2: "prep", 3: "dist"}        # dims[0] of a "ppl" launch record
@@ -223,6 +224,10 @@ SYMBOLS = [
     ("sbg_swd_project", _c.c_int, [_c.c_void_p] * 5 + [_c.c_int64, _c.c_int, _c.c_int, _c.c_int64, _c.c_void_p]),
     ("sbg_swd_l1_workspace", _c.c_int64, [_c.c_int, _c.c_int64]),
     ("sbg_swd_l1", _c.c_int, [_c.c_void_p] * 4 + [_c.c_int, _c.c_int64, _c.c_void_p]),
+    ("sbg_spectrum_workspace", _c.c_int64, [_c.c_int64, _c.c_int, _c.c_int]),
+    ("sbg_spectrum_rows", _c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_float, _c.c_float, _c.c_void_p, _c.c_int64, _c.c_int, _c.c_int,
+                                     _c.c_void_p]),
+    ("sbg_spectrum_cols", _c.c_int, [_c.c_void_p] * 4 + [_c.c_int64, _c.c_int, _c.c_int, _c.c_void_p]),
     ("sbg_prof_enable", _c.c_int, [_c.c_int]),
     ("sbg_prof_fetch", _c.c_int, [_c.POINTER(ProfRecord), _c.c_int]),
 ]
