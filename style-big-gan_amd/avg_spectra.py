@@ -25,16 +25,15 @@ The numbers are comparable between runs of one resolution and one ``--interp`` o
         [--noise-mode=const|random|none] [--device=auto|cuda|cpu] [--batch=64] [--db-range=lo,hi]
 """
 import argparse
+import contextlib
 import json
 import os
 
 import numpy as np
 import torch
 
-from .calc_metrics import resolve_device
-from .generate import NOISE_MODES
-from .nearest_neighbors import generated_queries
-from .snapshot_io import build_generator, config_overrides, snapshot_generator_state
+from .tool_support import (SNAPSHOT_HELP, add_device_option, add_sampling_options, add_snapshot_option, class_label, config_overrides, device_of,
+                           generated_images, load_generator, open_dataset, require_file, save_png, tool_device)
 from .torch_utils.ops import resident_set, spectrum
 
 NPZ_KEYS = ('spectrum', 'mean', 'std', 'image_size', 'interp', 'channels', 'num_images')
@@ -133,9 +132,7 @@ def average_spectra(G=None, dataset=None, against=None, num=DEFAULT_NUM, interp=
         raise ValueError('one of a data set and --against is required')
     if against is not None and G is None:
         raise ValueError('--against replaces the data set pass: it needs --snapshot, there is nothing else to compute')
-    if device is None:
-        device = next(iter(G.buffers())).device if G is not None else torch.device('cpu')
-    device = torch.device(device)
+    device = device_of(G, 'cpu' if device is None and G is None else device)
     if outdir is not None:
         os.makedirs(outdir, exist_ok=True)
 
@@ -173,17 +170,11 @@ def average_spectra(G=None, dataset=None, against=None, num=DEFAULT_NUM, interp=
     if G is None:
         return result
 
-    label = torch.zeros([1, G.c_dim], device=device)
-    if G.c_dim != 0:
-        if class_idx is None:
-            raise ValueError('Must specify class label with --class when using a conditional network')
-        label[:, class_idx] = 1
-    elif class_idx is not None:
-        print('warn: --class=lbl ignored when running on an unconditional network')
+    label = class_label(G, class_idx, device)
 
     def gen_batches():
         for lo in range(0, N, batch):
-            yield generated_queries(G, list(range(lo, min(lo + batch, N))), label, truncation_psi, noise_mode, device)
+            yield generated_images(G, list(range(lo, min(lo + batch, N))), label, truncation_psi, noise_mode, device)
 
     gen, _ = mean_spectrum(gen_batches(), R, interp, mean, std, device)
     real_full, gen_full = spectrum.full_from_half(real), spectrum.full_from_half(gen)
@@ -196,11 +187,10 @@ def average_spectra(G=None, dataset=None, against=None, num=DEFAULT_NUM, interp=
                  options=dict(num=num, interp=interp, trunc=truncation_psi, class_idx=class_idx, noise_mode=noise_mode, batch=batch, db_range=[lo, hi]))
     result.update(gen=gen, num_gen=N, stats=stats, canvas=canvas)
     if outdir is not None:
-        from .train_parts.trainers import write_grid_png
         save_npz(os.path.join(outdir, 'spectrum_gen.npz'), gen, mean, std, R, interp, C, N)
         with open(os.path.join(outdir, 'spectrum.json'), 'w') as f:
             json.dump(stats, f, indent=2)
-        write_grid_png(canvas, os.path.join(outdir, 'spectrum.png'))
+        save_png(canvas, os.path.join(outdir, 'spectrum.png'))
     return result
 
 
@@ -220,15 +210,13 @@ def parse_args(argv=None):
     """-> (config overrides as `key=value` strings, the tool's options)"""
     ap = argparse.ArgumentParser(prog='python -m style_big_gan_amd.avg_spectra', description=__doc__.split('\n')[0])
     ap.add_argument('--outdir', required=True, help='where to save spectrum_real.npz / spectrum_gen.npz / spectrum.json / spectrum.png')
-    ap.add_argument('--snapshot', help='network-snapshot-*.pt of this build (G_ema, or G when there is no EMA); without it only the data set is measured')
+    add_snapshot_option(ap, required=False, help=SNAPSHOT_HELP + '; without it only the data set is measured')
     ap.add_argument('--data', help='data set to measure, folder or zip (default: the run\'s data.dataset_path)')
     ap.add_argument('--against', help='a saved spectrum_*.npz that stands in for the data set (mean, std and the "real" spectrum)')
     ap.add_argument('--num', type=int, default=DEFAULT_NUM, help=f'images per set: min(N, the data set\'s size) (default: {DEFAULT_NUM})')
     ap.add_argument('--interp', type=int, choices=spectrum.PADS, default=1, help='zero-padding factor of the transform (default: 1)')
-    ap.add_argument('--trunc', dest='truncation_psi', type=float, default=1, help='truncation psi (default: 1)')
-    ap.add_argument('--class', dest='class_idx', type=int, help='class label (unconditional if not specified)')
-    ap.add_argument('--noise-mode', choices=NOISE_MODES, default='const', help='noise mode (default: const)')
-    ap.add_argument('--device', choices=('auto', 'cuda', 'cpu'), default='auto', help='where to run (default: auto)')
+    add_sampling_options(ap)
+    add_device_option(ap)
     ap.add_argument('--batch', type=int, default=64, help='images measured at a time (default: 64)')
     ap.add_argument('--db-range', type=db_pair, help='lo,hi of the grey scale of spectrum.png in dB (default: the 80 dB below the largest value)')
     args, rest = ap.parse_known_args(argv)
@@ -236,10 +224,8 @@ def parse_args(argv=None):
         ap.error('--num must be at least 1')
     if args.batch < 1:
         ap.error('--batch must be at least 1')
-    if args.snapshot is not None and not os.path.isfile(args.snapshot):
-        ap.error(f'--snapshot={args.snapshot}: no such file')
-    if args.against is not None and not os.path.isfile(args.against):
-        ap.error(f'--against={args.against}: no such file')
+    require_file(ap, '--snapshot', args.snapshot)
+    require_file(ap, '--against', args.against)
     if args.against is not None and args.snapshot is None:
         ap.error('--against replaces the data set pass: it needs --snapshot')
     if args.against is not None and args.data is not None:
@@ -250,27 +236,15 @@ def parse_args(argv=None):
 def run_avg_spectra(argv=None):
     overrides, args = parse_args(argv)
     from . import arguments
-    from .train_parts.datasets import datasets
     from .train_parts.trainers import training_set_kwargs_from_config
     config = arguments.load_config(overrides)
-    dev_type = resolve_device(args.device)
-    device = torch.device('cuda', torch.cuda.current_device()) if dev_type == 'cuda' else torch.device('cpu')
-    G = None
-    if args.snapshot is not None:
-        print(f'Loading networks from "{args.snapshot}"...')
-        G = build_generator(config, snapshot_generator_state(args.snapshot), device)
-    dataset = None
-    if args.against is None:
-        kw = training_set_kwargs_from_config(config, seed=config.gen.seed, path=args.data, mirror=False, use_labels=False)
-        print('Dataset options:', kw)
-        dataset = datasets[config.data.dataset](**kw)
-    try:
+    device = tool_device(args.device)
+    G = load_generator(config, args.snapshot, device) if args.snapshot is not None else None
+    kw = training_set_kwargs_from_config(config, seed=config.gen.seed, path=args.data, mirror=False, use_labels=False) if args.against is None else None
+    with open_dataset(config, kw) if kw is not None else contextlib.nullcontext() as dataset:         # --against: no data set
         result = average_spectra(G, dataset, against=args.against, num=args.num, interp=args.interp, truncation_psi=args.truncation_psi,
                                  noise_mode=args.noise_mode, class_idx=args.class_idx, batch=args.batch, outdir=args.outdir, device=device,
                                  db_range=args.db_range)
-    finally:
-        if dataset is not None:
-            dataset.close()
     if 'stats' in result:
         print(json.dumps({k: result['stats'][k] for k in ('lsd_db', 'hf_excess_db', 'num_real', 'num_gen', 'image_size', 'interp')}))
     return result

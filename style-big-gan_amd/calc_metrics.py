@@ -23,7 +23,8 @@ import tempfile
 import torch
 
 from .metrics import metric_main, metric_utils, perceptual_path_length
-from .snapshot_io import build_generator, config_overrides, snapshot_generator_state
+from .tool_support import (add_device_option, add_snapshot_option, config_overrides, dataset_kwargs_for, detector_kwargs, load_generator, require_file,
+                           resolve_device)
 
 MAX_GPUS = 16
 
@@ -33,15 +34,6 @@ def comma_list(s):
     if s is None or s.lower() == 'none' or s == '':
         return []
     return s.split(',')
-
-
-def detector_kwargs(detector):
-    """a callable or a TorchScript file -> MetricOptions(detector=...), a directory -> MetricOptions(detector_dir=...)"""
-    if callable(detector) or isinstance(detector, dict) or (isinstance(detector, str) and os.path.isfile(detector)):
-        return dict(detector=detector, detector_dir=None)
-    if isinstance(detector, str) and os.path.isdir(detector):
-        return dict(detector=None, detector_dir=detector)
-    raise ValueError(f'--detector={detector}: no such TorchScript file or directory (detectors are not downloaded in this build)')
 
 
 def needs_detector(metrics):
@@ -91,18 +83,6 @@ def calc_metrics(G, metrics, dataset_kwargs, detector, num_gpus=1, rank=0, devic
     return out
 
 
-def resolve_device(name):
-    if name == 'auto':
-        name = 'cuda' if torch.cuda.is_available() else 'cpu'
-    return name
-
-
-def dataset_kwargs_for(config, G, data=None, mirror=None):
-    """the data set kwargs of the run, with the tool's overrides: --data the path, --mirror the flips; the labels follow the network"""
-    from .train_parts.trainers import training_set_kwargs_from_config
-    return training_set_kwargs_from_config(config, seed=config.gen.seed, path=data, mirror=mirror, use_labels=G.c_dim != 0)
-
-
 def _worker(rank, overrides, opts, temp_dir):
     """one process per GPU (reference subprocess_fn :27-81): rendezvous over a file store, build G, run the metrics"""
     from . import arguments
@@ -118,7 +98,7 @@ def _worker(rank, overrides, opts, temp_dir):
         config = arguments.load_config(overrides)
         if rank == 0 and opts['verbose']:
             print(f'Loading network from "{opts["snapshot"]}"...')
-        G = build_generator(config, snapshot_generator_state(opts['snapshot']), device)
+        G = load_generator(config, opts['snapshot'], device, announce=False)
         kw = dataset_kwargs_for(config, G, data=opts['data'], mirror=opts['mirror'])
         if rank == 0 and opts['verbose']:
             print('Dataset options:', kw)
@@ -140,7 +120,7 @@ def _worker(rank, overrides, opts, temp_dir):
 def parse_args(argv=None):
     """-> (config overrides as `key=value` strings, the tool's options)"""
     ap = argparse.ArgumentParser(prog='python -m style_big_gan_amd.calc_metrics', description=__doc__.split('\n')[0])
-    ap.add_argument('--snapshot', required=True, help='network-snapshot-*.pt of this build (G_ema, or G when there is no EMA)')
+    add_snapshot_option(ap)
     ap.add_argument('--metrics', type=comma_list, default=['fid50k_full'], help='comma-separated list or "none" (default: fid50k_full)')
     ap.add_argument('--data', help='data set to evaluate against, folder or zip (default: the run\'s data.dataset_path)')
     ap.add_argument('--mirror', type=int, choices=(0, 1), help='whether the data set was augmented with x-flips during training (default: the run\'s data.mirror)')
@@ -148,7 +128,7 @@ def parse_args(argv=None):
     ap.add_argument('--detector', help='local TorchScript detector, or a directory holding inception-2015-12-05.pt / vgg16.pt; required unless no '
                     'metric of --metrics needs one (swd16k)')
     ap.add_argument('--verbose', type=int, choices=(0, 1), default=1, help='print optional information (default: 1)')
-    ap.add_argument('--device', choices=('auto', 'cuda', 'cpu'), default='auto', help='where to run (default: auto)')
+    add_device_option(ap)
     args, rest = ap.parse_known_args(argv)
     try:
         check_metrics(args.metrics)
@@ -158,15 +138,13 @@ def parse_args(argv=None):
         ap.error('--gpus must be at least 1')
     if args.gpus > MAX_GPUS:
         ap.error(f'--gpus must be at most {MAX_GPUS}')
-    if not os.path.isfile(args.snapshot):
-        ap.error(f'--snapshot={args.snapshot}: no such file')
+    require_file(ap, '--snapshot', args.snapshot)
     if args.detector is None:
         if needs_detector(args.metrics):
             ap.error('the following arguments are required: --detector')
     elif not os.path.exists(args.detector):
         ap.error(f'--detector={args.detector}: no such TorchScript file or directory (detectors are not downloaded in this build)')
-    if args.mirror is not None:
-        args.mirror = bool(args.mirror)
+    args.mirror = None if args.mirror is None else bool(args.mirror)
     return config_overrides(ap, rest), args
 
 

@@ -1,7 +1,7 @@
 """Generate images from a trained generator.
 
 Counterpart of the reference's ``stylegan2ada/generate.py`` (``generate_images`` :46-121): same options, same file names
-(``seed%04d.png`` / ``proj%02d.png``), same latents (``np.random.RandomState(seed).randn(1, z_dim)``), same failures and warnings.
+(``seed%04d.png`` / ``proj%02d.png``), same latents (one ``RandomState`` per seed, ``tool_support.seed_latents``), same failures and warnings.
 Differences:
 * the float -> uint8 step (``(img.permute(0, 2, 3, 1) * 127.5 + 128).clamp(0, 255).to(torch.uint8)``, :98,120) is one HIP kernel
   (torch_utils/ops/image_export.py, the ``clamp`` rule) instead of five tensor ops; CPU tensors take the reference's expression;
@@ -14,40 +14,18 @@ Differences:
 """
 import argparse
 import os
-import re
 
 import numpy as np
 import torch
 
-from .snapshot_io import build_generator, config_overrides, snapshot_generator_state
-from .torch_utils.ops import image_export
-
-NOISE_MODES = ('const', 'random', 'none')
-
-
-def num_range(s):
-    """a comma separated list of numbers 'a,b,c' or a range 'a-c' -> list of ints (the reference's option type, :25-33)"""
-    m = re.match(r'^(\d+)-(\d+)$', s)
-    if m:
-        return list(range(int(m.group(1)), int(m.group(2)) + 1))
-    return [int(x) for x in s.split(',')]
-
-
-def save_rgb(img, path):
-    """uint8 [H, W, 3] -> PNG, the way the reference's tools write every image (`PIL.Image.fromarray(img, 'RGB').save`)"""
-    import PIL.Image
-    PIL.Image.fromarray(np.ascontiguousarray(img), 'RGB').save(path)
-
-
-def to_uint8(img):
-    """synthesis output [N, C, H, W] -> uint8 [N, H, W, C] on the host (:98, :120)"""
-    return image_export.quantize(img.to(torch.float32), 'clamp').cpu().numpy()
+from .tool_support import (add_sampling_options, add_snapshot_option, class_label, config_overrides, device_of, load_generator, num_range, save_png,
+                           seed_latents, to_uint8)
 
 
 @torch.no_grad()
 def generate_images(G, seeds=None, truncation_psi=1, noise_mode='const', class_idx=None, projected_w=None, outdir=None, device=None):
     """-> uint8 images [N, H, W, 3], one per seed (or per projected w), written to `outdir` when it is given"""
-    device = torch.device(device) if device is not None else next(iter(G.buffers())).device
+    device = device_of(G, device)
     if outdir is not None:
         os.makedirs(outdir, exist_ok=True)
 
@@ -64,29 +42,21 @@ def generate_images(G, seeds=None, truncation_psi=1, noise_mode='const', class_i
         for idx, w in enumerate(ws):
             images.append(to_uint8(G.synthesis(w.unsqueeze(0), noise_mode=noise_mode))[0])
             if outdir is not None:
-                save_rgb(images[-1], f'{outdir}/proj{idx:02d}.png')
+                save_png(images[-1], f'{outdir}/proj{idx:02d}.png')
         return np.stack(images)
 
     if seeds is None:
         raise ValueError('--seeds option is required when not using --projected-w')
 
-    # Labels.
-    label = torch.zeros([1, G.c_dim], device=device)
-    if G.c_dim != 0:
-        if class_idx is None:
-            raise ValueError('Must specify class label with --class when using a conditional network')
-        label[:, class_idx] = 1
-    elif class_idx is not None:
-        print('warn: --class=lbl ignored when running on an unconditional network')
-
     # Generate images.
+    label = class_label(G, class_idx, device)
     images = []
     for seed_idx, seed in enumerate(seeds):
         print('Generating image for seed %d (%d/%d) ...' % (seed, seed_idx, len(seeds)))
-        z = torch.from_numpy(np.random.RandomState(seed).randn(1, G.z_dim)).to(device)
+        z = torch.from_numpy(seed_latents(G, [seed])).to(device)
         images.append(to_uint8(G(z, label, truncation_psi=truncation_psi, noise_mode=noise_mode))[0])
         if outdir is not None:
-            save_rgb(images[-1], f'{outdir}/seed{seed:04d}.png')
+            save_png(images[-1], f'{outdir}/seed{seed:04d}.png')
     return np.stack(images) if images else np.zeros([0, G.img_resolution, G.img_resolution, 3], dtype=np.uint8)
 
 
@@ -95,11 +65,9 @@ def generate_images(G, seeds=None, truncation_psi=1, noise_mode='const', class_i
 def parse_args(argv=None):
     """-> (config overrides as `key=value` strings, the tool's options)"""
     ap = argparse.ArgumentParser(prog='python -m style_big_gan_amd.generate', description=__doc__.split('\n')[0])
-    ap.add_argument('--snapshot', required=True, help='network-snapshot-*.pt of this build (G_ema, or G when there is no EMA)')
+    add_snapshot_option(ap)
     ap.add_argument('--seeds', type=num_range, help='list of random seeds')
-    ap.add_argument('--trunc', dest='truncation_psi', type=float, default=1, help='truncation psi (default: 1)')
-    ap.add_argument('--class', dest='class_idx', type=int, help='class label (unconditional if not specified)')
-    ap.add_argument('--noise-mode', choices=NOISE_MODES, default='const', help='noise mode (default: const)')
+    add_sampling_options(ap)
     ap.add_argument('--projected-w', help='projection result file (projected_w.npz of the projector)')
     ap.add_argument('--outdir', required=True, help='where to save the output images')
     args, rest = ap.parse_known_args(argv)
@@ -112,9 +80,8 @@ def run_generate(argv=None):
     overrides, args = parse_args(argv)
     from . import arguments
     config = arguments.load_config(overrides)
-    print(f'Loading networks from "{args.snapshot}"...')
     device = torch.device('cuda')
-    G = build_generator(config, snapshot_generator_state(args.snapshot), device)
+    G = load_generator(config, args.snapshot, device)
     return generate_images(G, seeds=args.seeds, truncation_psi=args.truncation_psi, noise_mode=args.noise_mode, class_idx=args.class_idx,
                            projected_w=args.projected_w, outdir=args.outdir, device=device)
 

@@ -46,10 +46,10 @@ import os
 import numpy as np
 import torch
 
-from .calc_metrics import dataset_kwargs_for, detector_kwargs, resolve_device
-from .generate import NOISE_MODES, num_range
-from .snapshot_io import build_generator, config_overrides, snapshot_generator_state
-from .torch_utils.ops import image_export, knn_manifold, nn_u8, resample_u8, resident_set
+from .tool_support import (add_device_option, add_sampling_options, add_snapshot_option, class_label, config_overrides, dataset_kwargs_for,  # noqa: F401
+                           detector_kwargs, device_of, generated_images, load_generator, num_range, open_dataset, require_file, save_png,
+                           snapshot_generator_state, tool_device)
+from .torch_utils.ops import knn_manifold, nn_u8, resample_u8, resident_set
 
 SPACES = ('pixel', 'vgg16')
 QUANTILES = (0.01, 0.05, 0.25, 0.50, 0.75)
@@ -104,21 +104,6 @@ def search(queries, store, k, mirrored, exclude=None):
     return key >> (_ROW_BITS + 1), key & ((1 << _ROW_BITS) - 1), (key >> _ROW_BITS) & 1
 
 
-def generated_queries(G, seeds, label, truncation_psi, noise_mode, device):
-    """the images of `seeds` in one batch, as the bytes generate.py writes -> uint8 [N, C, H, W] on `device`"""
-    z = torch.from_numpy(np.concatenate([np.random.RandomState(seed).randn(1, G.z_dim) for seed in seeds])).to(device)
-    img = G(z, label.expand(len(seeds), -1), truncation_psi=truncation_psi, noise_mode=noise_mode)
-    return image_export.quantize(img.to(torch.float32), 'clamp').permute(0, 3, 1, 2).contiguous()
-
-
-def rmse_summary(d2, F):
-    """min, the QUANTILES and the mean of sqrt(d2 / F)"""
-    rmse = np.sqrt(np.asarray(d2, dtype=np.float64) / F)
-    out = dict(min=float(rmse.min()), mean=float(rmse.mean()))
-    out.update({f'p{round(100 * q):02d}': float(v) for q, v in zip(QUANTILES, np.quantile(rmse, QUANTILES))})
-    return out
-
-
 def train_to_train(store, mirrored, batch):
     """-> int64 [S] on the store's device: d2 from every stored image to the nearest other image of the data set (its own row is excluded,
     as stored and mirrored)"""
@@ -133,9 +118,9 @@ def train_to_train(store, mirrored, batch):
     return out
 
 
-def dist_summary(d2):
-    """min, the QUANTILES and the mean of sqrt(d2)"""
-    dist = np.sqrt(np.asarray(d2, dtype=np.float64))
+def dist_summary(d2, F=1):
+    """min, the QUANTILES and the mean of sqrt(d2 / F): the distance, or with F the rmse over the F values of an image"""
+    dist = np.sqrt(np.asarray(d2, dtype=np.float64) / F)
     out = dict(min=float(dist.min()), mean=float(dist.mean()))
     out.update({f'p{round(100 * q):02d}': float(v) for q, v in zip(QUANTILES, np.quantile(dist, QUANTILES))})
     return out
@@ -192,7 +177,7 @@ def _feature_space(G, dataset, label, seeds, num, k, truncation_psi, noise_mode,
     result = dict(space='vgg16', F=F, res=dataset.resolution, k=k, mirrored=mirrored)
 
     def features_of(batch_seeds):
-        q = generated_queries(G, batch_seeds, label, truncation_psi, noise_mode, device)
+        q = generated_images(G, batch_seeds, label, truncation_psi, noise_mode, device)
         return q, detect(metric_utils._as_rgb(q), **call_kw).to(torch.float32)
 
     if seeds is not None:
@@ -211,10 +196,7 @@ def _feature_space(G, dataset, label, seeds, num, k, truncation_psi, noise_mode,
                                     dist=float(np.sqrt(d))) for d, i in zip(d2[r].tolist(), item[r].tolist())]
         result.update(neighbors=neighbors, canvas=canvas.cpu().numpy())
         if outdir is not None:
-            import PIL.Image
-            img = result['canvas']
-            png = PIL.Image.fromarray(img[:, :, 0], 'L') if C == 1 else PIL.Image.fromarray(np.ascontiguousarray(img), 'RGB')
-            png.save(os.path.join(outdir, 'neighbors.png'))
+            save_png(result['canvas'], os.path.join(outdir, 'neighbors.png'))
             with open(os.path.join(outdir, 'neighbors.json'), 'w') as f:
                 json.dump(dict(space='vgg16', F=F, k=k, seeds={str(s): v for s, v in neighbors.items()}), f, indent=2)
 
@@ -269,7 +251,7 @@ def nearest_training_images(G, dataset, seeds=None, num=None, k=5, res=None, tru
     batch = int(batch)
     if batch < 1:
         raise ValueError(f'--batch={batch}: must be at least 1')
-    device = torch.device(device) if device is not None else next(iter(G.buffers())).device
+    device = device_of(G, device)
     C, H, W = dataset.image_shape
     if (G.img_resolution, G.img_resolution) != (H, W) or getattr(G, 'img_channels', C) != C:
         raise ValueError(f'the generator makes {G.img_resolution} x {G.img_resolution} images, the data set holds {C} x {H} x {W}')
@@ -277,13 +259,7 @@ def nearest_training_images(G, dataset, seeds=None, num=None, k=5, res=None, tru
     if outdir is not None:
         os.makedirs(outdir, exist_ok=True)
 
-    label = torch.zeros([1, G.c_dim], device=device)
-    if G.c_dim != 0:
-        if class_idx is None:
-            raise ValueError('Must specify class label with --class when using a conditional network')
-        label[:, class_idx] = 1
-    elif class_idx is not None:
-        print('warn: --class=lbl ignored when running on an unconditional network')
+    label = class_label(G, class_idx, device)
     if space == 'vgg16':
         return _feature_space(G, dataset, label, seeds, num, k, truncation_psi, noise_mode, batch, outdir, device, max_gib, detector, dataset_kwargs,
                               dataset_name, cache_dir)
@@ -302,7 +278,7 @@ def nearest_training_images(G, dataset, seeds=None, num=None, k=5, res=None, tru
     result = dict(F=F, res=res if res is not None else dataset.resolution, k=k, mirrored=mirrored)
 
     def look_up(batch_seeds, kk):
-        q = generated_queries(G, batch_seeds, label, truncation_psi, noise_mode, device)
+        q = generated_images(G, batch_seeds, label, truncation_psi, noise_mode, device)
         return (q,) + search(reduce_images(q, res), small, kk, mirrored)
 
     if seeds is not None:
@@ -319,10 +295,7 @@ def nearest_training_images(G, dataset, seeds=None, num=None, k=5, res=None, tru
                                for t, (d, rw, f) in enumerate(zip(d2[0].cpu().tolist(), row[0].cpu().tolist(), fl[0].cpu().tolist()))]
         result.update(neighbors=neighbors, canvas=canvas.cpu().numpy())
         if outdir is not None:
-            import PIL.Image
-            img = result['canvas']
-            png = PIL.Image.fromarray(img[:, :, 0], 'L') if C == 1 else PIL.Image.fromarray(np.ascontiguousarray(img), 'RGB')
-            png.save(os.path.join(outdir, 'neighbors.png'))
+            save_png(result['canvas'], os.path.join(outdir, 'neighbors.png'))
             with open(os.path.join(outdir, 'neighbors.json'), 'w') as f:
                 json.dump(dict(F=F, res=result['res'], k=k, seeds={str(s): v for s, v in neighbors.items()}), f, indent=2)
 
@@ -332,8 +305,8 @@ def nearest_training_images(G, dataset, seeds=None, num=None, k=5, res=None, tru
         base = train_to_train(small, mirrored, max(1, min(batch, STORE_CHUNK_BYTES // F)))
         gen, base = gen.cpu().numpy(), base.cpu().numpy()
         p01 = float(np.quantile(base.astype(np.float64), 0.01))
-        stats = dict(F=F, res=result['res'], num=num, stored_images=S, mirrored=mirrored, gen_to_train=rmse_summary(gen, F),
-                     train_to_train=rmse_summary(base, F), train_p01_d2=p01, fraction_below_train_p01=float(np.mean(gen <= p01)))
+        stats = dict(F=F, res=result['res'], num=num, stored_images=S, mirrored=mirrored, gen_to_train=dist_summary(gen, F),
+                     train_to_train=dist_summary(base, F), train_p01_d2=p01, fraction_below_train_p01=float(np.mean(gen <= p01)))
         result.update(gen_to_train=gen, train_to_train=base, stats=stats)
         if outdir is not None:
             np.savez(os.path.join(outdir, 'nn_stats.npz'), gen_to_train=gen, train_to_train=base)
@@ -347,7 +320,7 @@ def nearest_training_images(G, dataset, seeds=None, num=None, k=5, res=None, tru
 def parse_args(argv=None):
     """-> (config overrides as `key=value` strings, the tool's options)"""
     ap = argparse.ArgumentParser(prog='python -m style_big_gan_amd.nearest_neighbors', description=__doc__.split('\n')[0])
-    ap.add_argument('--snapshot', required=True, help='network-snapshot-*.pt of this build (G_ema, or G when there is no EMA)')
+    add_snapshot_option(ap)
     ap.add_argument('--outdir', required=True, help='where to save neighbors.png / neighbors.json / nn_stats.npz / nn_stats.json')
     ap.add_argument('--seeds', type=num_range, help='seeds whose images get a row of neighbours')
     ap.add_argument('--num', type=int, help='distance statistics over the images of seeds 0..N-1')
@@ -357,10 +330,8 @@ def parse_args(argv=None):
     ap.add_argument('--res', type=int, help='compare box-reduced copies of this resolution (a power of two; default: full size)')
     ap.add_argument('--data', help='data set to search, folder or zip (default: the run\'s data.dataset_path)')
     ap.add_argument('--mirror', type=int, choices=(0, 1), help='whether the data set holds the x-flips (default: the run\'s data.mirror)')
-    ap.add_argument('--trunc', dest='truncation_psi', type=float, default=1, help='truncation psi (default: 1)')
-    ap.add_argument('--class', dest='class_idx', type=int, help='class label (unconditional if not specified)')
-    ap.add_argument('--noise-mode', choices=NOISE_MODES, default='const', help='noise mode (default: const)')
-    ap.add_argument('--device', choices=('auto', 'cuda', 'cpu'), default='auto', help='where to run (default: auto)')
+    add_sampling_options(ap)
+    add_device_option(ap)
     ap.add_argument('--batch', type=int, default=64, help='images generated and searched at a time with --num (default: 64)')
     args, rest = ap.parse_known_args(argv)
     if args.seeds is None and args.num is None:
@@ -380,32 +351,23 @@ def parse_args(argv=None):
             ap.error(f'--detector={args.detector}: no such TorchScript file or directory (detectors are not downloaded in this build)')
         if args.res is not None:
             ap.error('--res cannot be combined with --space=vgg16: the detector sees full-size images')
-    if not os.path.isfile(args.snapshot):
-        ap.error(f'--snapshot={args.snapshot}: no such file')
-    if args.mirror is not None:
-        args.mirror = bool(args.mirror)
+    require_file(ap, '--snapshot', args.snapshot)
+    args.mirror = None if args.mirror is None else bool(args.mirror)
     return config_overrides(ap, rest), args
 
 
 def run_nearest_neighbors(argv=None):
     overrides, args = parse_args(argv)
     from . import arguments
-    from .train_parts.datasets import datasets
     config = arguments.load_config(overrides)
-    dev_type = resolve_device(args.device)
-    device = torch.device('cuda', torch.cuda.current_device()) if dev_type == 'cuda' else torch.device('cpu')
-    print(f'Loading networks from "{args.snapshot}"...')
-    G = build_generator(config, snapshot_generator_state(args.snapshot), device)
+    device = tool_device(args.device)
+    G = load_generator(config, args.snapshot, device)
     kw = dataset_kwargs_for(config, G, data=args.data, mirror=args.mirror)
-    print('Dataset options:', kw)
-    dataset = datasets[config.data.dataset](**kw)
-    try:
+    with open_dataset(config, kw) as dataset:
         feature = dict(space=args.space, detector=args.detector, dataset_kwargs=kw, dataset_name=config.data.dataset) if args.space == 'vgg16' else {}
         result = nearest_training_images(G, dataset, seeds=args.seeds, num=args.num, k=args.k, res=args.res, truncation_psi=args.truncation_psi,
                                          noise_mode=args.noise_mode, class_idx=args.class_idx, batch=args.batch, outdir=args.outdir, device=device,
                                          **feature)
-    finally:
-        dataset.close()
     if 'stats' in result:
         print(json.dumps(result['stats']))
     return result

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from .snapshot_io import build_generator, config_overrides, generator_common_kwargs, snapshot_generator_state     # noqa: F401
+from .tool_support import add_snapshot_option, config_overrides, generator_common_kwargs, load_generator, save_png     # noqa: F401
 from .torch_utils.ops import projector as proj_ops
 
 LPIPS_KWARGS = dict(resize_images=False, return_lpips=True)
@@ -177,7 +177,7 @@ def load_target(path, resolution):
 def parse_args(argv=None):
     """-> (config overrides as `key=value` strings, the projector's options)"""
     ap = argparse.ArgumentParser(prog='python -m style_big_gan_amd.projector', description=__doc__.split('\n')[0])
-    ap.add_argument('--snapshot', required=True, help='network-snapshot-*.pt of this build (G_ema, or G when there is no EMA)')
+    add_snapshot_option(ap)
     ap.add_argument('--target', required=True, help='target image file to project')
     ap.add_argument('--outdir', required=True, help='where to save the output images')
     ap.add_argument('--num-steps', type=int, default=1000, help='number of optimization steps (default: 1000)')
@@ -200,9 +200,8 @@ def run_projection(argv=None):
     np.random.seed(args.seed)
     torch.manual_seed(args.seed)
 
-    print(f'Loading networks from "{args.snapshot}"...')
     device = torch.device('cuda')
-    G = build_generator(config, snapshot_generator_state(args.snapshot), device)
+    G = load_generator(config, args.snapshot, device)
 
     target_pil, target_uint8 = load_target(args.target, G.img_resolution)
 
@@ -225,10 +224,9 @@ def run_projection(argv=None):
                 video.append_data(np.concatenate([target_uint8, render(projected_w)], axis=1))
             video.close()
 
-        import PIL.Image
         target_pil.save(f'{args.outdir}/target.png')
         projected_w = projected_w_steps[-1]
-        PIL.Image.fromarray(render(projected_w), 'RGB').save(f'{args.outdir}/proj.png')
+        save_png(render(projected_w), f'{args.outdir}/proj.png')
         np.savez(f'{args.outdir}/projected_w.npz', w=projected_w.unsqueeze(0).cpu().numpy())
 
 

@@ -20,8 +20,8 @@ import os
 import numpy as np
 import torch
 
-from .generate import NOISE_MODES, num_range, save_rgb, to_uint8
-from .snapshot_io import build_generator, config_overrides, snapshot_generator_state
+from .tool_support import (add_sampling_options, add_snapshot_option, config_overrides, device_of, load_generator, num_range, save_png, seed_latents,
+                           to_uint8)
 from .torch_utils.ops import image_export
 
 
@@ -46,7 +46,7 @@ def grid_canvas(image_dict, row_seeds, col_seeds, resolution):
 @torch.no_grad()
 def generate_style_mix(G, row_seeds, col_seeds, col_styles=range(0, 7), truncation_psi=1, noise_mode='const', outdir=None, device=None, batch=16):
     """-> {(row_seed, col_seed): uint8 [H, W, 3]} in the reference's order: the unmixed images first, then the matrix row by row"""
-    device = torch.device(device) if device is not None else next(iter(G.buffers())).device
+    device = device_of(G, device)
     row_seeds, col_seeds, col_styles = list(row_seeds), list(col_seeds), list(col_styles)
     if outdir is not None:
         os.makedirs(outdir, exist_ok=True)
@@ -55,8 +55,7 @@ def generate_style_mix(G, row_seeds, col_seeds, col_styles=range(0, 7), truncati
     # The reference's `list(set(row_seeds + col_seeds))`: the order is whatever Python's set iteration gives.  It decides the batch order
     # of the mapping and synthesis calls and the order of the (seed, seed) keys only, never a result; it is reproduced as Python gives it.
     all_seeds = list(set(row_seeds + col_seeds))
-    all_z = np.stack([np.random.RandomState(seed).randn(G.z_dim) for seed in all_seeds])
-    all_w = G.mapping(torch.from_numpy(all_z).to(device), None).to(torch.float32)
+    all_w = G.mapping(torch.from_numpy(seed_latents(G, all_seeds)).to(device), None).to(torch.float32)
     w_avg = G.mapping.w_avg
     where = {seed: i for i, seed in enumerate(all_seeds)}
     S = len(all_seeds)
@@ -72,9 +71,9 @@ def generate_style_mix(G, row_seeds, col_seeds, col_styles=range(0, 7), truncati
     if outdir is not None:
         print('Saving images...')
         for (row_seed, col_seed), image in image_dict.items():
-            save_rgb(image, f'{outdir}/{row_seed}-{col_seed}.png')
+            save_png(image, f'{outdir}/{row_seed}-{col_seed}.png')
         print('Saving image grid...')
-        save_rgb(grid_canvas(image_dict, row_seeds, col_seeds, G.img_resolution), f'{outdir}/grid.png')
+        save_png(grid_canvas(image_dict, row_seeds, col_seeds, G.img_resolution), f'{outdir}/grid.png')
     return image_dict
 
 
@@ -83,12 +82,11 @@ def generate_style_mix(G, row_seeds, col_seeds, col_styles=range(0, 7), truncati
 def parse_args(argv=None):
     """-> (config overrides as `key=value` strings, the tool's options)"""
     ap = argparse.ArgumentParser(prog='python -m style_big_gan_amd.style_mixing', description=__doc__.split('\n')[0])
-    ap.add_argument('--snapshot', required=True, help='network-snapshot-*.pt of this build (G_ema, or G when there is no EMA)')
+    add_snapshot_option(ap)
     ap.add_argument('--rows', dest='row_seeds', type=num_range, required=True, help='random seeds to use for image rows')
     ap.add_argument('--cols', dest='col_seeds', type=num_range, required=True, help='random seeds to use for image columns')
     ap.add_argument('--styles', dest='col_styles', type=num_range, default=num_range('0-6'), help='style layer range (default: 0-6)')
-    ap.add_argument('--trunc', dest='truncation_psi', type=float, default=1, help='truncation psi (default: 1)')
-    ap.add_argument('--noise-mode', choices=NOISE_MODES, default='const', help='noise mode (default: const)')
+    add_sampling_options(ap, class_idx=False)
     ap.add_argument('--outdir', required=True, help='where to save the output images')
     args, rest = ap.parse_known_args(argv)
     return config_overrides(ap, rest), args
@@ -98,9 +96,8 @@ def run_style_mix(argv=None):
     overrides, args = parse_args(argv)
     from . import arguments
     config = arguments.load_config(overrides)
-    print(f'Loading networks from "{args.snapshot}"...')
     device = torch.device('cuda')
-    G = build_generator(config, snapshot_generator_state(args.snapshot), device)
+    G = load_generator(config, args.snapshot, device)
     return generate_style_mix(G, row_seeds=args.row_seeds, col_seeds=args.col_seeds, col_styles=args.col_styles, truncation_psi=args.truncation_psi,
                               noise_mode=args.noise_mode, outdir=args.outdir, device=device)
 

@@ -1,0 +1,168 @@
+"""What the snapshot tools (generate, style_mixing, projector, calc_metrics, nearest_neighbors, avg_spectra) share, each piece once: a generator
+built from the run's config and a ``network-snapshot-*.pt`` of this build (written by ``BaseTrainer.save_snapshot``), the ``key=value`` config
+overrides ``starter`` takes, the options several tools declare alike, the device and the data set of a run, the class label, the seeded latents
+and the bytes of generated images.  What a tool validates and the options whose help differs per tool stay in the tool."""
+import contextlib
+import os
+import re
+
+import numpy as np
+import torch
+
+from .torch_utils.ops import image_export
+
+NOISE_MODES = ('const', 'random', 'none')
+SNAPSHOT_HELP = 'network-snapshot-*.pt of this build (G_ema, or G when there is no EMA)'
+
+
+def num_range(s):
+    """a comma separated list of numbers 'a,b,c' or a range 'a-c' -> list of ints (the reference's option type, generate.py :25-33)"""
+    m = re.match(r'^(\d+)-(\d+)$', s)
+    return list(range(int(m.group(1)), int(m.group(2)) + 1)) if m else [int(x) for x in s.split(',')]
+
+
+def add_snapshot_option(ap, required=True, help=SNAPSHOT_HELP):
+    ap.add_argument('--snapshot', required=required, help=help)
+
+
+def add_sampling_options(ap, class_idx=True):
+    """--trunc, --class (unless `class_idx` is off) and --noise-mode, in this order"""
+    ap.add_argument('--trunc', dest='truncation_psi', type=float, default=1, help='truncation psi (default: 1)')
+    if class_idx:
+        ap.add_argument('--class', dest='class_idx', type=int, help='class label (unconditional if not specified)')
+    ap.add_argument('--noise-mode', choices=NOISE_MODES, default='const', help='noise mode (default: const)')
+
+
+def add_device_option(ap):
+    ap.add_argument('--device', choices=('auto', 'cuda', 'cpu'), default='auto', help='where to run (default: auto)')
+
+
+def require_file(ap, flag, path):
+    """an option that was given must name a file"""
+    if path is not None and not os.path.isfile(path):
+        ap.error(f'{flag}={path}: no such file')
+
+
+def config_overrides(parser, rest):
+    """the arguments an argparse parser did not recognise must all be `key=value` config overrides -> the list, or the parser's error"""
+    bad = [r for r in rest if '=' not in r or r.startswith('-')]
+    if bad:
+        parser.error(f'unrecognised arguments: {" ".join(bad)}')
+    return rest
+
+
+def resolve_device(name):
+    return name if name != 'auto' else 'cuda' if torch.cuda.is_available() else 'cpu'
+
+
+def tool_device(name):
+    """'auto' | 'cuda' | 'cpu' -> the torch.device a one-process tool runs on"""
+    return torch.device('cuda', torch.cuda.current_device()) if resolve_device(name) == 'cuda' else torch.device('cpu')
+
+
+def device_of(G, device):
+    """the given device, or the generator's"""
+    return torch.device(device) if device is not None else next(iter(G.buffers())).device
+
+
+def generator_common_kwargs(state):
+    """c_dim, img_resolution and img_channels of a generator, read from its state dict (the CLI has no data set to ask)"""
+    res = [int(m.group(1)) for k in state for m in [re.match(r'synthesis\.b(\d+)\.', k)] if m]
+    if not res:
+        raise RuntimeError('the snapshot holds no mapping/synthesis generator')
+    img_resolution = max(res)
+    torgb = state.get(f'synthesis.b{img_resolution}.torgb.weight')
+    embed = state.get('mapping.embed.weight')
+    return dict(c_dim=int(embed.shape[1]) if embed is not None else 0, img_resolution=img_resolution,
+                img_channels=int(torgb.shape[0]) if torgb is not None else 3)
+
+
+def build_generator(config, state, device):
+    """G through the `generators` registry with the config's gens_args, weights from `state` (strict)"""
+    from .train_parts.generators import generators
+    from .train_parts.trainers import BaseTrainer
+    name = config.gen.generator
+    kw = BaseTrainer._model_kwargs(config.gens_args[name], generator_common_kwargs(state))
+    G = generators[name](**kw)
+    G.load_state_dict(state, strict=True)
+    return G.eval().requires_grad_(False).to(device)
+
+
+def snapshot_generator_state(path):
+    """G_ema of a network-snapshot-*.pt, or G when the run kept no average"""
+    snap = torch.load(path, map_location='cpu', weights_only=True)
+    key = 'G_ema' if snap.get('G_ema') is not None else 'G'
+    if key not in snap:
+        raise RuntimeError(f'{path} holds neither G_ema nor G')
+    return snap[key]
+
+
+def load_generator(config, snapshot, device, announce=True):
+    """G of the snapshot file on `device`; `build_generator` is looked up when called, so a stand-in set on this module is used"""
+    if announce:
+        print(f'Loading networks from "{snapshot}"...')
+    return build_generator(config, snapshot_generator_state(snapshot), device)
+
+
+def dataset_kwargs_for(config, G, data=None, mirror=None):
+    """the data set kwargs of the run, with the tool's overrides: --data the path, --mirror the flips; the labels follow the network"""
+    from .train_parts.trainers import training_set_kwargs_from_config
+    return training_set_kwargs_from_config(config, seed=config.gen.seed, path=data, mirror=mirror, use_labels=G.c_dim != 0)
+
+
+@contextlib.contextmanager
+def open_dataset(config, kwargs):
+    """the run's data set built from `kwargs`, closed on exit"""
+    from .train_parts.datasets import datasets
+    print('Dataset options:', kwargs)
+    dataset = datasets[config.data.dataset](**kwargs)
+    try:
+        yield dataset
+    finally:
+        dataset.close()
+
+
+def detector_kwargs(detector):
+    """a callable or a TorchScript file -> MetricOptions(detector=...), a directory -> MetricOptions(detector_dir=...)"""
+    if callable(detector) or isinstance(detector, dict) or (isinstance(detector, str) and os.path.isfile(detector)):
+        return dict(detector=detector, detector_dir=None)
+    if isinstance(detector, str) and os.path.isdir(detector):
+        return dict(detector=None, detector_dir=detector)
+    raise ValueError(f'--detector={detector}: no such TorchScript file or directory (detectors are not downloaded in this build)')
+
+
+def class_label(G, class_idx, device):
+    """-> one-hot [1, c_dim] on `device`; a conditional network needs a class, an unconditional one ignores it with a warning"""
+    label = torch.zeros([1, G.c_dim], device=device)
+    if G.c_dim != 0:
+        if class_idx is None:
+            raise ValueError('Must specify class label with --class when using a conditional network')
+        label[:, class_idx] = 1
+    elif class_idx is not None:
+        print('warn: --class=lbl ignored when running on an unconditional network')
+    return label
+
+
+def seed_latents(G, seeds):
+    """-> float64 [len(seeds), z_dim], every row from a generator of its own seed (the reference's `randn(1, z_dim)` draws the same numbers)"""
+    return np.stack([np.random.RandomState(seed).randn(G.z_dim) for seed in seeds])
+
+
+def to_uint8(img):
+    """synthesis output [N, C, H, W] -> uint8 [N, H, W, C] on the host (the reference's generate.py :98, :120)"""
+    return image_export.quantize(img.to(torch.float32), 'clamp').cpu().numpy()
+
+
+def generated_images(G, seeds, label, truncation_psi, noise_mode, device):
+    """the images of `seeds` in one batch, as the bytes generate.py writes -> uint8 [N, C, H, W] on `device`"""
+    z = torch.from_numpy(seed_latents(G, seeds)).to(device)
+    img = G(z, label.expand(len(seeds), -1), truncation_psi=truncation_psi, noise_mode=noise_mode)
+    return image_export.quantize(img.to(torch.float32), 'clamp').permute(0, 3, 1, 2).contiguous()
+
+
+def save_png(img, path):
+    """uint8 [H, W, C] -> PNG: mode 'L' for one channel, 'RGB' for three (the way the reference's tools write every image)"""
+    import PIL.Image
+    img = np.ascontiguousarray(img)
+    assert img.ndim == 3 and img.shape[2] in [1, 3]
+    (PIL.Image.fromarray(img[:, :, 0], 'L') if img.shape[2] == 1 else PIL.Image.fromarray(img, 'RGB')).save(path)

@@ -66,14 +66,9 @@ def setup_snapshot_image_grid(training_set, random_seed=0):
 
 
 def write_grid_png(canvas, fname):
-    """uint8 HWC canvas -> PNG: mode 'L' for one channel, 'RGB' for three (reference :114-118)"""
-    import PIL.Image
-    canvas = np.ascontiguousarray(canvas)
-    assert canvas.ndim == 3 and canvas.shape[2] in [1, 3]
-    if canvas.shape[2] == 1:
-        PIL.Image.fromarray(canvas[:, :, 0], 'L').save(fname)
-    else:
-        PIL.Image.fromarray(canvas, 'RGB').save(fname)
+    """uint8 HWC canvas -> PNG: mode 'L' for one channel, 'RGB' for three (reference :114-118); the tools' writer"""
+    from ..tool_support import save_png
+    save_png(canvas, fname)
 
 
 def save_image_grid(img, fname, drange, grid_size):

@@ -127,7 +127,7 @@ def _cpu_generator(config, state, device):
 def test_cli_run_on_the_cpu(tmp_path, capsys, monkeypatch):
     _, overrides, snap, data = _run(tmp_path)
     det = _detectors(str(tmp_path / "det"))
-    monkeypatch.setattr(calc_metrics, "build_generator", _cpu_generator)
+    monkeypatch.setattr("style_big_gan_amd.tool_support.build_generator", _cpu_generator)
     fid, pr = scores.compute_fid, scores.compute_pr
     monkeypatch.setattr(scores, "compute_fid", lambda opts, max_real, num_gen, **kw: fid(opts, max_real=max_real, num_gen=24, **kw))
     monkeypatch.setattr(scores, "compute_pr", lambda opts, max_real, num_gen, nhood_size, row_batch_size, col_batch_size, **kw:

@@ -151,7 +151,7 @@ def _stats_of(d2, F):
 def test_cli_run_on_the_cpu(tmp_path, capsys, monkeypatch):
     """the whole tool from a snapshot the trainer wrote, the generator evaluated by the CPU restatement of the same network"""
     _, overrides, snap, data = _run(tmp_path)
-    monkeypatch.setattr(NN, "build_generator", _cpu_generator)
+    monkeypatch.setattr("style_big_gan_amd.tool_support.build_generator", _cpu_generator)
     out = tmp_path / "out"
     result = NN.run_nearest_neighbors(overrides + [f"--snapshot={snap}", f"--outdir={out}", "--seeds=3,0,11", "--num=10", "--k=4", "--batch=4",
                                                    "--device=cpu"])
@@ -215,7 +215,7 @@ def test_a_generator_that_returns_training_images_is_flagged(tmp_path, monkeypat
     _, overrides, snap, data = _run(tmp_path)
     dataset = ImageFolderDataset(path=data, xflip=True)
     bank = np.stack([dataset[i][0] for i in range(0, 40, 3)])   # training images, mirrored ones among them
-    monkeypatch.setattr(NN, "build_generator", lambda config, state, device: N.BankGenerator(bank).to(device))
+    monkeypatch.setattr("style_big_gan_amd.tool_support.build_generator", lambda config, state, device: N.BankGenerator(bank).to(device))
     out = tmp_path / "out"
     result = NN.run_nearest_neighbors(overrides + [f"--snapshot={snap}", f"--outdir={out}", "--num=30", "--res=8", "--batch=7", "--device=cpu"])
     stats = json.load(open(out / "nn_stats.json"))

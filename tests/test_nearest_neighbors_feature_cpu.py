@@ -201,7 +201,7 @@ def test_a_stale_cache_file_is_recomputed(tmp_path):
 def test_cli_run_on_the_cpu(tmp_path, capsys, monkeypatch):
     """the whole tool from a snapshot the trainer wrote, with a TorchScript vgg16.pt; and --space=pixel against a run without the option"""
     _, overrides, snap, data = _run(tmp_path)
-    monkeypatch.setattr(NN, "build_generator", _cpu_generator)
+    monkeypatch.setattr("style_big_gan_amd.tool_support.build_generator", _cpu_generator)
     monkeypatch.setenv("SBG_CACHE_DIR", str(tmp_path / "cache"))
     det = tmp_path / "det"
     os.makedirs(det)

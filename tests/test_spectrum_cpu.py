@@ -216,7 +216,7 @@ def test_tool_end_to_end(tmp_path, monkeypatch, capsys):
     _, overrides, snap, _ = _run(tmp_path)
     data, items = SU.tool_dataset(tmp_path)
     bank = [items]
-    monkeypatch.setattr(AS, "build_generator", lambda config, state, device: SU.OrderedGenerator(bank[0]).to(device))
+    monkeypatch.setattr("style_big_gan_amd.tool_support.build_generator", lambda config, state, device: SU.OrderedGenerator(bank[0]).to(device))
     common = overrides + [f"--data={data}", "--device=cpu", "--batch=7", "--interp=2"]
 
     # the data set alone

@@ -79,7 +79,7 @@ def test_tool_on_the_device_equals_the_cpu_run(dev, tmp_path, monkeypatch):
     data, items = SU.tool_dataset(tmp_path)
     yy, xx = np.meshgrid(np.arange(16), np.arange(16), indexing="ij")
     bank = (items.astype(np.int64) + (8 * (-1) ** (xx + yy))[None, None]).astype(np.uint8)
-    monkeypatch.setattr(AS, "build_generator", lambda config, state, device: SU.OrderedGenerator(bank).to(device))
+    monkeypatch.setattr("style_big_gan_amd.tool_support.build_generator", lambda config, state, device: SU.OrderedGenerator(bank).to(device))
     runs = {}
     for device in ("cuda", "cpu"):
         out = tmp_path / device
