@@ -655,6 +655,20 @@ int sbg_spectrum_rows(const void* images, int is_u8, const float* window, const 
 int sbg_spectrum_cols(const void* workspace, const float* window, const float* stages, double* acc, int64_t BC, int R, int S, sbg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Multi-scale structural similarity between two image batches (Wang, Simoncelli, Bovik 2003; the pairwise diversity tool diversity.py; the
+ * reference has no counterpart).  The definition -- float64 moments under a separable 11-tap window whose every rounding is stated, the SSIM
+ * map and fixed-order float64 means -- is in csrc/msssim.hip and DESIGN.md section 23; torch_utils/ops/msssim.py evaluates it for CPU tensors
+ * to the same bits.  Images are byte values, uint8 when is_u8, else fp32, [BC, S, S] (BC image-channels).
+ *   sbg_msssim_workspace: bytes of the tile partials of one level call (S a power of two in [16, 16384]), -1 for unsupported sizes.
+ *   sbg_msssim_level: out[bc] = {mean of cs, mean of ssim} (float64 [BC, 2]) over the (S - 10)^2 map of x[bc] against y[bc]; window: float64
+ *                     [11]; C1, C2: the stabilising constants.  Two launches (tiles, merge), no atomics: two runs give the same bits.
+ *   sbg_msssim_down:  y (fp32 [BC, S/2, S/2]) = the 2 x 2 box mean ((a + b) + (c + d)) * 0.25f of x; S a power of two in [2, 16384]. */
+int64_t sbg_msssim_workspace(int64_t BC, int S);
+int sbg_msssim_level(const void* x, const void* y, int is_u8, const double* window, double C1, double C2, double* out, void* workspace, int64_t BC, int S,
+                     sbg_stream_t stream);
+int sbg_msssim_down(const void* x, int is_u8, float* y, int64_t BC, int S, sbg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * In-process launch timing (measurement only; bench.py's roofline figures come from here).
  * While enabled, every kernel launch of this library is bracketed by two hipEvents recorded on the launch stream
  * and logged with its algorithmic flops / bytes.  sbg_prof_fetch() synchronises the logged events, writes up to `max`
@@ -680,7 +694,8 @@ enum sbg_kernel_kind {
                                  * store runs per query tile) / 3 merge; then Q, M, F clipped to INT32_MAX, k, runs */
     SBG_K_SWD = 27,             /* dims[0] = variant: 0 pyr_down (B, C, S) / 1 pyr_lap (B, C, S) / 2 gather (B, C, S, P) / 3 moments (M, C, chunks) /
                                  * 4 project (M, K, D) / 5 l1 (D, M, chunks) / 6 merge of the float64 partials (values, chunks); M clipped to INT32_MAX */
-    SBG_K_SPECTRUM = 28         /* dims[0] = variant: 0 rows / 1 cols; then BC (image-channels of the call), R, S */
+    SBG_K_SPECTRUM = 28,        /* dims[0] = variant: 0 rows / 1 cols; then BC (image-channels of the call), R, S */
+    SBG_K_MSSSIM = 29           /* dims[0] = variant: 0 level / 1 down / 2 merge; then BC (image-channels of the call, clipped to INT32_MAX), S */
 };
 /* Kernel-variant codes in the records of the streaming kernels (which kernel served the launch):
  *   bias_act     dims[4] = 1 vec8 / 2 scalar,  dims[5] = bias mode (0 none, 1 channel-minor vector, 2 one per 8-vector, 3 generic)
