@@ -531,6 +531,22 @@ int sbg_knn_probe(const void* probes, const void* manifold, const void* radius, 
 int64_t sbg_knn_topk_workspace(int Q, int M, int k);
 int sbg_knn_topk(const void* queries, const void* manifold, int Q, int M, int64_t F, int k, const int32_t* exclude, float* d2, int32_t* index,
                  void* workspace, sbg_stream_t stream);
+/* Per-probe realism score (Kynkaanniemi et al., "Improved Precision and Recall Metric for Assessing Generative Models", NeurIPS 2019,
+ * section 5; the reference has no such pass), same kernels and arithmetic, on the fp16 d of the membership test.  With radius fp16 [C]
+ * (negative: the point is pruned and takes no part) and exclude int32 [P] on the device or NULL (a manifold index, or -1 for none):
+ *   eligible(i, j) = radius[j] >= 0 and j != exclude[i]
+ *   q(i, j) = +inf when d(i, j) == 0 (also at radius 0), else float(radius[j]) / float(d(i, j)): one IEEE fp32 division (a radius of -0
+ *             counts as +0)
+ *   score[i] (fp32 [P]) = max of q(i, j) over the eligible j, 0 when there is none;
+ *   index[i] (int32 [P]) = the lowest eligible j attaining it, -1 when there is none.
+ * Without `exclude`, score >= 1 is exactly sbg_knn_in_manifold's flag.  P, C in [1, 2^24]; F a multiple of 8; dense 16-byte aligned rows
+ * and workspace; only `exclude` may be NULL; anything else is SBG_ERR_INVALID and launches nothing.  Workspace of
+ * sbg_knn_realism_workspace(P, C) bytes (-1 for unsupported sizes): up16(4 P) + up16(4 C) + (runs > 1 ? 8 P runs : 0), one 64-bit key
+ * bits(score) << 32 | ~j per (run, row), merged by an unsigned maximum.  No atomics, and keys of distinct columns are distinct: any
+ * split and any two calls give the same bits. */
+int64_t sbg_knn_realism_workspace(int P, int C);
+int sbg_knn_realism(const void* probes, const void* manifold, const void* radius, int P, int C, int64_t F, const int32_t* exclude, float* score,
+                    int32_t* index, void* workspace, sbg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * End of a training phase over a flat fp32 gradient bucket: the reference's per-parameter loop `misc.nan_to_num(param.grad, nan=0,
@@ -684,7 +700,7 @@ enum sbg_kernel_kind {
     SBG_K_RESAMPLE = 21,        /* dims[0] = variant: 0 h (N, rows, in_w, out_w, C, dims[6] = strip), 1 v (N, row_bytes, in_h, out_h, ksize,
                                  * dims[6] = 1 dword / 2 byte loads) */
     SBG_K_PR = 22,              /* dims[0] = variant: 0 single / 1 split (the tile kernel, one / several column runs per row tile), 2 merge,
-                                 * 3 norms; then R, C, F, k, runs, dims[6] = 0 radius / 1 membership / 2 probe */
+                                 * 3 norms; then R, C, F, k, runs, dims[6] = 0 radius / 1 membership / 2 probe / 3 top-k / 4 realism */
     SBG_K_GRAD_FINISH = 23,     /* dims[0] = variant: 0 sweep (records, n clipped to INT32_MAX, dims[3] = 1 when the scale is applied),
                                  * 1 merge (records) */
     SBG_K_RESIDENT = 24,        /* dims = B, C, H, W, out_f32, 0, dims[6] = 1 dword path (4 pixels per work-item) / 2 byte path */

@@ -117,7 +117,7 @@ PROJ_VARIANTS = {0: "reg", 1: "reg_bwd", 2: "normalize", 3: "sqdist", 4: "sqdist
 IMG_VARIANTS = {0: "quantize_tile", 1: "truncate_mix"}      # dims[0] of an "image_export" launch record
 QUANT_RULES = {"grid": 0, "clamp": 1}                       # enum sbg_quant_rule
 RESAMPLE_VARIANTS = {0: "h", 1: "v"}                        # dims[0] of a "resample" launch record
-PR_VARIANTS = {0: "single", 1: "split", 2: "merge", 3: "norms"}    # dims[0] of a "pr" launch record (dims[6]: 0 radius, 1 membership, 2 probe, 3 top-k)
+PR_VARIANTS = {0: "single", 1: "split", 2: "merge", 3: "norms"}    # dims[0] of a "pr" launch record (dims[6]: 0 radius, 1 membership, 2 probe, 3 top-k, 4 realism)
 GRAD_FINISH_VARIANTS = {0: "sweep", 1: "merge"}             # dims[0] of a "grad_finish" launch record
 DIFFAUG_VARIANTS = {0: "sum", 1: "apply", 2: "adj_sum", 3: "adj_apply", 4: "single", 5: "adj_single"}      # dims[0] of a "diffaug" launch record
 DIFFAUG_WORDS = 12                                          # SBG_DIFFAUG_WORDS: int32 words per sample of the packed parameter table
@@ -208,6 +208,8 @@ SYMBOLS = [
     ("sbg_knn_probe", _c.c_int, [_c.c_void_p] * 3 + [_c.c_int, _c.c_int, _c.c_int64] + [_c.c_void_p] * 4),
     ("sbg_knn_topk_workspace", _c.c_int64, [_c.c_int] * 3),
     ("sbg_knn_topk", _c.c_int, [_c.c_void_p] * 2 + [_c.c_int, _c.c_int, _c.c_int64, _c.c_int] + [_c.c_void_p] * 5),
+    ("sbg_knn_realism_workspace", _c.c_int64, [_c.c_int] * 2),
+    ("sbg_knn_realism", _c.c_int, [_c.c_void_p] * 3 + [_c.c_int, _c.c_int, _c.c_int64] + [_c.c_void_p] * 5),
     ("sbg_grad_finish_records", _c.c_int64, [_c.c_int64]),
     ("sbg_grad_finish_sweep", _c.c_int, [_c.c_void_p, _c.c_int64, _c.c_float, _c.c_void_p, _c.c_void_p]),
     ("sbg_grad_finish_merge", _c.c_int, [_c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_void_p]),

@@ -7,6 +7,9 @@
 //                 -- the pass behind density / coverage (Naeem et al., ICML 2020) and, as count > 0, behind precision / recall
 //   topk:         d2[i, t], index[i, t] = the t-th smallest (d2(queries[i], manifold[j]), j) over j != exclude[i]   (fp32, int32; t < k <= 8)
 //                 -- the feature-space search of nearest_neighbors.py; selection is on d2 itself, nothing is rounded to fp16
+//   realism:      score[i] = max_j radius[j] / d(probes[i], manifold[j]) over the j with radius[j] >= 0 and j != exclude[i]  (fp32; +inf where
+//                 d == 0; 0 when there is no such j),  index[i] = the lowest j attaining it  (int32; -1 when there is none)
+//                 -- the realism score of Kynkaanniemi et al. (NeurIPS 2019, section 5); a pruned ball is a negative radius
 // Arithmetic: n(x) = sum x_f^2 and s(x, y) = sum x_f y_f are fp32 sums of fp16 products; d2 = max((n(x) + n(y)) - 2 s, 0) in fp32;
 // d = fp16_rn(sqrt_f32(d2)).  Rounding is monotone, so the radius kernel selects on d2 (and the probe pass takes its minimum on d2) and
 // rounds the selected value once.
@@ -24,10 +27,11 @@
 // merges the runs in index order (`split` + `merge`).  The lists, their keys, the split and the merge of lists are knn_select.h's, with
 // its order and tie rules; an OR, an integer sum and a minimum do not depend on the order either, and there are no atomics: two runs
 // give the same bits.
+// Realism candidates are RealismKey (below): one unsigned maximum orders by score, then by the lower index, and is order-free as well.
 // Top-k candidates are knn_select.h's KeyF32, which needs d2 never negative and never -0: n(x) + n(y) is a sum of squares, so +0 or
 // positive; a - b of two floats is -0 only for a = -0, b = +0 (a - a is +0 under round-to-nearest), so (n(x) + n(y)) - 2 s is +0,
 // positive, or negative and then replaced by the +0 of fmaxf(., 0).  A row past the end, or equal to exclude[q], gets the sentinel.
-// Launch-log key: kind SBG_K_PR, dims = {variant (0 single, 1 split, 2 merge, 3 norms), R, C, F, k, runs, 0 radius / 1 membership / 2 probe / 3 top-k}.
+// Launch-log key: kind SBG_K_PR, dims = {variant (0 single, 1 split, 2 merge, 3 norms), R, C, F, k, runs, 0 radius / 1 membership / 2 probe / 3 top-k / 4 realism}.
 #include "conv_common.h"
 #include "knn_select.h"
 #include "reduce.h"
@@ -38,7 +42,7 @@ using namespace knnsel;
 namespace {
 
 constexpr int kPrSingle = 0, kPrSplit = 1, kPrMerge = 2, kPrNorms = 3;
-constexpr int kRadius = 0, kMember = 1, kProbe = 2, kTopk = 3;       // what the tile kernel reduces a query row's distances to (dims[6] of a record)
+constexpr int kRadius = 0, kMember = 1, kProbe = 2, kTopk = 3, kRealism = 4;       // what the tile kernel reduces a query row's distances to (dims[6] of a record)
 
 constexpr int BK = 64;                      // K-step
 constexpr int KG = BK / 8;                  // 16-B k-groups per K-step
@@ -54,10 +58,10 @@ struct KnnArgs {
     const unsigned short* q; const unsigned short* m;     // query rows [R, F], manifold [C, F]
     const float* nq; const float* nm;                      // their squared norms
     const unsigned short* radius;                          // membership and probe: fp16 [C]
-    union { void* out; float* d2; };                       // radius fp16 [R], membership uint8 [R], probe count int32 [R]; top-k: d2 [R, k]
-    union { void* nearest = nullptr; int32_t* index; };    // the probe's second output, fp16 [R]; top-k: index [R, k]
+    union { void* out; float* d2; };                       // radius fp16 [R], membership uint8 [R], probe count int32 [R]; top-k: d2 [R, k]; realism: score fp32 [R]
+    union { void* nearest = nullptr; int32_t* index; };    // the probe's second output, fp16 [R]; top-k: index [R, k]; realism: index [R]
     void* part;
-    const int32_t* exclude = nullptr;                      // top-k: [R] or null
+    const int32_t* exclude = nullptr;                      // top-k and realism: [R] or null
     int R, C, F, k, runs, ctiles, tiles_per_run;
 };
 
@@ -87,6 +91,25 @@ __device__ __forceinline__ float dist_f16(float d2) { return (float)(_Float16)sq
 
 struct ProbePart { int count; float d2; };                 // a run's share of a probe row: balls that hold it, smallest d2
 
+// A realism candidate: (uint64(bits(score)) << 32) | ~row, unsigned, so the LARGEST key is the highest score and, among equal scores, the
+// lowest row.  A score is +0, positive or +inf (radius >= 0 over d > 0, its sign bit cleared so that a radius of -0 counts as +0): such
+// floats order as their bits do.  Rows are below 2^24, so ~row is never 0 and every candidate's key is above `none`; `none` itself
+// decodes to what a row without candidates gets, score 0 and index -1.  Keys of distinct rows are distinct: a maximum over them does
+// not depend on the order, the split or the launch.  Every candidate is divided: there is no pre-test.
+struct RealismKey {
+    static constexpr uint64_t none = 0;
+    static __device__ __forceinline__ uint64_t make(float radius, float d, int row)
+    {
+        const float q = d == 0.f ? __builtin_inff() : radius / d;          // one IEEE division of the two fp16 values; 0 / 0 is never kept
+        return ((uint64_t)(__float_as_uint(q) & 0x7fffffffu) << 32) | (uint32_t)~row;
+    }
+    static __device__ __forceinline__ void store(uint64_t key, float* score, int32_t* index)
+    {
+        *score = __uint_as_float((uint32_t)(key >> 32));
+        *index = (int32_t)~(uint32_t)key;
+    }
+};
+
 // What the radius mode writes for row q from its merged list of d2 (a multiset: kthvalue counts duplicates): the k-th entry, as fp16
 struct RadiusFinish {
     using type = float;
@@ -105,7 +128,7 @@ struct RadiusFinish {
 template <int KL, int MODE>
 __device__ __forceinline__ void knn_tile_body(const KnnArgs& p)
 {
-    constexpr bool MEMBER = MODE == kMember, PROBE = MODE == kProbe, TOPK = MODE == kTopk;
+    constexpr bool MEMBER = MODE == kMember, PROBE = MODE == kProbe, TOPK = MODE == kTopk, REALISM = MODE == kRealism;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     float* const prm = reinterpret_cast<float*>(smem + PARAM_OFF);          // [parity][0: norm, 1: radius][BT]
 
@@ -133,14 +156,18 @@ __device__ __forceinline__ void knn_tile_body(const KnnArgs& p)
     for (int j = 0; j < 4; j++) { const int r = q0 + wp + 16 * j + fr; nqv[j] = r < p.R ? p.nq[r] : 0.f; }
 
     uint64_t T[4][TOPK ? KL : 1];       // top-k: the lists of keys
+    uint64_t best[4];                   // realism: the largest key
     int excl[4];
-    if constexpr (TOPK) {
+    if constexpr (TOPK || REALISM) {
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const int r = q0 + wp + 16 * j + fr;
             excl[j] = (r < p.R && p.exclude) ? p.exclude[r] : -1;
+            best[j] = RealismKey::none;
+            if constexpr (TOPK) {
 #pragma unroll
-            for (int t = 0; t < KL; t++) T[j][t] = KeyF32::none;
+                for (int t = 0; t < KL; t++) T[j][t] = KeyF32::none;
+            }
         }
     }
 
@@ -168,7 +195,7 @@ __device__ __forceinline__ void knn_tile_body(const KnnArgs& p)
         if (tid < BT) {       // a padded column is at +inf (and has a negative radius): read after the K loop's barriers
             const int c = c0 + tid;
             prm[(par * 2 + 0) * BT + tid] = c < p.C ? p.nm[c] : __builtin_inff();
-            if (MEMBER || PROBE) prm[(par * 2 + 1) * BT + tid] = c < p.C ? f16_bits_to_f32(p.radius[c]) : -1.f;
+            if (MEMBER || PROBE || REALISM) prm[(par * 2 + 1) * BT + tid] = c < p.C ? f16_bits_to_f32(p.radius[c]) : -1.f;
         }
 
         short8_t ra[4], rb[4];
@@ -234,11 +261,16 @@ __device__ __forceinline__ void knn_tile_body(const KnnArgs& p)
             for (int e = 0; e < 4; e++) {
                 const int col = wc + 16 * i + 4 * fg + e;
                 const float nmv = prm[(par * 2 + 0) * BT + col];
-                const float rv = (MEMBER || PROBE) ? prm[(par * 2 + 1) * BT + col] : 0.f;
+                const float rv = (MEMBER || PROBE || REALISM) ? prm[(par * 2 + 1) * BT + col] : 0.f;
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
                     const float d2 = dist2(nqv[j], nmv, acc[i][j][e]);
                     if constexpr (TOPK) { const int row = c0 + col; keep_smallest<KL>(T[j], (row < p.C && row != excl[j]) ? KeyF32::make(d2, row) : KeyF32::none); }
+                    else if constexpr (REALISM) {       // a padded column has radius -1, as a pruned point has: its row needs no test
+                        const int row = c0 + col;
+                        const uint64_t key = (rv >= 0.f && row != excl[j]) ? RealismKey::make(rv, dist_f16(d2), row) : RealismKey::none;
+                        best[j] = key > best[j] ? key : best[j];
+                    }
                     else if (MEMBER) inside[j] |= (dist_f16(d2) <= rv) ? 1 : 0;
                     else if (PROBE) { inside[j] += (dist_f16(d2) <= rv) ? 1 : 0; nearest[j] = fminf(nearest[j], d2); }
                     else keep_smallest<KL>(L[j], d2);
@@ -288,6 +320,21 @@ __device__ __forceinline__ void knn_tile_body(const KnnArgs& p)
                 reinterpret_cast<ProbePart*>(p.part)[(int64_t)run * p.R + q] = ProbePart{c, v};
             }
         }
+    } else if constexpr (REALISM) {
+        uint64_t* bs = reinterpret_cast<uint64_t*>(smem);        // [manifold wave][BT] keys
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            uint64_t v = best[j], o;
+            o = __shfl_xor(v, 16, 64); v = o > v ? o : v;
+            o = __shfl_xor(v, 32, 64); v = o > v ? o : v;
+            if (fg == 0) bs[(wave >> 1) * BT + wp + 16 * j + fr] = v;
+        }
+        __syncthreads();
+        if (tid < BT && q < p.R) {
+            const uint64_t a = bs[tid], b = bs[BT + tid], v = a > b ? a : b;
+            if (p.runs == 1) RealismKey::store(v, p.d2 + q, p.index + q);
+            else reinterpret_cast<uint64_t*>(p.part)[(int64_t)run * p.R + q] = v;
+        }
     } else {
         finish_run<KL, PARAM_OFF>(smem, L, q0, p.R, p.runs, run, reinterpret_cast<float*>(p.part), RadiusFinish{reinterpret_cast<unsigned short*>(p.out), p.k});
     }
@@ -297,6 +344,8 @@ template <int KL, bool MEMBER>
 __global__ __launch_bounds__(256) void knn_tile_kernel(KnnArgs p) { knn_tile_body<KL, MEMBER ? kMember : kRadius>(p); }
 
 __global__ __launch_bounds__(256) void knn_probe_tile_kernel(KnnArgs p) { knn_tile_body<4, kProbe>(p); }
+
+__global__ __launch_bounds__(256) void knn_realism_tile_kernel(KnnArgs p) { knn_tile_body<4, kRealism>(p); }
 
 // two waves per SIMD: without the bound KL = 8 takes 198 + 64 registers and a CU holds one workgroup; with it 254, no scratch
 template <int KL>
@@ -324,14 +373,24 @@ __global__ __launch_bounds__(256) void knn_merge_probe_kernel(const ProbePart* _
     nearest[q] = f32_to_f16_bits(sqrtf(v));
 }
 
+__global__ __launch_bounds__(256) void knn_merge_realism_kernel(const uint64_t* __restrict__ part, float* __restrict__ score, int32_t* __restrict__ index,
+                                                                int R, int runs)
+{
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= R) return;
+    uint64_t v = RealismKey::none;
+    for (int s = 0; s < runs; s++) { const uint64_t t = part[(int64_t)s * R + q]; v = t > v ? t : v; }
+    RealismKey::store(v, score + q, index + q);
+}
+
 int list_len(int k) { return k + 1 <= 4 ? 4 : 8; }         // radius: the (k + 1)-th neighbour
 
 // The plan of a mode: its k limits, and what a run leaves per query row -- a list of floats (radius), one byte (membership; the bytes
-// of all rows together are rounded up to 16), a ProbePart (probe), a list of 64-bit keys (top-k).
+// of all rows together are rounded up to 16), a ProbePart (probe), a list of 64-bit keys (top-k), one RealismKey (realism).
 bool knn_plan(int R, int C, int k, int mode, RunPlan& pl)
 {
     if (mode == kTopk ? (k < 1 || k > kMaxTopk) : (k < 0 || k + 1 > kMaxK1)) return false;
-    const int64_t part = mode == kMember ? 1 : mode == kProbe ? (int64_t)sizeof(ProbePart) : mode == kTopk ? 8 * topk_list_len(k) : 4 * list_len(k);
+    const int64_t part = mode == kMember ? 1 : mode == kProbe ? (int64_t)sizeof(ProbePart) : mode == kRealism ? 8 : mode == kTopk ? 8 * topk_list_len(k) : 4 * list_len(k);
     if (!plan_runs(R, C, 4, part, pl)) return false;
     if (mode == kMember) pl.bytes = up16(pl.bytes);
     return true;
@@ -371,6 +430,7 @@ constexpr auto knn_tile_kernel_of()
 {
     if constexpr (MODE == kTopk) return knn_topk_tile_kernel<KL>;
     else if constexpr (MODE == kProbe) return knn_probe_tile_kernel;
+    else if constexpr (MODE == kRealism) return knn_realism_tile_kernel;
     else return knn_tile_kernel<KL, MODE == kMember>;
 }
 
@@ -468,6 +528,30 @@ extern "C" int sbg_knn_probe(const void* probes, const void* manifold, const voi
         SbgProfScope prof(s, SBG_K_PR, 0.0, 8.0 * P * (double)pl.runs + 6.0 * P, {kPrMerge, P, C, a.F, 0, pl.runs, kProbe});
         SBG_LAUNCH(knn_merge_probe_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, (const ProbePart*)a.part, (int*)count, (unsigned short*)nearest,
                    P, pl.runs);
+        SBG_HIP_LAUNCH_CHECK();
+    }
+    return SBG_OK;
+}
+
+extern "C" int64_t sbg_knn_realism_workspace(int P, int C)
+{
+    RunPlan pl;
+    if (!knn_plan(P, C, 0, kRealism, pl)) return -1;
+    return pl.bytes;
+}
+
+extern "C" int sbg_knn_realism(const void* probes, const void* manifold, const void* radius, int P, int C, int64_t F, const int32_t* exclude, float* score,
+                               int32_t* index, void* workspace, sbg_stream_t stream)
+{
+    SBG_CHECK(radius && index, "knn_realism: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    KnnArgs a; RunPlan pl;
+    a.index = index; a.exclude = exclude;
+    const int st = knn_run<kRealism>("knn_realism", probes, manifold, radius, P, C, F, 0, score, workspace, s, a, pl);
+    if (st != SBG_OK) return st;
+    if (pl.runs > 1) {
+        SbgProfScope prof(s, SBG_K_PR, 0.0, 8.0 * P * (double)pl.runs + 8.0 * P, {kPrMerge, P, C, a.F, 0, pl.runs, kRealism});
+        SBG_LAUNCH(knn_merge_realism_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, (const uint64_t*)a.part, score, index, P, pl.runs);
         SBG_HIP_LAUNCH_CHECK();
     }
     return SBG_OK;

@@ -1,6 +1,6 @@
 """The scores computed from feature statistics: Frechet distance (FID), kernel distance (KID), Inception score (IS), improved
 precision / recall (PR) and, beyond the reference, density / coverage (PRDC: Naeem et al., "Reliable Fidelity and Diversity Metrics
-for Generative Models", ICML 2020) and the detector-free sliced Wasserstein distance on Laplacian-pyramid patches (SWD: Karras et al.,
+for Generative Models", ICML 2020), the per-image realism score of the improved precision / recall paper (`realism_scores`) and the detector-free sliced Wasserstein distance on Laplacian-pyramid patches (SWD: Karras et al.,
 "Progressive Growing of GANs", ICLR 2018, section 5; the last part of this file).  Arithmetic of the reference's ``stylegan2ada/metrics/{frechet_inception_distance, kernel_inception_distance,
 inception_score, precision_recall}.py``; each function cites the lines it follows.  Detector names are the reference's file names; the
 files themselves are never fetched (see metric_utils.get_feature_detector)."""
@@ -219,6 +219,53 @@ def compute_prdc(opts, max_real, num_gen, nhood_size, row_batch_size, dataset_na
     gen = metric_utils.compute_feature_stats_for_generator(opts=opts, dataset_name=dataset_name, detector_url=VGG16, detector_kwargs=kw, rel_lo=0, rel_hi=1,
                                                            capture_all=True, max_items=num_gen).get_all_torch().to(half).to(opts.device)
     return prdc_fused(real, gen, nhood_size, row_batch_size, opts.num_gpus, opts.rank)       # the kernels on the device, the op layer's torch path on the CPU
+
+
+def pruned_radii(radius, keep):
+    """fp16 radii [N] -> the same with all but the ceil(keep * N) smallest set to -1: the realism score's pruning of the balls that reach
+    too far.  Among equal radii the lower index is kept (a stable sort of the fp16 values)."""
+    n = radius.shape[0]
+    num_keep = int(np.ceil(keep * n))
+    order = torch.sort(radius.to(torch.float32), stable=True).indices
+    out = torch.full_like(radius, -1)
+    out[order[:num_keep]] = radius[order[:num_keep]]
+    return out
+
+
+def realism_scores(real_features, gen_features, nhood_size=3, keep=0.5, row_batch_size=10000, leave_one_out=False):
+    """The realism score of every generated feature (Kynkaanniemi et al., NeurIPS 2019, section 5):
+    R(g) = max_r radius_k(r) / |g - r| over the real features whose k-NN radius (self-distance included, as for precision) is among the
+    ceil(keep N) smallest.  -> (score fp32 [M], item int32 [M]: the real feature attaining it, radius_kept fp16 [N]: -1 where pruned);
+    with `leave_one_out` also (real_score [N], real_item [N]): every real feature against the kept balls of the others, its own
+    excluded -- the baseline the generated scores are read against.  One process; `knn_manifold.realism` on either device."""
+    radius = realism_radii(real_features, nhood_size, keep, row_batch_size)
+    out = realism_sweep(gen_features, real_features, radius, row_batch_size) + (radius,)
+    if leave_one_out:
+        out = out + realism_sweep(real_features, real_features, radius, row_batch_size, own=True)
+    return out
+
+
+def realism_radii(real_features, nhood_size=3, keep=0.5, row_batch_size=10000):
+    """the kept balls of `realism_scores`: fp16 [N], the k-NN radius of every real feature, -1 where pruned"""
+    if not 0 < keep <= 1:
+        raise ValueError(f'realism_scores: keep = {keep} must lie in (0, 1]')
+    return pruned_radii(_radii_fused(real_features, nhood_size, row_batch_size, 1, 0), keep)
+
+
+def realism_sweep(probes, real_features, radius_kept, row_batch_size=10000, own=False):
+    """`knn_manifold.realism` of `probes` in row batches -> (score fp32 [P], item int32 [P]); `own`: probe i is real feature i, whose
+    own ball is left out"""
+    device = real_features.device
+    score, item = [], []
+    for lo in range(0, probes.shape[0], row_batch_size):
+        hi = min(lo + row_batch_size, probes.shape[0])
+        exclude = torch.arange(lo, hi, dtype=torch.int32, device=device) if own else None
+        s, i = knn_manifold.realism(probes[lo:hi], real_features, radius_kept, exclude)
+        score.append(s)
+        item.append(i)
+    if not score:
+        return torch.empty([0], dtype=torch.float32, device=device), torch.empty([0], dtype=torch.int32, device=device)
+    return torch.cat(score), torch.cat(item)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------

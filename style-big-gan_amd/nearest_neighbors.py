@@ -46,9 +46,9 @@ import os
 import numpy as np
 import torch
 
-from .tool_support import (add_device_option, add_sampling_options, add_snapshot_option, class_label, config_overrides, dataset_kwargs_for,  # noqa: F401
-                           detector_kwargs, device_of, generated_images, load_generator, num_range, open_dataset, require_file, save_png,
-                           snapshot_generator_state, tool_device)
+from .tool_support import (add_device_option, add_sampling_options, add_snapshot_option, checked_features, class_label, config_overrides,  # noqa: F401
+                           dataset_features, dataset_kwargs_for, detector_kwargs, device_of, generated_images, load_generator, num_range, open_dataset,
+                           require_file, save_png, snapshot_generator_state, tool_device, vgg16_feature_options)
 from .torch_utils.ops import knn_manifold, nn_u8, resample_u8, resident_set
 
 SPACES = ('pixel', 'vgg16')
@@ -126,44 +126,13 @@ def dist_summary(d2, F=1):
     return out
 
 
-def checked_features(features, what):
-    """float features [N, F] -> fp16 on their device, finite and of a width the kernel takes"""
-    features = features.to(torch.float16)
-    if features.ndim != 2 or features.shape[1] % 8 != 0:
-        raise ValueError(f'--space=vgg16: the detector returns features of shape {list(features.shape[1:])} for {what}; the search needs a vector per '
-                         'image whose width is a multiple of 8')
-    if not bool(torch.isfinite(features).all()):
-        raise ValueError(f'--space=vgg16: the features of {what} are not all finite in fp16')
-    return features.contiguous()
-
-
-def dataset_features(opts, dataset, dataset_name):
-    """the detector's feature of every item of `dataset`, in item order -> float32 tensor [len(dataset), F] on the host"""
-    from .metrics import metric_utils, scores
-    kw = metric_utils.detector_call_kwargs(opts, scores.VGG16, dict(return_features=True))
-    stats = metric_utils.compute_feature_stats_for_dataset(opts, scores.VGG16, kw, dataset_name=dataset_name, capture_all=True)
-    if opts.cache and stats.num_items != len(dataset):      # a stale cache file (its name does not key on the row count): not used
-        opts.cache = False
-        stats = metric_utils.compute_feature_stats_for_dataset(opts, scores.VGG16, kw, dataset_name=dataset_name, capture_all=True)
-    if stats.num_items != len(dataset):
-        raise ValueError(f'--space=vgg16: dataset_kwargs describe a data set of {stats.num_items} items, the data set searched holds {len(dataset)}')
-    return stats.get_all_torch()
-
-
 def _feature_space(G, dataset, label, seeds, num, k, truncation_psi, noise_mode, batch, outdir, device, max_gib, detector, dataset_kwargs, dataset_name,
                    cache_dir):
     """the --space=vgg16 half of `nearest_training_images`"""
     from .metrics import metric_utils, scores
     from .train_parts.dataloaders import ResidentDataloader
     C, H, W = dataset.image_shape
-    if isinstance(detector, str) and os.path.isdir(detector):
-        # a directory is resolved to the file here: the process-wide detector cache and the feature cache key on what they are given, and
-        # the bare name `vgg16.pt` would stand for whichever directory was loaded first
-        if not os.path.isfile(os.path.join(detector, scores.VGG16)):
-            raise ValueError(f'--detector={detector}: the directory does not hold {scores.VGG16}')
-        detector = os.path.join(detector, scores.VGG16)
-    opts = metric_utils.MetricOptions(dataset_kwargs=dataset_kwargs, device=device, cache_dir=cache_dir, **detector_kwargs(detector))
-    opts.cache = not callable(metric_utils.detector_source(opts, scores.VGG16))        # cache only when the detector is a file
+    opts = vgg16_feature_options(detector, dataset_kwargs, device, cache_dir)
     call_kw = metric_utils.detector_call_kwargs(opts, scores.VGG16, dict(return_features=True))
     detect = metric_utils._detector(opts, scores.VGG16)
     manifold = checked_features(dataset_features(opts, dataset, dataset_name).to(device), 'the data set')

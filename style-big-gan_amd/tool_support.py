@@ -1,7 +1,8 @@
-"""What the snapshot tools (generate, style_mixing, projector, calc_metrics, nearest_neighbors, avg_spectra, diversity) share, each piece once: a generator
-built from the run's config and a ``network-snapshot-*.pt`` of this build (written by ``BaseTrainer.save_snapshot``), the ``key=value`` config
-overrides ``starter`` takes, the options several tools declare alike, the device and the data set of a run, the class label, the seeded latents
-and the bytes of generated images.  What a tool validates and the options whose help differs per tool stay in the tool."""
+"""What the snapshot tools (generate, style_mixing, projector, calc_metrics, nearest_neighbors, avg_spectra, diversity, realism) share, each piece once: a
+generator built from the run's config and a ``network-snapshot-*.pt`` of this build (written by ``BaseTrainer.save_snapshot``), the ``key=value`` config
+overrides ``starter`` takes, the options several tools declare alike, the device and the data set of a run, the class label, the seeded latents,
+the bytes of generated images and the ``vgg16.pt`` features of a data set.  What a tool validates and the options whose help differs per tool stay
+in the tool."""
 import contextlib
 import os
 import re
@@ -129,6 +130,44 @@ def detector_kwargs(detector):
     if isinstance(detector, str) and os.path.isdir(detector):
         return dict(detector=None, detector_dir=detector)
     raise ValueError(f'--detector={detector}: no such TorchScript file or directory (detectors are not downloaded in this build)')
+
+
+def vgg16_feature_options(detector, dataset_kwargs, device, cache_dir=None):
+    """MetricOptions for the `vgg16.pt` features of a data set and of images (nearest_neighbors --space=vgg16, realism).  A directory is
+    resolved to the file here: the process-wide detector cache and the feature cache key on what they are given, and the bare name
+    `vgg16.pt` would stand for whichever directory was loaded first.  Features are cached only when the detector is a file."""
+    from .metrics import metric_utils, scores
+    if isinstance(detector, str) and os.path.isdir(detector):
+        if not os.path.isfile(os.path.join(detector, scores.VGG16)):
+            raise ValueError(f'--detector={detector}: the directory does not hold {scores.VGG16}')
+        detector = os.path.join(detector, scores.VGG16)
+    opts = metric_utils.MetricOptions(dataset_kwargs=dataset_kwargs, device=device, cache_dir=cache_dir, **detector_kwargs(detector))
+    opts.cache = not callable(metric_utils.detector_source(opts, scores.VGG16))
+    return opts
+
+
+def checked_features(features, what, option='--space=vgg16'):
+    """float features [N, F] -> fp16 on their device, finite and of a width the kernel takes"""
+    features = features.to(torch.float16)
+    if features.ndim != 2 or features.shape[1] % 8 != 0:
+        raise ValueError(f'{option}: the detector returns features of shape {list(features.shape[1:])} for {what}; the search needs a vector per '
+                         'image whose width is a multiple of 8')
+    if not bool(torch.isfinite(features).all()):
+        raise ValueError(f'{option}: the features of {what} are not all finite in fp16')
+    return features.contiguous()
+
+
+def dataset_features(opts, dataset, dataset_name, option='--space=vgg16'):
+    """the detector's feature of every item of `dataset`, in item order -> float32 tensor [len(dataset), F] on the host"""
+    from .metrics import metric_utils, scores
+    kw = metric_utils.detector_call_kwargs(opts, scores.VGG16, dict(return_features=True))
+    stats = metric_utils.compute_feature_stats_for_dataset(opts, scores.VGG16, kw, dataset_name=dataset_name, capture_all=True)
+    if opts.cache and stats.num_items != len(dataset):      # a stale cache file (its name does not key on the row count): not used
+        opts.cache = False
+        stats = metric_utils.compute_feature_stats_for_dataset(opts, scores.VGG16, kw, dataset_name=dataset_name, capture_all=True)
+    if stats.num_items != len(dataset):
+        raise ValueError(f'{option}: dataset_kwargs describe a data set of {stats.num_items} items, the data set searched holds {len(dataset)}')
+    return stats.get_all_torch()
 
 
 def class_label(G, class_idx, device):

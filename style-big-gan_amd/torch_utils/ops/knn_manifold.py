@@ -10,7 +10,8 @@ reference does not have.  One definition for both devices:
     d    = fp16(sqrt_f32(d2))                        selection and comparison happen on these fp16 values
 
 ``topk`` is the feature-space search of ``nearest_neighbors.py``: the k nearest manifold rows of every query with their indices, selected
-on the fp32 d2 itself.
+on the fp32 d2 itself.  ``realism`` is the per-probe realism score of the improved precision / recall paper (its section 5): the largest
+radius / d over the manifold's kept balls with the index that attains it, on the same fp16 d.
 
 Device tensors must be fp16 and run the kernels; a missing kernel or an unsupported input is an error, never a quiet torch fallback.
 CPU tensors run the same definition in torch (float64 sums rounded to fp32, then the steps above), so the metric's plumbing is testable
@@ -134,6 +135,68 @@ def probe(probes, manifold, radius):
     _lib.check(lib.sbg_knn_probe(probes.data_ptr(), manifold.data_ptr(), radius.data_ptr(), P, C, F, count.data_ptr(), nearest.data_ptr(), ws.data_ptr(),
                                  _lib.stream_ptr(probes.device)), "sbg_knn_probe")
     return count, nearest
+
+
+def realism(probes, manifold, radius, exclude=None):
+    """probes [P, F], manifold [C, F], radius [C] (negative: the point is pruned), exclude int32 [P] or None (a manifold index, or -1)
+    -> (score fp32 [P], index int32 [P]): the realism score of Kynkaanniemi et al. (NeurIPS 2019, section 5) on the module's fp16 d.
+
+        eligible(i, j) = radius[j] >= 0 and j != exclude[i]
+        q(i, j)        = +inf when d(i, j) == 0 (also at radius 0), else float(radius[j]) / float(d(i, j)), one fp32 division
+        score[i]       = max of q(i, j) over the eligible j; 0 when there is none
+        index[i]       = the lowest eligible j attaining it; -1 when there is none
+
+    A maximum with ties to the lower index depends on no order, so any cut of the probes into batches gives the same bits; and since q
+    is formed from the d that `in_manifold` compares, ``score >= 1`` is `in_manifold(probes, manifold, radius)` when nothing is excluded.
+    Device tensors must be fp16 (``exclude`` int32) and run the kernel; anything else raises.  CPU tensors run the definition in torch."""
+    what = "knn_manifold.realism"
+    _check(probes, manifold, 0)
+    P, F = probes.shape
+    C = manifold.shape[0]
+    if radius.shape != (C,) or radius.device != manifold.device:
+        raise RuntimeError(f"{what}: expects one radius per manifold point on its device, got {tuple(radius.shape)} on {radius.device}")
+    if exclude is not None:
+        if exclude.dtype != torch.int32:
+            raise RuntimeError(f"{what}: exclude must be int32, got {exclude.dtype}")
+        if exclude.shape != (P,) or exclude.device != probes.device:
+            raise RuntimeError(f"{what}: expects one excluded manifold index per probe on its device, got {tuple(exclude.shape)} on {exclude.device}")
+    if probes.device.type != "cuda":
+        n_manifold = manifold.to(torch.float64).square().sum(1).to(torch.float32)
+        r = radius.to(torch.float16).to(torch.float32)
+        cols = torch.arange(C)
+        score, index = [], []
+        for lo in range(0, P, _CPU_ROWS):
+            d = _cpu_distances(probes[lo:lo + _CPU_ROWS], manifold, n_manifold).to(torch.float32)
+            q = torch.where(d == 0, torch.full_like(d, float("inf")), (r[None, :] / d).abs())      # abs: a radius of -0 counts as +0
+            eligible = (r >= 0)[None, :].expand_as(q)
+            if exclude is not None:
+                eligible = eligible & (cols[None, :] != exclude[lo:lo + _CPU_ROWS, None])
+            q = torch.where(eligible, q, torch.full_like(q, -1.0))
+            best = q.max(dim=1).values
+            first = (q == best[:, None]).to(torch.uint8).argmax(dim=1)          # of equal maxima the first: the lowest index
+            none = best < 0
+            score.append(torch.where(none, torch.zeros_like(best), best))
+            index.append(torch.where(none, torch.full_like(first, -1), first).to(torch.int32))
+        if not score:
+            return torch.empty([0], dtype=torch.float32), torch.empty([0], dtype=torch.int32)
+        return torch.cat(score), torch.cat(index)
+    probes, manifold, radius = (_lib.require_dtype(t, torch.float16, what).contiguous() for t in (probes, manifold, radius))
+    score = torch.empty([P], dtype=torch.float32, device=probes.device)
+    index = torch.empty([P], dtype=torch.int32, device=probes.device)
+    if P == 0:
+        return score, index
+    if F % 8 != 0:
+        raise RuntimeError(f"{what}: the feature width {F} must be a multiple of 8 (16-byte pieces) for the device path")
+    if exclude is not None:
+        exclude = exclude.contiguous()
+    lib = _lib.load()
+    nbytes = lib.sbg_knn_realism_workspace(P, C)
+    if nbytes < 0:
+        raise RuntimeError(f"{what}: unsupported sizes P={P} C={C}")
+    ws = _lib.workspace(nbytes, probes.device, "sbg_knn_realism_workspace")
+    _lib.check(lib.sbg_knn_realism(probes.data_ptr(), manifold.data_ptr(), radius.data_ptr(), P, C, F, None if exclude is None else exclude.data_ptr(),
+                                   score.data_ptr(), index.data_ptr(), ws.data_ptr(), _lib.stream_ptr(probes.device)), "sbg_knn_realism")
+    return score, index
 
 
 def topk(queries, manifold, k, exclude=None):
