@@ -81,8 +81,9 @@ __global__ void __launch_bounds__(256) grid_sample_bwd_kernel(GridArgs p)
         float ix, iy;
         sample_pos(p, n, oy, ox, ix, iy);
         const float fx = floorf(ix), fy = floorf(iy);
-        const float tx = ix - fx, ty = iy - fy;
         const bool sane = (ix > -2.0f) && (ix < (float)p.IW + 1.0f) && (iy > -2.0f) && (iy < (float)p.IH + 1.0f);
+        // (inf - inf = NaN would survive the multiplication by the zero neighbour differences of dgrid below)
+        const float tx = sane ? ix - fx : 0.0f, ty = sane ? iy - fy : 0.0f;
         const int x0 = sane ? (int)fx : -4, y0 = sane ? (int)fy : -4;
         const bool vx0 = x0 >= 0 && x0 < p.IW, vx1 = x0 + 1 >= 0 && x0 + 1 < p.IW;
         const bool vy0 = y0 >= 0 && y0 < p.IH, vy1 = y0 + 1 >= 0 && y0 + 1 < p.IH;
