@@ -238,7 +238,7 @@ int run(bool adj, const float* x, const int32_t* table, float* y, float* workspa
     if (N == 0) return SBG_OK;
     SBG_CHECK(x && table && y, "diffaug: null pointer");
     SBG_CHECK(x != y, "diffaug: in-place operation is not supported");
-    SBG_CHECK(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(table)) & 3) == 0, "diffaug: pointers must be 4-byte aligned");
+    SBG_CHECK(sbg_aligned(x, 4) && sbg_aligned(y, 4) && sbg_aligned(table, 4), "diffaug: pointers must be 4-byte aligned");
     const int len = (int)len64;
     const bool vec = W % 4 == 0 && sbg_aligned16(x) && sbg_aligned16(y);
     const int access = vec ? 1 : 2;
@@ -260,7 +260,7 @@ int run(bool adj, const float* x, const int32_t* table, float* y, float* workspa
         return SBG_OK;
     }
 
-    SBG_CHECK(workspace != nullptr && (reinterpret_cast<uintptr_t>(workspace) & 3) == 0, "diffaug: the workspace must be a 4-byte aligned device pointer");
+    SBG_CHECK(workspace != nullptr && sbg_aligned(workspace, 4), "diffaug: the workspace must be a 4-byte aligned device pointer");
     const int chunks = (len + kChunk - 1) / kChunk;
     const int groups = H * W / (vec ? 4 : 1);
     const int bps = (groups + NT - 1) / NT;

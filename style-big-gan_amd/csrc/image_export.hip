@@ -139,7 +139,7 @@ extern "C" int sbg_img_quantize_tile(const float* img, uint8_t* canvas, int N, i
     SBG_CHECK(rule == SBG_QUANT_GRID || rule == SBG_QUANT_CLAMP, "img_quantize_tile: unknown rule %d", rule);
     hipStream_t s = (hipStream_t)stream;
     // four pixels per work-item: whole groups per row, 16-byte aligned loads, 4-byte aligned stores (4 * C bytes per group from an aligned base)
-    const bool rows16 = W % 4 == 0 && sbg_aligned16(img) && sn % 4 == 0 && sh % 4 == 0 && (reinterpret_cast<uintptr_t>(canvas) & 3) == 0;
+    const bool rows16 = W % 4 == 0 && sbg_aligned16(img) && sn % 4 == 0 && sh % 4 == 0 && sbg_aligned(canvas, 4);
     int mode = kPixel;
     if (rows16 && sw == 1 && (C == 1 || sc % 4 == 0)) mode = kPlanar4;
     else if (rows16 && C == 3 && sc == 1 && sw == 3) mode = kMinor4;

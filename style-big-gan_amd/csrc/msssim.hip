@@ -17,13 +17,14 @@
 //  adds the lanes; the workgroup writes one pair of tile partials.  A half wave reads 32 consecutive float64 of one row (all 64 banks
 //  once) at every step of the column walk, and 32 consecutive fp32 in the row pass: no pitch padding is needed.  A map smaller than the
 //  tile takes the same path.  LDS: 2 x 26 x 42 x 4 + 5 x 26 x 32 x 8 + 32 = 42048 bytes.
-// merge: one workgroup per (image-channel, term): lane t adds the tile partials t, t + 256, ... (tiles in row-major order) from 0, block_sum
-//  adds the lanes, the sum is divided by n n.  No atomics; the order depends on S alone.
+// merge: the shared merge kernel (merge.h) adds the tile partials of one (image-channel, term), tiles in row-major order, and divides the
+//  sum by n n.  No atomics; the order depends on S alone.
 // down: y[i, j] = ((a + b) + (c + d)) * 0.25f in fp32, a b the upper left and right pixels of the 2 x 2 block, c d the lower ones.
 // Launch-log key: kind SBG_K_MSSSIM, dims = {0 level | 1 down | 2 merge, BC clipped to INT32_MAX, S}.
 #pragma clang fp contract(off)
 #include "sbg_common.h"
 #include "reduce.h"
+#include "merge.h"
 
 namespace {
 
@@ -34,9 +35,6 @@ constexpr int TW = 32, TH = 16;                         // map tile of one workg
 constexpr int IW = TW + kHalo, IH = TH + kHalo;         // its source pixels
 constexpr int kMaxSide = 16384;
 constexpr int64_t kMaxGrid = (int64_t)1 << 24;          // workgroups of one launch: 2^32 work-items
-
-__device__ __forceinline__ float pixel(unsigned char v) { return (float)v; }
-__device__ __forceinline__ float pixel(float v) { return v; }
 
 template <class T>
 __global__ __launch_bounds__(NT) void msssim_level_kernel(const T* __restrict__ x, const T* __restrict__ y, const double* __restrict__ g,
@@ -59,8 +57,8 @@ __global__ __launch_bounds__(NT) void msssim_level_kernel(const T* __restrict__ 
         const int r = idx / IW, c = idx - r * IW;
         const int iy = oy0 + r, ix = ox0 + c;
         const bool ok = iy < S && ix < S;
-        xs[idx] = ok ? pixel(xp[(int64_t)iy * S + ix]) : 0.f;
-        ys[idx] = ok ? pixel(yp[(int64_t)iy * S + ix]) : 0.f;
+        xs[idx] = ok ? sbg_pixel(xp[(int64_t)iy * S + ix]) : 0.f;
+        ys[idx] = ok ? sbg_pixel(yp[(int64_t)iy * S + ix]) : 0.f;
     }
     __syncthreads();
 
@@ -111,17 +109,6 @@ __global__ __launch_bounds__(NT) void msssim_level_kernel(const T* __restrict__ 
     }
 }
 
-// one workgroup per output value: out[v] = (the sum of partial[v * tiles .. + tiles)) / count
-__global__ __launch_bounds__(NT) void msssim_merge_kernel(const double* __restrict__ partial, double* __restrict__ out, int tiles, double count)
-{
-    __shared__ double red[NT / 64];
-    const double* p = partial + (int64_t)blockIdx.x * tiles;
-    double s = 0.0;
-    for (int i = threadIdx.x; i < tiles; i += NT) s = s + p[i];
-    s = block_sum<NT>(s, red);
-    if (threadIdx.x == 0) out[blockIdx.x] = s / count;
-}
-
 template <class T>
 __global__ __launch_bounds__(NT) void msssim_down_kernel(const T* __restrict__ x, float* __restrict__ y, int64_t total, int S, int logH)
 {
@@ -130,14 +117,11 @@ __global__ __launch_bounds__(NT) void msssim_down_kernel(const T* __restrict__ x
         const int ox = (int)(i & (H - 1)), oy = (int)((i >> logH) & (H - 1));
         const int64_t plane = i >> (2 * logH);
         const T* p = x + (plane * S + 2 * oy) * S + 2 * ox;
-        const float a = pixel(p[0]), b = pixel(p[1]), c = pixel(p[S]), d = pixel(p[S + 1]);
+        const float a = sbg_pixel(p[0]), b = sbg_pixel(p[1]), c = sbg_pixel(p[S]), d = sbg_pixel(p[S + 1]);
         y[i] = ((a + b) + (c + d)) * 0.25f;
     }
 }
 
-inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-inline int clip31(int64_t v) { return (int)(v > INT32_MAX ? INT32_MAX : v); }
-inline bool pow2_side(int S, int lo) { return S >= lo && S <= kMaxSide && (S & (S - 1)) == 0; }
 inline int tiles_of(int S, int* tiles_x)
 {
     const int n = S - kHalo, tx = (n + TW - 1) / TW, ty = (n + TH - 1) / TH;
@@ -149,7 +133,7 @@ inline int tiles_of(int S, int* tiles_x)
 
 extern "C" int64_t sbg_msssim_workspace(int64_t BC, int S)
 {
-    if (BC < 1 || !pow2_side(S, 16)) return -1;
+    if (BC < 1 || !sbg_pow2_in(S, 16, kMaxSide)) return -1;
     const int64_t tiles = tiles_of(S, nullptr);
     if (BC > kMaxGrid / tiles) return -1;
     return 8 * 2 * BC * tiles;
@@ -160,8 +144,8 @@ extern "C" int sbg_msssim_level(const void* x, const void* y, int is_u8, const d
 {
     SBG_CHECK(sbg_msssim_workspace(BC, S) >= 0, "msssim_level: bad sizes BC=%lld S=%d (S a power of two in [16, %d], BC x tiles <= 2^24)",
               (long long)BC, S, kMaxSide);
-    SBG_CHECK(x && y && window && out && workspace && aligned(x, is_u8 ? 1 : 4) && aligned(y, is_u8 ? 1 : 4) && aligned(window, 8) && aligned(out, 8)
-              && aligned(workspace, 8), "msssim_level: null or misaligned pointer");
+    SBG_CHECK(x && y && window && out && workspace && sbg_aligned(x, is_u8 ? 1 : 4) && sbg_aligned(y, is_u8 ? 1 : 4) && sbg_aligned(window, 8) && sbg_aligned(out, 8)
+              && sbg_aligned(workspace, 8), "msssim_level: null or misaligned pointer");
     SBG_CHECK(C1 > 0.0 && C2 > 0.0, "msssim_level: the constants C1=%g and C2=%g must be positive", C1, C2);
     int tiles_x = 0;
     const int tiles = tiles_of(S, &tiles_x), n = S - kHalo;
@@ -170,7 +154,7 @@ extern "C" int sbg_msssim_level(const void* x, const void* y, int is_u8, const d
     hipStream_t st = (hipStream_t)stream;
     const double px = (double)BC * S * S;
     {
-        SbgProfScope prof(st, SBG_K_MSSSIM, 2.0 * 5 * kTaps * 2 * px, (is_u8 ? 2.0 : 8.0) * px + 16.0 * (double)BC * tiles, {kLevel, clip31(BC), S});
+        SbgProfScope prof(st, SBG_K_MSSSIM, 2.0 * 5 * kTaps * 2 * px, (is_u8 ? 2.0 : 8.0) * px + 16.0 * (double)BC * tiles, {kLevel, sbg_clip31(BC), S});
         if (is_u8)
             SBG_LAUNCH(msssim_level_kernel<unsigned char>, dim3((unsigned)(BC * tiles)), dim3(NT), 0, st, (const unsigned char*)x, (const unsigned char*)y,
                        window, (double*)workspace, S, n, tiles_x, tiles, C1, C2);
@@ -179,21 +163,19 @@ extern "C" int sbg_msssim_level(const void* x, const void* y, int is_u8, const d
                        (double*)workspace, S, n, tiles_x, tiles, C1, C2);
         SBG_HIP_LAUNCH_CHECK();
     }
-    SbgProfScope prof(st, SBG_K_MSSSIM, 0.0, 16.0 * (double)BC * tiles + 16.0 * (double)BC, {kMerge, clip31(BC), S});
-    SBG_LAUNCH(msssim_merge_kernel, dim3((unsigned)(2 * BC)), dim3(NT), 0, st, (const double*)workspace, out, tiles, (double)n * (double)n);
-    SBG_HIP_LAUNCH_CHECK();
-    return SBG_OK;
+    SbgProfScope prof(st, SBG_K_MSSSIM, 0.0, 16.0 * (double)BC * tiles + 16.0 * (double)BC, {kMerge, sbg_clip31(BC), S});
+    return merge_partials<double>((const double*)workspace, out, 2 * BC, tiles, (double)n * (double)n, st);
 }
 
 extern "C" int sbg_msssim_down(const void* x, int is_u8, float* y, int64_t BC, int S, sbg_stream_t stream)
 {
     SBG_CHECK(BC >= 0 && BC <= ((int64_t)1 << 40), "msssim_down: bad size BC=%lld", (long long)BC);
-    SBG_CHECK(pow2_side(S, 2), "msssim_down: side %d, a power of two in [2, %d] is supported", S, kMaxSide);
+    SBG_CHECK(sbg_pow2_in(S, 2, kMaxSide), "msssim_down: side %d, a power of two in [2, %d] is supported", S, kMaxSide);
     if (BC == 0) return SBG_OK;
-    SBG_CHECK(x && y && (const void*)x != (const void*)y && aligned(x, is_u8 ? 1 : 4) && aligned(y, 4), "msssim_down: x and y must be distinct aligned device pointers");
+    SBG_CHECK(x && y && (const void*)x != (const void*)y && sbg_aligned(x, is_u8 ? 1 : 4) && sbg_aligned(y, 4), "msssim_down: x and y must be distinct aligned device pointers");
     const int64_t total = BC * (S / 2) * (S / 2);
     hipStream_t st = (hipStream_t)stream;
-    SbgProfScope prof(st, SBG_K_MSSSIM, 0.0, (is_u8 ? 4.0 : 16.0) * total + 4.0 * total, {kDown, clip31(BC), S});
+    SbgProfScope prof(st, SBG_K_MSSSIM, 0.0, (is_u8 ? 4.0 : 16.0) * total + 4.0 * total, {kDown, sbg_clip31(BC), S});
     int logH = 0;
     while ((2 << logH) < S) logH++;
     if (is_u8)

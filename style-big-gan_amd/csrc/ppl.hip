@@ -173,7 +173,5 @@ extern "C" int sbg_ppl_dist(const float* feats, float* dist, void* workspace, in
     SbgProfScope prof(s, SBG_K_PPL, 3.0 * B * (double)F, 4.0 * (2.0 * B * (double)F + 2.0 * B * nchunk + B), {kPplDist, B, (int)(F >> 10), (int)(F & 1023), vec4});
     SBG_LAUNCH(sqdist_partial_kernel<true>, dim3((unsigned)nchunk, (unsigned)B), dim3(kDistThreads), 0, s, feats, feats + (int64_t)B * F, (float*)workspace,
                F, (int)nchunk, vec4);
-    SBG_LAUNCH(sqdist_final_kernel, dim3((unsigned)B), dim3(kDistThreads), 0, s, (const float*)workspace, dist, (int)nchunk, eps2);
-    SBG_HIP_LAUNCH_CHECK();
-    return SBG_OK;
+    return merge_partials<float>((const float*)workspace, dist, B, (int)nchunk, eps2, s);
 }

@@ -363,7 +363,7 @@ extern "C" int sbg_proj_noise_reg(const float* const* bufs, const int* res, int 
 {
     BufTable T;
     if (!fill_table(T, res, nbuf, "proj_noise_reg")) return SBG_ERR_INVALID;
-    SBG_CHECK(bufs && means && reg && workspace && sbg_aligned16(workspace) && ((uintptr_t)means & 7) == 0, "proj_noise_reg: null or misaligned pointer");
+    SBG_CHECK(bufs && means && reg && workspace && sbg_aligned16(workspace) && sbg_aligned(means, 8), "proj_noise_reg: null or misaligned pointer");
     for (int b = 0; b < nbuf; b++) {
         SBG_CHECK(bufs[b] && sbg_aligned16(bufs[b]), "proj_noise_reg: buffer %d is null or not 16-byte aligned", b);
         T.buf[b] = const_cast<float*>(bufs[b]);
@@ -410,7 +410,7 @@ extern "C" int sbg_proj_noise_reg_bwd(const float* const* bufs, float* const* gr
 {
     BufTable T;
     if (!fill_table(T, res, nbuf, "proj_noise_reg_bwd")) return SBG_ERR_INVALID;
-    SBG_CHECK(bufs && grads && means && g && workspace && sbg_aligned16(workspace) && ((uintptr_t)means & 7) == 0,
+    SBG_CHECK(bufs && grads && means && g && workspace && sbg_aligned16(workspace) && sbg_aligned(means, 8),
               "proj_noise_reg_bwd: null or misaligned pointer");
     int blocks = 0;
     int64_t elems = 0;
@@ -488,12 +488,8 @@ extern "C" int sbg_proj_sqdist(const float* t, const float* s_, float* dist, voi
         SbgProfScope prof(s, SBG_K_PROJECTOR, 3.0 * F, 8.0 * F + 4.0 * nchunk, {kProjSqdist, 0, (int)(F >> 10), (int)(F & 1023), vec4});
         SBG_LAUNCH(sqdist_partial_kernel<false>, dim3((unsigned)nchunk, 1), dim3(kDistThreads), 0, s, t, s_, (float*)workspace, F, (int)nchunk, vec4);
     }
-    {
-        SbgProfScope prof(s, SBG_K_PROJECTOR, 1.0 * nchunk, 4.0 * nchunk + 4.0, {kProjSqdist, 1, (int)(F >> 10), (int)(F & 1023), vec4});
-        SBG_LAUNCH(sqdist_final_kernel, dim3(1), dim3(kDistThreads), 0, s, (const float*)workspace, dist, (int)nchunk, 1.0f);
-    }
-    SBG_HIP_LAUNCH_CHECK();
-    return SBG_OK;
+    SbgProfScope prof(s, SBG_K_PROJECTOR, 1.0 * nchunk, 4.0 * nchunk + 4.0, {kProjSqdist, 1, (int)(F >> 10), (int)(F & 1023), vec4});
+    return merge_partials<float>((const float*)workspace, dist, 1, (int)nchunk, 1.0f, s);
 }
 
 extern "C" int sbg_proj_sqdist_bwd(const float* t, const float* s_, const float* g, float* ds, int64_t F, sbg_stream_t stream)

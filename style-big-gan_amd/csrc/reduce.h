@@ -1,5 +1,7 @@
 // reduce.h -- the one definition of the fixed-order sums behind the tool kernels' reproducibility claims (ppl.hip, projector.hip,
-// knn_manifold.hip, mbstd.hip, sqdist.h, grad_finish.hip).  The ORDER IS PART OF THE CONTRACT: the bit-for-bit tests and DESIGN.md rest on it.
+// knn_manifold.hip, diffaug.hip, mbstd.hip, grad_finish.hip, swd.hip, msssim.hip, sqdist.h, merge.h).  The ORDER IS PART OF THE CONTRACT:
+// the bit-for-bit tests and DESIGN.md rest on it.  merge.h adds the partials of a split sum with it; torch_utils/ops/_exact_common.py
+// states the same order in numpy.
 //   wave_sum:   the 64-lane xor butterfly, offsets 32, 16, ... 1; every lane ends with the same value.
 //   block_sum:  wave_sum in each wave, then the NT / 64 per-wave values added LEFT TO RIGHT IN WAVE ORDER,
 //               ((red[0] + red[1]) + red[2]) + ...; every work-item ends with the same value.
@@ -30,7 +32,7 @@ static __device__ __forceinline__ float block_sum(float v, float* red)
     return s;
 }
 
-// The float64 forms (grad_finish.hip): the same butterfly and the same wave order; `red` holds NT / 64 doubles.
+// The float64 forms (grad_finish.hip, swd.hip, msssim.hip, merge.h): the same butterfly and the same wave order; `red` holds NT / 64 doubles.
 static __device__ __forceinline__ double wave_sum(double v)
 {
 #pragma unroll

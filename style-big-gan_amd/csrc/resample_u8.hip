@@ -184,10 +184,10 @@ extern "C" int sbg_u8_resample_v(const uint8_t* src, int64_t src_img_stride, int
     SBG_CHECK(row_bytes <= (1 << 30), "u8_resample_v: rows too long");
     const int64_t padded = ((int64_t)row_bytes + 3) / 4 * 4;
     SBG_CHECK(src_pitch >= row_bytes && src_img_stride >= 0, "u8_resample_v: the source pitch is shorter than a row, or a negative image stride");
-    SBG_CHECK(mult4(reinterpret_cast<intptr_t>(dst)) && mult4(dst_pitch) && mult4(dst_img_stride) && dst_pitch >= padded,
+    SBG_CHECK(sbg_aligned(dst, 4) && mult4(dst_pitch) && mult4(dst_img_stride) && dst_pitch >= padded,
               "u8_resample_v: dst, dst_pitch and dst_img_stride must be multiples of 4 and dst_pitch >= %lld", (long long)padded);
     SBG_CHECK(N == 1 || dst_img_stride >= (int64_t)out_h * dst_pitch, "u8_resample_v: bad image stride");
-    const bool dword = mult4(reinterpret_cast<intptr_t>(src)) && mult4(src_pitch) && mult4(src_img_stride) && src_pitch >= padded;
+    const bool dword = sbg_aligned(src, 4) && mult4(src_pitch) && mult4(src_img_stride) && src_pitch >= padded;
     const int ncols = (int)((padded / 4 + 63) / 64), ngroups = (out_h + 3) / 4;
     const int64_t blocks = (int64_t)ncols * ngroups * N;
     SBG_CHECK(blocks <= 0x7fffffff, "u8_resample_v: too many workgroups");

@@ -68,12 +68,11 @@ __global__ __launch_bounds__(kBlock) void gather_images_kernel(const uint8_t* __
     }
 }
 
-inline bool aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 // the one place that decides the path
 inline int gather_path(const uint8_t* store, int W, const void* out, int out_f32)
 {
-    return (W % 4 == 0 && aligned_to(store, 4) && aligned_to(out, out_f32 ? 16 : 4)) ? kPathDword : kPathByte;
+    return (W % 4 == 0 && sbg_aligned(store, 4) && sbg_aligned(out, out_f32 ? 16 : 4)) ? kPathDword : kPathByte;
 }
 
 } // namespace
@@ -88,7 +87,7 @@ extern "C" int sbg_u8_gather_images(const uint8_t* store, int64_t S, int C, int 
     const int64_t image_bytes = (int64_t)C * H * W;
     SBG_CHECK(image_bytes <= 0x7fffffff - kBlock, "u8_gather_images: an image of %lld values is too large", (long long)image_bytes);   // chunks * 256 stays an int
     SBG_CHECK(S <= INT64_MAX / image_bytes, "u8_gather_images: the store's size overflows");
-    SBG_CHECK(aligned_to(slot, 4) && (!out_f32 || (aligned_to(out, 4) && aligned_to(lut, 4))), "u8_gather_images: slot, lut and an fp32 out must be 4-byte aligned");
+    SBG_CHECK(sbg_aligned(slot, 4) && (!out_f32 || (sbg_aligned(out, 4) && sbg_aligned(lut, 4))), "u8_gather_images: slot, lut and an fp32 out must be 4-byte aligned");
     const int path = gather_path(store, W, out, out_f32);
     const bool dword = path == kPathDword;
     const int wq = dword ? W / 4 : W;

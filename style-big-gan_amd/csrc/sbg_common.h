@@ -119,6 +119,15 @@ template <> struct Vec8<f16_s> {
 static inline int sbg_dtype_size(int dtype) { return dtype == SBG_F32 ? 4 : 2; }
 static inline bool sbg_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// Host checks of the tool entry points.  `bytes` is a power of two; sbg_clip31 fits a 64-bit size into a launch-log dim; lo >= 1.
+static inline bool sbg_aligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
+static inline int sbg_clip31(int64_t v) { return (int)(v > INT32_MAX ? INT32_MAX : v); }
+static inline bool sbg_pow2_in(int v, int lo, int hi) { return v >= lo && v <= hi && (v & (v - 1)) == 0; }
+
+// An image sample as fp32: the tools take uint8 byte values or the same values as fp32.
+static __device__ __forceinline__ float sbg_pixel(unsigned char v) { return (float)v; }
+static __device__ __forceinline__ float sbg_pixel(float v) { return v; }
+
 // Grid size for streaming kernels: enough workgroups to fill 256 CUs x 8, grid-stride the rest.
 static inline unsigned sbg_stream_grid(int64_t work_items, int block)
 {

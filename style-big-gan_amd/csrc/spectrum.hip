@@ -36,8 +36,6 @@ constexpr int kMaxCol = 4;              // column samples per lane: 1024 / 256
 
 __device__ __forceinline__ int sw(int i) { return i ^ (-((i >> 5) & 1) & 31); }
 __device__ __forceinline__ int bitrev(int v, int bits) { return (int)(__brev((unsigned)v) >> (32 - bits)); }
-__device__ __forceinline__ float pixel(unsigned char v) { return (float)v; }
-__device__ __forceinline__ float pixel(float v) { return v; }
 
 // the stages h0, 2 h0, .., S/2 of `lines` lines of S complex values at `pitch`, all work-items of the workgroup; ends behind a barrier
 __device__ __forceinline__ void fft_stages(float2* buf, const float2* __restrict__ tw, int S, int logS, int h0, int lines, int pitch, int tid, int nt)
@@ -88,7 +86,7 @@ __global__ __launch_bounds__(NT) void spectrum_rows_kernel(const T* __restrict__
         for (int idx = tid; idx < G * R; idx += NT) {       // line gl, position block qx: sample n = bitrev(qx) of row bitrev(q0 + p G + gl)
             const int gl = idx >> logR, qx = idx & (R - 1);
             const int n = bitrev(qx, logR), y = bitrev(q0 + p * G + gl, logR);
-            const float v = fmaf(pixel(img[(int64_t)y * R + n]), s, t);
+            const float v = fmaf(sbg_pixel(img[(int64_t)y * R + n]), s, t);
             const float2 a = make_float2(v * window[n], 0.f);
             for (int r = 0; r < P; r++) buf[gl * pitch + sw((qx << logP) + r)] = a;
         }
@@ -157,7 +155,6 @@ __global__ __launch_bounds__(NT) void spectrum_cols_kernel(const float2* __restr
     for (int i = 0; i < kMaxOwn; i++) { const int ky = tid + i * nt; if (ky < S) arow[ky] = own[i]; }
 }
 
-inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 inline int log2i(int v) { int l = 0; while ((1 << l) < v) l++; return l; }
 inline bool sizes_ok(int R, int S)
 {
@@ -181,7 +178,7 @@ extern "C" int sbg_spectrum_rows(const void* images, int is_u8, const float* win
 {
     SBG_CHECK(sbg_spectrum_workspace(BC, R, S) >= 0, "spectrum_rows: bad sizes BC=%lld R=%d S=%d (R a power of two in [16, 1024], S = R, 2 R or 4 R)",
               (long long)BC, R, S);
-    SBG_CHECK(images && window && stages && workspace && aligned(images, is_u8 ? 1 : 4) && aligned(window, 4) && aligned(stages, 8) && aligned(workspace, 8),
+    SBG_CHECK(images && window && stages && workspace && sbg_aligned(images, is_u8 ? 1 : 4) && sbg_aligned(window, 4) && sbg_aligned(stages, 8) && sbg_aligned(workspace, 8),
               "spectrum_rows: null or misaligned pointer");
     const RowPlan p = row_plan(S);
     const size_t lds = row_lds(S);
@@ -190,7 +187,7 @@ extern "C" int sbg_spectrum_rows(const void* images, int is_u8, const float* win
     hipStream_t st = (hipStream_t)stream;
     const double px = (double)BC * R * R;
     SbgProfScope prof(st, SBG_K_SPECTRUM, 5.0 * px * S / R * log2i(S), (is_u8 ? 1.0 : 4.0) * px + 8.0 * (double)BC * (S / 2 + 1) * R,
-                      {kRows, (int)(BC > INT32_MAX ? INT32_MAX : BC), R, S});
+                      {kRows, sbg_clip31(BC), R, S});
     if (is_u8)
         SBG_LAUNCH(spectrum_rows_kernel<unsigned char>, dim3((unsigned)grid), dim3(NT), lds, st, (const unsigned char*)images, window, (const float2*)stages,
                    (float2*)workspace, s, t, R, log2i(R), S, log2i(S), p.G, p.passes, p.pad);
@@ -205,7 +202,7 @@ extern "C" int sbg_spectrum_cols(const void* workspace, const float* window, con
 {
     SBG_CHECK(sbg_spectrum_workspace(BC, R, S) >= 0, "spectrum_cols: bad sizes BC=%lld R=%d S=%d (R a power of two in [16, 1024], S = R, 2 R or 4 R)",
               (long long)BC, R, S);
-    SBG_CHECK(workspace && window && stages && acc && aligned(workspace, 8) && aligned(window, 4) && aligned(stages, 8) && aligned(acc, 8),
+    SBG_CHECK(workspace && window && stages && acc && sbg_aligned(workspace, 8) && sbg_aligned(window, 4) && sbg_aligned(stages, 8) && sbg_aligned(acc, 8),
               "spectrum_cols: null or misaligned pointer");
     static_assert(kMaxOwn * NT >= 4096 && kMaxCol * NT >= 1024, "a lane's registers hold the largest line");
     const int nt = cols_nt(S);
@@ -213,7 +210,7 @@ extern "C" int sbg_spectrum_cols(const void* workspace, const float* window, con
     hipStream_t st = (hipStream_t)stream;
     const double lines = (double)BC * (S / 2 + 1);
     SbgProfScope prof(st, SBG_K_SPECTRUM, 5.0 * lines * S * log2i(S), 8.0 * lines * R + 16.0 * (S / 2 + 1) * S,
-                      {kCols, (int)(BC > INT32_MAX ? INT32_MAX : BC), R, S});
+                      {kCols, sbg_clip31(BC), R, S});
     SBG_LAUNCH(spectrum_cols_kernel, dim3((unsigned)(S / 2 + 1)), dim3(nt), (size_t)8 * S, st, (const float2*)workspace, window, (const float2*)stages, acc,
                (int)BC, R, log2i(R), S, log2i(S));
     SBG_HIP_LAUNCH_CHECK();

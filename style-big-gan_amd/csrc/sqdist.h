@@ -1,12 +1,13 @@
 // sqdist.h -- the LPIPS squared distance dist[r] = (sum_f (a[r, f] - b[r, f])^2) / div for B rows of F features, shared by
-// ppl.hip (B rows, div = eps^2) and projector.hip (one row, div = 1: x / 1.0f is x).  Two launches, no float atomics:
+// ppl.hip (B rows, div = eps^2) and projector.hip (one row, div = 1).  Two launches, no float atomics:
 //   partial:  grid (nchunk, B); workgroup (chunk, r) sums its kDistChunk features of row r -> part[r, chunk]
-//   final:    grid (B); workgroup r adds the nchunk partials of row r and divides once
+//   final:    the shared merge kernel (merge.h) adds the nchunk partials of row r and divides once
 // Every work-item's share is summed in index order, then block_sum (reduce.h): the same bits on every run.  Each square is rounded
 // before it is added.  The callers own the launch-log scopes; nothing here logs.
 #pragma once
 #include "sbg_common.h"
 #include "reduce.h"
+#include "merge.h"
 
 namespace {
 
@@ -50,16 +51,6 @@ __global__ __launch_bounds__(kDistThreads) void sqdist_partial_kernel(const floa
     }
     const float tot = block_sum<kDistThreads>(s, red);
     if (threadIdx.x == 0) part[(int64_t)r * nchunk + chunk] = tot;
-}
-
-__global__ __launch_bounds__(kDistThreads) void sqdist_final_kernel(const float* __restrict__ part, float* __restrict__ dist, int nchunk, float div)
-{
-    __shared__ float red[kDistThreads / 64];
-    const int r = blockIdx.x;
-    float s = 0.f;
-    for (int k = threadIdx.x; k < nchunk; k += kDistThreads) s += part[(int64_t)r * nchunk + k];
-    const float tot = block_sum<kDistThreads>(s, red);
-    if (threadIdx.x == 0) dist[r] = tot / div;
 }
 
 } // namespace

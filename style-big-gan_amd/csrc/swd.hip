@@ -15,8 +15,8 @@
 // Sums (moments, l1): float64, fixed order.  The data of one output value is cut into chunks whose length depends on the shape alone
 // (moments: 1024 descriptor rows of one channel = 50176 values; l1: 16384 elements of one direction).  In a chunk, lane t of the 256 adds the
 // elements t, t + 256, ... in ascending order, block_sum (reduce.h) adds the lanes; one workgroup per chunk writes one float64 partial.
-// The merge kernel (one workgroup per output value) lets lane t add the partials t, t + 256, ... in ascending order, then block_sum.  No
-// atomics, no dependence on the launch geometry: two runs give the same bits.
+// The partials of one output value are added by the shared merge kernel (merge.h, div = 1).  No atomics, no dependence on the launch
+// geometry: two runs give the same bits.
 //   moments   out[c] = {sum, sum of squares} of channel c over all M * 49 values, each value widened to float64 before squaring
 //   l1        out[d] = sum_m |(double)a[d, m] - (double)b[d, m]|
 // project.  p[d, m] = the fp32 chain over k = 0..K-1 from 0:  acc = fmaf(fmaf(x[m, k], s[c(k)], t[c(k)]), dir[k, d], acc),  c(k) = k / 49,
@@ -29,6 +29,7 @@
 // 3 moments (M clipped, C, chunks) / 4 project (M clipped, K, D) / 5 l1 (D, M clipped, chunks) / 6 merge (values, chunks).
 #include "sbg_common.h"
 #include "reduce.h"
+#include "merge.h"
 
 namespace {
 
@@ -144,17 +145,6 @@ __global__ __launch_bounds__(NT) void swd_l1_kernel(const float* __restrict__ a,
     if (threadIdx.x == 0) partial[(int64_t)d * chunks + chunk] = s;
 }
 
-// one workgroup per output value: out[v] = the sum of partial[v * chunks .. + chunks)
-__global__ __launch_bounds__(NT) void swd_merge_kernel(const double* __restrict__ partial, double* __restrict__ out, int chunks)
-{
-    __shared__ double red[NT / 64];
-    const double* p = partial + (int64_t)blockIdx.x * chunks;
-    double s = 0.0;
-    for (int i = threadIdx.x; i < chunks; i += NT) s += p[i];
-    s = block_sum<NT>(s, red);
-    if (threadIdx.x == 0) out[blockIdx.x] = s;
-}
-
 constexpr int PM = 128, PD = 128, KC = 32;              // project: descriptor rows, directions and k per staged chunk
 constexpr int PLD = PM + 1;                             // LDS row pitch (floats)
 
@@ -209,16 +199,10 @@ __global__ __launch_bounds__(NT) void swd_project_kernel(const float* __restrict
         }
 }
 
-inline int clip31(int64_t v) { return (int)(v > INT32_MAX ? INT32_MAX : v); }
-inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-inline bool pow2_side(int S) { return S >= 2 && (S & (S - 1)) == 0; }
-
 int merge(const double* partial, double* out, int values, int chunks, hipStream_t s)
 {
     SbgProfScope prof(s, SBG_K_SWD, 0.0, 8.0 * values * (double)chunks + 8.0 * values, {kMerge, values, chunks});
-    SBG_LAUNCH(swd_merge_kernel, dim3((unsigned)values), dim3(NT), 0, s, partial, out, chunks);
-    SBG_HIP_LAUNCH_CHECK();
-    return SBG_OK;
+    return merge_partials<double>(partial, out, values, chunks, 1.0, s);
 }
 
 } // namespace
@@ -226,9 +210,9 @@ int merge(const double* partial, double* out, int values, int chunks, hipStream_
 extern "C" int sbg_swd_pyr_down(const float* x, float* y, int B, int C, int S, sbg_stream_t stream)
 {
     SBG_CHECK(B >= 0 && C >= 1, "swd_pyr_down: bad sizes B=%d C=%d", B, C);
-    SBG_CHECK(pow2_side(S) && S >= 4 && S <= 16384, "swd_pyr_down: side %d, a power of two in [4, 16384] is supported", S);
+    SBG_CHECK(sbg_pow2_in(S, 4, 16384), "swd_pyr_down: side %d, a power of two in [4, 16384] is supported", S);
     if (B == 0) return SBG_OK;
-    SBG_CHECK(x && y && x != y && aligned(x, 4) && aligned(y, 4), "swd_pyr_down: x and y must be distinct 4-byte aligned device pointers");
+    SBG_CHECK(x && y && x != y && sbg_aligned(x, 4) && sbg_aligned(y, 4), "swd_pyr_down: x and y must be distinct 4-byte aligned device pointers");
     const int64_t total = (int64_t)B * C * (S / 2) * (S / 2);
     hipStream_t s = (hipStream_t)stream;
     SbgProfScope prof(s, SBG_K_SWD, 0.0, 20.0 * total, {kDown, B, C, S});
@@ -240,9 +224,9 @@ extern "C" int sbg_swd_pyr_down(const float* x, float* y, int B, int C, int S, s
 extern "C" int sbg_swd_pyr_lap(const float* fine, const float* coarse, float* out, int B, int C, int S, sbg_stream_t stream)
 {
     SBG_CHECK(B >= 0 && C >= 1, "swd_pyr_lap: bad sizes B=%d C=%d", B, C);
-    SBG_CHECK(pow2_side(S) && S >= 4 && S <= 16384, "swd_pyr_lap: side %d, a power of two in [4, 16384] is supported", S);
+    SBG_CHECK(sbg_pow2_in(S, 4, 16384), "swd_pyr_lap: side %d, a power of two in [4, 16384] is supported", S);
     if (B == 0) return SBG_OK;
-    SBG_CHECK(fine && coarse && out && aligned(fine, 4) && aligned(coarse, 4) && aligned(out, 4), "swd_pyr_lap: null or misaligned pointer");
+    SBG_CHECK(fine && coarse && out && sbg_aligned(fine, 4) && sbg_aligned(coarse, 4) && sbg_aligned(out, 4), "swd_pyr_lap: null or misaligned pointer");
     SBG_CHECK(coarse != out, "swd_pyr_lap: `out` may be `fine`, never `coarse`");
     const int64_t total = (int64_t)B * C * S * S;
     hipStream_t s = (hipStream_t)stream;
@@ -260,7 +244,7 @@ extern "C" int sbg_swd_gather(const float* level, const int32_t* centres, float*
     SBG_CHECK(row_offset >= 0 && M >= 0 && row_offset + (int64_t)B * P <= M, "swd_gather: rows [%lld, +%lld) leave the %lld descriptor rows",
               (long long)row_offset, (long long)B * P, (long long)M);
     if (B == 0) return SBG_OK;
-    SBG_CHECK(level && centres && desc && aligned(level, 4) && aligned(centres, 4) && aligned(desc, 4), "swd_gather: null or misaligned pointer");
+    SBG_CHECK(level && centres && desc && sbg_aligned(level, 4) && sbg_aligned(centres, 4) && sbg_aligned(desc, 4), "swd_gather: null or misaligned pointer");
     const int64_t total = (int64_t)B * P * C * kPP;
     hipStream_t s = (hipStream_t)stream;
     SbgProfScope prof(s, SBG_K_SWD, 0.0, 8.0 * total + 8.0 * B * P, {kGather, B, C, S, P});
@@ -278,11 +262,11 @@ extern "C" int64_t sbg_swd_moments_workspace(int64_t M, int C)
 extern "C" int sbg_swd_moments(const float* desc, double* out, void* workspace, int64_t M, int C, sbg_stream_t stream)
 {
     SBG_CHECK(sbg_swd_moments_workspace(M, C) >= 0, "swd_moments: bad sizes M=%lld C=%d (M >= 1, 1..4 channels)", (long long)M, C);
-    SBG_CHECK(desc && out && workspace && aligned(desc, 4) && aligned(out, 8) && aligned(workspace, 8), "swd_moments: null or misaligned pointer");
+    SBG_CHECK(desc && out && workspace && sbg_aligned(desc, 4) && sbg_aligned(out, 8) && sbg_aligned(workspace, 8), "swd_moments: null or misaligned pointer");
     const int chunks = (int)((M + kMomRows - 1) / kMomRows);
     hipStream_t s = (hipStream_t)stream;
     {
-        SbgProfScope prof(s, SBG_K_SWD, 0.0, 4.0 * (double)M * C * kPP, {kMoments, clip31(M), C, chunks});
+        SbgProfScope prof(s, SBG_K_SWD, 0.0, 4.0 * (double)M * C * kPP, {kMoments, sbg_clip31(M), C, chunks});
         SBG_LAUNCH(swd_moments_kernel, dim3((unsigned)chunks, (unsigned)C), dim3(NT), 0, s, desc, (double*)workspace, M, C, chunks);
         SBG_HIP_LAUNCH_CHECK();
     }
@@ -295,11 +279,11 @@ extern "C" int sbg_swd_project(const float* desc, const float* s_c, const float*
     SBG_CHECK(M >= 1 && C >= 1 && C <= 4 && D >= 1, "swd_project: bad sizes M=%lld C=%d D=%d (1..4 channels)", (long long)M, C, D);
     SBG_CHECK(dirs_ld >= D, "swd_project: the directions' row pitch %lld is below D=%d", (long long)dirs_ld, D);
     SBG_CHECK((M + PM - 1) / PM <= INT32_MAX && (D + PD - 1) / PD <= 65535, "swd_project: M=%lld D=%d is too large", (long long)M, D);
-    SBG_CHECK(desc && s_c && t_c && dirs && out && aligned(desc, 4) && aligned(s_c, 4) && aligned(t_c, 4) && aligned(dirs, 4) && aligned(out, 4),
+    SBG_CHECK(desc && s_c && t_c && dirs && out && sbg_aligned(desc, 4) && sbg_aligned(s_c, 4) && sbg_aligned(t_c, 4) && sbg_aligned(dirs, 4) && sbg_aligned(out, 4),
               "swd_project: null or misaligned pointer");
     const int K = C * kPP;
     hipStream_t s = (hipStream_t)stream;
-    SbgProfScope prof(s, SBG_K_SWD, 2.0 * (double)M * K * D, 4.0 * ((double)M * K + (double)K * D + (double)M * D), {kProject, clip31(M), K, D});
+    SbgProfScope prof(s, SBG_K_SWD, 2.0 * (double)M * K * D, 4.0 * ((double)M * K + (double)K * D + (double)M * D), {kProject, sbg_clip31(M), K, D});
     SBG_LAUNCH(swd_project_kernel, dim3((unsigned)((M + PM - 1) / PM), (unsigned)((D + PD - 1) / PD)), dim3(NT), 0, s, desc, s_c, t_c, dirs, out, M, K, D,
                dirs_ld);
     SBG_HIP_LAUNCH_CHECK();
@@ -317,11 +301,11 @@ extern "C" int64_t sbg_swd_l1_workspace(int D, int64_t M)
 extern "C" int sbg_swd_l1(const float* a, const float* b, double* out, void* workspace, int D, int64_t M, sbg_stream_t stream)
 {
     SBG_CHECK(sbg_swd_l1_workspace(D, M) >= 0, "swd_l1: bad sizes D=%d M=%lld (1 <= D <= 65535, M >= 1)", D, (long long)M);
-    SBG_CHECK(a && b && out && workspace && aligned(a, 4) && aligned(b, 4) && aligned(out, 8) && aligned(workspace, 8), "swd_l1: null or misaligned pointer");
+    SBG_CHECK(a && b && out && workspace && sbg_aligned(a, 4) && sbg_aligned(b, 4) && sbg_aligned(out, 8) && sbg_aligned(workspace, 8), "swd_l1: null or misaligned pointer");
     const int chunks = (int)((M + kL1Chunk - 1) / kL1Chunk);
     hipStream_t s = (hipStream_t)stream;
     {
-        SbgProfScope prof(s, SBG_K_SWD, 0.0, 8.0 * (double)D * (double)M, {kL1, D, clip31(M), chunks});
+        SbgProfScope prof(s, SBG_K_SWD, 0.0, 8.0 * (double)D * (double)M, {kL1, D, sbg_clip31(M), chunks});
         SBG_LAUNCH(swd_l1_kernel, dim3((unsigned)chunks, (unsigned)D), dim3(NT), 0, s, a, b, (double*)workspace, M, chunks);
         SBG_HIP_LAUNCH_CHECK();
     }

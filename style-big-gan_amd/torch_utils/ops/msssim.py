@@ -16,14 +16,13 @@ import numpy as np
 import torch
 
 from ... import _lib
-from .swd import _block_sum_np, _strided_sum_np
+from ._exact_common import NT, block_sum_np, strided_sum_np
 
 TAPS = 11
 SIGMA2X2 = 4.5                  # 2 sigma^2, sigma = 1.5
 WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)      # Wang et al. 2003, finest level first
 C1 = (0.01 * 255) ** 2
 C2 = (0.03 * 255) ** 2
-NT = 256                        # work-items of a workgroup
 TILE_H, TILE_W = 16, 32         # map entries of one workgroup of the level kernel
 MIN_SIDE, MAX_SIDE = 16, 16384
 
@@ -117,7 +116,7 @@ def _map_mean_np(m):
     lanes = np.zeros([q, ty * tx, NT], dtype=np.float64)
     for i in range(TILE_H // rows):
         lanes = lanes + t[:, :, i]
-    return _strided_sum_np(_block_sum_np(lanes)) / np.float64(float(n) * float(n))
+    return strided_sum_np(block_sum_np(lanes)) / np.float64(float(n) * float(n))
 
 
 def _level_terms_cpu(x, y, g):
@@ -152,7 +151,7 @@ def level_terms(x, y):
     need = lib.sbg_msssim_workspace(n * c, s)
     if need < 0:
         raise ValueError(f"msssim.level_terms: {n * c} image-channels of side {s} are more than the 2^24 tiles of one launch; cut the batch")
-    ws = torch.empty([need // 8], dtype=torch.float64, device=x.device)
+    ws = _lib.workspace(need, x.device, "sbg_msssim_workspace")
     _lib.check(lib.sbg_msssim_level(x.data_ptr(), y.data_ptr(), int(x.dtype == torch.uint8), g.data_ptr(), C1, C2, out.data_ptr(), ws.data_ptr(), n * c, s,
                                     _lib.stream_ptr(x.device)), "sbg_msssim_level")
     return out

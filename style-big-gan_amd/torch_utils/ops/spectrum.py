@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from ... import _lib
-from .swd import _fma32
+from ._exact_common import fma32
 
 PADS = (1, 2, 4)
 MIN_SIDE, MAX_SIDE = 16, 1024
@@ -104,8 +104,8 @@ def _stages_np(re, im, stages, S, h0):
         ar, br, ai, bi = re[..., 0, :], re[..., 1, :], im[..., 0, :], im[..., 1, :]
         wr = np.broadcast_to(stages[h - 1:2 * h - 1, 0], br.shape)
         wi = np.broadcast_to(stages[h - 1:2 * h - 1, 1], br.shape)
-        tr = _fma32(br, wr, -(bi * wi))                 # the inner products are fp32 products: rounded before the fmaf
-        ti = _fma32(br, wi, bi * wr)
+        tr = fma32(br, wr, -(bi * wi))                 # the inner products are fp32 products: rounded before the fmaf
+        ti = fma32(br, wi, bi * wr)
         re = np.stack([ar + tr, ar - tr], axis=-2).reshape(lead + (S,))
         im = np.stack([ai + ti, ai - ti], axis=-2).reshape(lead + (S,))
         h *= 2
@@ -116,7 +116,7 @@ def _transform_np(x, s, t, window, stages, S):
     """x fp32 ndarray [BC, R, R] -> (re, im) fp32 [BC, S/2 + 1, S]: the windowed transform Y[kx, ky] of every image-channel"""
     R = x.shape[2]
     P, rev = S // R, _bitrev(R)
-    v = _fma32(x, np.broadcast_to(np.float32(s), x.shape), np.broadcast_to(np.float32(t), x.shape))
+    v = fma32(x, np.broadcast_to(np.float32(s), x.shape), np.broadcast_to(np.float32(t), x.shape))
     a = v * window[None, None, :]
     # the samples in bit-reversed order, each P times: what the stages h < P make of the zero padding
     re = np.repeat(a[:, :, rev], P, axis=2)

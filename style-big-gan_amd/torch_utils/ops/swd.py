@@ -15,10 +15,10 @@ import numpy as np
 import torch
 
 from ... import _lib
+from ._exact_common import chunked_sum_np, fma32
 
 PATCH = 7
 PP = PATCH * PATCH          # values per channel in a descriptor row
-NT = 256                    # work-items of the summing workgroups
 MOMENT_ROWS = 1024          # descriptor rows per chunk of channel_moments
 L1_CHUNK = 16384            # elements per chunk of sorted_l1
 
@@ -137,40 +137,6 @@ def gather_descriptors(level, centres, out, row_offset=0):
 
 # ------------------------------------------------------------------------------------------------ fixed-order float64 sums
 
-def _block_sum_np(lanes):
-    """csrc/reduce.h block_sum over the last axis of 256 lanes: the xor butterfly (offsets 32 .. 1) in each wave, the four waves left to right"""
-    w = lanes.reshape(lanes.shape[:-1] + (NT // 64, 64))
-    lane = np.arange(64)
-    for off in (32, 16, 8, 4, 2, 1):
-        w = w + w[..., lane ^ off]
-    s = w[..., 0, 0]
-    for i in range(1, NT // 64):
-        s = s + w[..., i, 0]
-    return s
-
-
-def _strided_sum_np(v):
-    """v float64 [..., n] -> [...]: lane t adds the elements t, t + 256, ... in ascending order, then block_sum"""
-    n = v.shape[-1]
-    rounds = -(-n // NT)
-    if rounds * NT != n:
-        v = np.concatenate([v, np.zeros(v.shape[:-1] + (rounds * NT - n,), dtype=np.float64)], axis=-1)       # + 0.0 changes nothing
-    v = v.reshape(v.shape[:-1] + (rounds, NT))
-    acc = np.zeros(v.shape[:-2] + (NT,), dtype=np.float64)
-    for r in range(rounds):
-        acc = acc + v[..., r, :]
-    return _block_sum_np(acc)
-
-
-def _chunked_sum_np(v, chunk):
-    """v float64 [Q, n] -> [Q]: chunks of `chunk` elements summed by _strided_sum_np, the chunk sums by _strided_sum_np again"""
-    q, n = v.shape
-    chunks = -(-n // chunk)
-    if chunks * chunk != n:
-        v = np.concatenate([v, np.zeros([q, chunks * chunk - n], dtype=np.float64)], axis=1)
-    return _strided_sum_np(_strided_sum_np(v.reshape(q, chunks, chunk)))
-
-
 def channel_moments(desc, channels):
     """desc fp32 [M, 49 C] -> float64 [C, 2] on desc's device: per channel, the sum and the sum of squares of its M * 49 values.  Chunks of
     1024 descriptor rows; in a chunk lane t of 256 adds the values t, t + 256, ... (row-major inside the channel's [rows, 49] slab), the
@@ -182,13 +148,10 @@ def channel_moments(desc, channels):
     if desc.device.type != "cuda":
         v = desc.numpy().astype(np.float64).reshape(m, channels, PP).transpose(1, 0, 2).reshape(channels, m * PP)
         both = np.concatenate([v, v * v], axis=0)           # [2 C, M * 49]: sums first, then squares
-        sums = _chunked_sum_np(both, MOMENT_ROWS * PP)
+        sums = chunked_sum_np(both, MOMENT_ROWS * PP)
         return torch.from_numpy(np.stack([sums[:channels], sums[channels:]], axis=1).copy())
     lib = _lib.load()
-    need = lib.sbg_swd_moments_workspace(m, channels)
-    if need < 0:
-        _lib.check(1, "sbg_swd_moments_workspace")
-    ws = torch.empty([max(need // 8, 1)], dtype=torch.float64, device=desc.device)
+    ws = _lib.workspace(lib.sbg_swd_moments_workspace(m, channels), desc.device, "sbg_swd_moments_workspace")
     out = torch.empty([channels, 2], dtype=torch.float64, device=desc.device)
     _lib.check(lib.sbg_swd_moments(desc.data_ptr(), out.data_ptr(), ws.data_ptr(), m, channels, _lib.stream_ptr(desc.device)), "sbg_swd_moments")
     return out
@@ -204,32 +167,15 @@ def sorted_l1(a, b):
     d, m = a.shape
     if a.device.type != "cuda":
         diff = np.abs(a.numpy().astype(np.float64) - b.numpy().astype(np.float64))
-        return torch.from_numpy(_chunked_sum_np(diff, L1_CHUNK).copy())
+        return torch.from_numpy(chunked_sum_np(diff, L1_CHUNK).copy())
     lib = _lib.load()
-    need = lib.sbg_swd_l1_workspace(d, m)
-    if need < 0:
-        _lib.check(1, "sbg_swd_l1_workspace")
-    ws = torch.empty([max(need // 8, 1)], dtype=torch.float64, device=a.device)
+    ws = _lib.workspace(lib.sbg_swd_l1_workspace(d, m), a.device, "sbg_swd_l1_workspace")
     out = torch.empty([d], dtype=torch.float64, device=a.device)
     _lib.check(lib.sbg_swd_l1(a.data_ptr(), b.data_ptr(), out.data_ptr(), ws.data_ptr(), d, m, _lib.stream_ptr(a.device)), "sbg_swd_l1")
     return out
 
 
 # ------------------------------------------------------------------------------------------------ projection
-
-def _fma32(a, b, c):
-    """float32 arrays -> fmaf(a, b, c), one rounding: the product of two floats is exact in float64; the float64 sum is taken with its
-    exact error (two-sum) and forced to an odd last bit when inexact, after which the rounding to float32 is the rounding of the exact value"""
-    p = a.astype(np.float64) * b.astype(np.float64)
-    c = c.astype(np.float64)
-    s = p + c
-    bb = s - p
-    err = (p - (s - bb)) + (c - bb)
-    fix = (err != 0) & ((s.view(np.int64) & 1) == 0) & np.isfinite(s)
-    if fix.any():
-        s = np.where(fix, np.nextafter(s, np.where(err > 0, np.inf, -np.inf)), s)
-    return s.astype(np.float32)
-
 
 def project(desc, s, t, dirs):
     """desc fp32 [M, 49 C], s / t fp32 [C], dirs fp32 [49 C, D] (any row pitch: a column slice of a wider table is taken as it is) ->
@@ -250,8 +196,8 @@ def project(desc, s, t, dirs):
         x, sn, tn, dn = desc.numpy(), s.numpy(), t.numpy(), dirs.numpy()
         acc = np.zeros([d, m], dtype=np.float32)
         for kk in range(k):
-            xh = _fma32(x[:, kk], np.broadcast_to(sn[kk // PP], [m]), np.broadcast_to(tn[kk // PP], [m]))
-            acc = _fma32(np.broadcast_to(xh[None, :], [d, m]), np.broadcast_to(dn[kk, :, None], [d, m]), acc)
+            xh = fma32(x[:, kk], np.broadcast_to(sn[kk // PP], [m]), np.broadcast_to(tn[kk // PP], [m]))
+            acc = fma32(np.broadcast_to(xh[None, :], [d, m]), np.broadcast_to(dn[kk, :, None], [d, m]), acc)
         return torch.from_numpy(acc)
     out = torch.empty([d, m], dtype=torch.float32, device=desc.device)
     _lib.check(_lib.load().sbg_swd_project(desc.data_ptr(), s.data_ptr(), t.data_ptr(), dirs.data_ptr(), out.data_ptr(), m, c, d, dirs.stride(0),

@@ -11,7 +11,8 @@ TERM_ATOL = 1e-9        # per-level term: values <= 255, moments <= 65025, under
                         # the denominators are >= C1 = 6.5 and >= C2 = 58.5
 SCORE_RTOL = 1e-8       # pair score, on pairs whose every level term is >= 0.1 (the power is not Lipschitz near 0)
 PUBLISHED = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
-GPU_SHAPES = [(1, 1, 16), (5, 3, 32), (2, 3, 64)]           # (N, C, S): a 6 x 6 map; a ragged 22 x 22 map, odd image-channel count; 54 x 54: 4 x 2 tiles
+GPU_SHAPES = [(1, 1, 16), (5, 3, 32), (2, 3, 64), (1, 1, 512)]     # (N, C, S): a 6 x 6 map; a ragged 22 x 22 map, odd image-channel count; 54 x 54:
+                                                                    # 4 x 2 tiles; 502 x 502: 32 x 16 = 512 tiles, two rounds per lane of the merge
 
 
 def ref_window2d():

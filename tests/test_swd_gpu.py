@@ -169,6 +169,12 @@ def test_sorted_l1(dev):
     with expect_launch("swd", lambda r: r[:3] == (6, 2, 3), "merge of three chunks"):
         got = swd.sorted_l1(a.to(dev), b.to(dev))
     assert _same_bits(got, swd.sorted_l1(a, b))
+    # 258 chunks of a direction: a lane of the merge adds two partials
+    m = 257 * 16384 + 5
+    a, b = torch.randn(2, m, generator=gen) * 3, torch.randn(2, m, generator=gen) * 3
+    with expect_launch("swd", lambda r: r[:3] == (6, 2, 258), "merge of 258 chunks"):
+        got = swd.sorted_l1(a.to(dev), b.to(dev))
+    assert _same_bits(got, swd.sorted_l1(a, b))
 
 
 def test_end_to_end_against_the_restatement(dev):
