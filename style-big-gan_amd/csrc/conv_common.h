@@ -1,6 +1,7 @@
-// conv_common.h -- what the convolution kernels (conv_k64.hip, conv_up2.hip, conv_igemm.hip, conv_thin.hip; conv_wgrad.hip for the first
-// two items) share on the host side: the LDS-DMA sentinel, the MFMA wrappers, the kernel argument block, the host launch layer
-// (conv_is_plain, conv_prof_bytes, conv_launch) and the entry points of the per-file dispatchers.  The device-side pieces are in conv_device.h.
+// conv_common.h -- what the convolution kernels (conv_k64.hip, conv_up2.hip, conv_igemm.hip, conv_thin.hip, conv_wgrad.hip) share on the
+// host side: the LDS-DMA sentinel, the MFMA wrappers, the one launch function launch_as (these three are all conv_wgrad.hip takes: it has
+// its own argument block and byte model), the kernel argument block ConvArgs, the forward launch layer (conv_is_plain, conv_prof_bytes,
+// conv_launch) and the entry points of the per-file dispatchers.  The device-side pieces are in conv_device.h.
 #pragma once
 #include "sbg_common.h"
 #include <cstdlib>
@@ -67,19 +68,27 @@ static inline double conv_prof_bytes(const ConvArgs& a, double outpix)
     return 2.0 * a.N * a.IH * a.IW * (double)a.Cin + 2.0 * a.ntaps * a.Cout * (double)a.Cin + ys * outpix * (double)a.Cout * (a.accumulate ? 2 : 1);
 }
 
-// One launch of a convolution kernel: grid bound, dynamic-LDS limit (raised once per kernel), profiler scope, launch, error check.
+// One launch of a kernel of the family: grid bound, dynamic-LDS limit (raised once per kernel), profiler scope, launch, error check.
+// kind = the profiler's kernel kind, who = the entry point named in the error texts.
 // dims = the profiler's shape key; its last entry is the code that names the kernel (bench.py, profiles/summarize.py, tests read it).
+template <auto Kern, class... Args>
+static int launch_as(int kind, const char* who, int64_t nblk, unsigned grid_y, unsigned block, int lds, hipStream_t stream, double flops,
+                     double bytes, std::initializer_list<int> dims, const Args&... args)
+{
+    if (nblk > INT32_MAX || nblk < 1) return sbg_fail(SBG_ERR_INVALID, "%s: grid too large", who);
+    if (lds > 64 * 1024 && !SBG_RAISE_LDS_ONCE(Kern, lds))
+        return sbg_fail(SBG_ERR_LAUNCH, "%s: cannot raise the dynamic LDS limit to %d bytes", who, lds);
+    SbgProfScope prof(stream, kind, flops, bytes, dims);
+    SBG_LAUNCH(Kern, dim3((unsigned)nblk, grid_y), dim3(block), lds, stream, args...);
+    SBG_HIP_LAUNCH_CHECK();
+    return SBG_OK;
+}
+// the forward / data-gradient convolutions (conv_wgrad.hip calls launch_as with its own kinds)
 template <auto Kern, class... Args>
 static int conv_launch(int64_t nblk, unsigned grid_y, unsigned block, int lds, hipStream_t stream, double flops, double bytes,
                        std::initializer_list<int> dims, const Args&... args)
 {
-    if (nblk > INT32_MAX || nblk < 1) return sbg_fail(SBG_ERR_INVALID, "conv2d_igemm: grid too large");
-    if (lds > 64 * 1024 && !SBG_RAISE_LDS_ONCE(Kern, lds))
-        return sbg_fail(SBG_ERR_LAUNCH, "conv2d_igemm: cannot raise the dynamic LDS limit to %d bytes", lds);
-    SbgProfScope prof(stream, SBG_K_CONV_IGEMM, flops, bytes, dims);
-    SBG_LAUNCH(Kern, dim3((unsigned)nblk, grid_y), dim3(block), lds, stream, args...);
-    SBG_HIP_LAUNCH_CHECK();
-    return SBG_OK;
+    return launch_as<Kern>(SBG_K_CONV_IGEMM, "conv2d_igemm", nblk, grid_y, block, lds, stream, flops, bytes, dims, args...);
 }
 
 } // namespace sbgconv

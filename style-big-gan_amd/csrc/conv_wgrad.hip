@@ -21,18 +21,7 @@
 
 namespace {
 
-struct bf16_mfma {}; struct f16_mfma {};
-template <class MF> struct Mfma;
-template <> struct Mfma<bf16_mfma> {
-    static __device__ __forceinline__ float4_t run(short8_t a, short8_t b, float4_t c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-    }
-};
-template <> struct Mfma<f16_mfma> {
-    static __device__ __forceinline__ float4_t run(short8_t a, short8_t b, float4_t c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
-    }
-};
+using sbgconv::bf16_mfma; using sbgconv::f16_mfma; using sbgconv::Mfma;
 
 struct WgradArgs {
     const unsigned short* a; const unsigned short* b; float* out; float* ws;
@@ -62,7 +51,6 @@ static __device__ __forceinline__ bool wgrad_decode_block(const WgradArgs& p, in
     ta = tile % p.atiles; tb = tile / p.atiles;
     return split < p.nsplit;
 }
-static inline unsigned wgrad_grid(const WgradArgs& a) { return 8u * (unsigned)(a.atiles * a.btiles) * (unsigned)((a.nsplit + 7) / 8); }
 
 typedef __attribute__((address_space(3))) short4_t* lds_s4_ptr;
 
@@ -551,50 +539,50 @@ __global__ __launch_bounds__(256) void conv_wgrad_thin_kernel(WgradArgs p, int d
     }
 }
 
-struct ThinPlan { bool ok; int dymin, dxmin, RY, PCOLS, wave_lds, nwg; };
+// ---------------------------------------------------------------------------------------------------------------------
+// Host side.  wgrad_plan decides everything about a call, once, from the validated parameter block alone (no HIP calls): the kernel
+// that serves it, its tiles and pixel splits, launch geometry, launch-record code and the profiler's figures.  Both entry points read it.
 
-static ThinPlan thin_plan(const sbg_wgrad_params* q)
+enum WgradFamily { WG_EMPTY, WG_THIN, WG_ROWS, WG_BIG, WG_TAPS };      // no pixels | thin | rows | conv_wgrad_kernel 128 x 128, one tap | 64 x 64, groups of nine taps
+
+struct WgradPlan {
+    WgradFamily family;
+    int bca, bcb;                                       // channels per workgroup tile (thin: 16-channel fragments per wave)
+    int atiles, btiles, nchunks, nsplit, chunks_per_split;
+    int64_t grid; int block, lds;
+    int code;                                           // dims[6] of the launch record
+    unsigned a_bytes, b_bytes;                          // rows kernel: byte extents of the operands
+    int dymin, dxmin, RY, PCOLS, wave_lds;              // thin kernel: tap window origin, patch rows x columns, LDS bytes per wave (grid = workgroups of four waves)
+    double flops_per_tap, bytes_ab, bytes_out_per_tap;  // profiler: a launch over t taps does flops_per_tap * t and moves bytes_ab + bytes_out_per_tap * t
+};
+
+static bool thin_plan(const sbg_wgrad_params& q, WgradPlan& pl)
 {
-    ThinPlan t; t.ok = false;
-    if (q->Ca > 32 || q->Cb > 32 || q->Ca * q->Cb > 512 || q->ntaps > 9 || q->ntaps < 1 || q->stride < 1 || q->stride > 2 || q->N < 1) return t;
-    int dy0 = q->tap_dy[0], dy1 = dy0, dx0 = q->tap_dx[0], dx1 = dx0;
-    for (int i = 1; i < q->ntaps; i++) {
-        if (q->tap_dy[i] < dy0) dy0 = q->tap_dy[i]; if (q->tap_dy[i] > dy1) dy1 = q->tap_dy[i];
-        if (q->tap_dx[i] < dx0) dx0 = q->tap_dx[i]; if (q->tap_dx[i] > dx1) dx1 = q->tap_dx[i];
+    if (q.Ca > 32 || q.Cb > 32 || q.Ca * q.Cb > 512 || q.ntaps > 9 || q.stride > 2) return false;
+    int dy0 = q.tap_dy[0], dy1 = dy0, dx0 = q.tap_dx[0], dx1 = dx0;
+    for (int i = 1; i < q.ntaps; i++) {
+        if (q.tap_dy[i] < dy0) dy0 = q.tap_dy[i]; if (q.tap_dy[i] > dy1) dy1 = q.tap_dy[i];
+        if (q.tap_dx[i] < dx0) dx0 = q.tap_dx[i]; if (q.tap_dx[i] > dx1) dx1 = q.tap_dx[i];
     }
-    if (dy1 - dy0 > 2 || dx1 - dx0 > 2) return t;
-    t.dymin = dy0; t.dxmin = dx0; t.RY = dy1 - dy0 + 1; t.PCOLS = q->stride * 31 + (dx1 - dx0) + 1;
-    t.wave_lds = ((32 * q->Ca + t.RY * t.PCOLS * q->Cb) * 2 + 15) & ~15;
-    const int64_t nchunks = (int64_t)q->N * q->PH * ((q->PW + 31) / 32);
-    int64_t nwg = (nchunks + 15) / 16;                    // at least four chunks per wave
-    if (nwg > 2048) nwg = 2048;
-    if (nwg < 1) nwg = 1;
-    t.nwg = (int)nwg;
-    t.ok = nchunks < INT32_MAX;
-    return t;
+    const int64_t nchunks = (int64_t)q.N * q.PH * ((q.PW + 31) / 32);
+    if (dy1 - dy0 > 2 || dx1 - dx0 > 2 || nchunks >= INT32_MAX) return false;
+    pl.dymin = dy0; pl.dxmin = dx0; pl.RY = dy1 - dy0 + 1; pl.PCOLS = q.stride * 31 + (dx1 - dx0) + 1;
+    pl.wave_lds = ((32 * q.Ca + pl.RY * pl.PCOLS * q.Cb) * 2 + 15) & ~15;
+    pl.grid = (nchunks + 15) / 16;                       // at least four chunks per wave
+    if (pl.grid > 2048) pl.grid = 2048;
+    return true;
 }
 
-static void plan_split(WgradArgs& a, int bca, int bcb, int target)     // target = workgroups aimed for (tiles x pixel splits)
+static bool rows_kernel_ok(const sbg_wgrad_params& q, WgradPlan& pl)
 {
-    a.atiles = (a.Ca + bca - 1) / bca;
-    a.btiles = (a.Cb + bcb - 1) / bcb;
-    a.nchunks = (int)((a.P + 31) / 32);
-    const int tiles = a.atiles * a.btiles;
-    int want = (target + tiles - 1) / tiles;             // ~target workgroups in total
-    int maxsplit = a.nchunks / 8; if (maxsplit < 1) maxsplit = 1;   // at least 8 chunks of work per workgroup
-    if (want > maxsplit) want = maxsplit;
-    if (want < 1) want = 1;
-    a.chunks_per_split = (a.nchunks + want - 1) / want;
-    a.nsplit = (a.nchunks + a.chunks_per_split - 1) / a.chunks_per_split;
-}
-
-static bool use_big_tile(int ntaps) { return ntaps == 1; }
-
-static int rows_bca(const WgradArgs& a)      // a-tile width of the rows kernel: 128 halves the staged bytes per MFMA
-{
-    // 128 wherever there are 128 a channels: half the staged bytes and 0.72 instead of 1.22 fragment reads per MFMA.  (While the compiler still
-    // guarded the fragment reads with vmcnt(0), the wide tile lost 7-10 % at stride 1 up to 512 channels: one workgroup per CU, nothing overlapped.)
-    return a.Ca >= 128 ? 128 : 64;
+    if (q.stride > 2 || (q.PW % 32) != 0 || q.ntaps != 9) return false;
+    for (int t = 0; t < 9; t++)          // the kernel hard-codes a row-major 3x3 tap window starting at (dy[0], dx[0])
+        if (q.tap_dy[t] != q.tap_dy[0] + t / 3 || q.tap_dx[t] != q.tap_dx[0] + t % 3) return false;
+    if (q.as_n < 0 || q.as_h < 0 || q.as_w < 0 || q.bs_n < 0 || q.bs_h < 0 || q.bs_w < 0) return false;
+    auto extent = [&](int h, int w, int c, int64_t s_n, int64_t s_h, int64_t s_w) { return 2 * ((int64_t)(q.N - 1) * s_n + (int64_t)(h - 1) * s_h + (int64_t)(w - 1) * s_w + c); };
+    const int64_t ab = extent(q.PH, q.PW, q.Ca, q.as_n, q.as_h, q.as_w), bb = extent(q.BH, q.BW, q.Cb, q.bs_n, q.bs_h, q.bs_w);
+    pl.a_bytes = (unsigned)ab; pl.b_bytes = (unsigned)bb;
+    return ab < (int64_t)SBG_OOB_OFFSET && bb < (int64_t)SBG_OOB_OFFSET;
 }
 
 // Stages of the rows kernel (LDS: stages x (a + patch pieces) + 1 KiB).  Measured flat from 2 to 6 stages at one workgroup per CU (the L2 -> LDS
@@ -605,18 +593,59 @@ static constexpr int rows_nstage(int stride, int bca)
     return stride == 1 ? 4 : 2;               // 4 x 19 + 1 = 77 KB / 2 x 31 + 1 = 63 KB: two per CU
 }
 
-static bool rows_kernel_ok(const sbg_wgrad_params* q, const WgradArgs& a)
+static void plan_split(WgradPlan& pl, const sbg_wgrad_params& q, int bca, int bcb, int target)     // target = workgroups aimed for (tiles x pixel splits)
 {
-    if ((q->stride != 1 && q->stride != 2) || (q->PW % 32) != 0 || q->ntaps != 9) return false;
-    for (int t = 0; t < 9; t++)          // the kernel hard-codes a row-major 3x3 tap window starting at (dy[0], dx[0])
-        if (q->tap_dy[t] != q->tap_dy[0] + t / 3 || q->tap_dx[t] != q->tap_dx[0] + t % 3) return false;
-    if (q->as_n < 0 || q->as_h < 0 || q->as_w < 0 || q->bs_n < 0 || q->bs_h < 0 || q->bs_w < 0) return false;
-    const int64_t ab = 2 * ((int64_t)(q->N - 1) * q->as_n + (int64_t)(q->PH - 1) * q->as_h + (int64_t)(q->PW - 1) * q->as_w + q->Ca);
-    const int64_t bb = 2 * ((int64_t)(q->N - 1) * q->bs_n + (int64_t)(q->BH - 1) * q->bs_h + (int64_t)(q->BW - 1) * q->bs_w + q->Cb);
-    return ab < (int64_t)SBG_OOB_OFFSET && bb < (int64_t)SBG_OOB_OFFSET && a.P > 0;
+    pl.bca = bca; pl.bcb = bcb;
+    pl.atiles = (q.Ca + bca - 1) / bca;
+    pl.btiles = (q.Cb + bcb - 1) / bcb;
+    const int tiles = pl.atiles * pl.btiles;
+    int want = (target + tiles - 1) / tiles;             // ~target workgroups in total
+    int maxsplit = pl.nchunks / 8; if (maxsplit < 1) maxsplit = 1;   // at least 8 chunks of work per workgroup
+    if (want > maxsplit) want = maxsplit;
+    if (want < 1) want = 1;
+    pl.chunks_per_split = (pl.nchunks + want - 1) / want;
+    pl.nsplit = (pl.nchunks + pl.chunks_per_split - 1) / pl.chunks_per_split;
+    pl.grid = 8 * (int64_t)tiles * ((pl.nsplit + 7) / 8);          // the splits padded to the eight XCDs (wgrad_decode_block)
 }
 
-static int fill_args(const sbg_wgrad_params* q, WgradArgs& a)
+static WgradPlan wgrad_plan(const sbg_wgrad_params& q)
+{
+    WgradPlan pl = {};
+    const int64_t P = (int64_t)q.N * q.PH * q.PW;
+    pl.family = WG_EMPTY; pl.nsplit = 1;
+    if (P == 0) return pl;                               // an empty batch: decided before anything divides
+    pl.nchunks = (int)((P + 31) / 32);
+    pl.block = 256;
+    if (thin_plan(q, pl)) {
+        pl.family = WG_THIN;
+        pl.bca = (q.Ca + 15) / 16; pl.bcb = (q.Cb + 15) / 16;
+        pl.atiles = pl.btiles = 1; pl.nsplit = 4 * (int)pl.grid; pl.chunks_per_split = 0;      // one slab per wave
+        pl.lds = 4 * pl.wave_lds;
+        pl.code = 3000000 + pl.bca * 10 + pl.bcb;
+    } else if (rows_kernel_ok(q, pl)) {
+        pl.family = WG_ROWS;
+        // a tile of 128 wherever there are 128 a channels: half the staged bytes and 0.72 instead of 1.22 fragment reads per MFMA.  (While the compiler still
+        // guarded the fragment reads with vmcnt(0), the wide tile lost 7-10 % at stride 1 up to 512 channels: one workgroup per CU, nothing overlapped.)
+        plan_split(pl, q, q.Ca >= 128 ? 128 : 64, 64, 512);      // one resident workgroup per CU: two waves of workgroups, half the slab traffic
+        // stage = a pieces + 3 x patch pieces, 1 KiB each; one more KiB behind the stages takes the spare pieces
+        const int stage_kib = pl.bca / 16 + 3 * ((q.stride * 31 + 3 + 7) / 8);
+        pl.block = 512;
+        pl.lds = (rows_nstage(q.stride, pl.bca) * stage_kib + 1) * 1024;
+        pl.code = 1000000 + pl.bca * 1000 + 64;          // 1xxxxxx = rows kernel (profiles/summarize.py joins the launch log with the kernel trace on this)
+    } else {
+        pl.family = q.ntaps == 1 ? WG_BIG : WG_TAPS;
+        const int tile = pl.family == WG_BIG ? 128 : 64, nt = pl.family == WG_BIG ? 1 : 9;
+        plan_split(pl, q, tile, tile, 1024);
+        pl.lds = (1 + nt) * 32 * (tile * 2 + 32);        // one a tile and nt b tiles of 32 pixels, rows padded by 32 B
+        pl.code = tile * 1000 + tile;
+    }
+    pl.flops_per_tap = 2.0 * (double)P * q.Ca * (double)q.Cb;
+    pl.bytes_ab = 2.0 * (double)P * q.Ca + 2.0 * (double)q.N * q.BH * q.BW * q.Cb;
+    pl.bytes_out_per_tap = 4.0 * (double)q.Ca * q.Cb * (pl.nsplit > 1 ? pl.nsplit : 1);
+    return pl;
+}
+
+static int fill_args(const sbg_wgrad_params* q, WgradPlan& pl, WgradArgs& a)
 {
     SBG_CHECK(q && q->a && q->b && q->out, "conv2d_wgrad: null pointer");
     SBG_CHECK(q->dtype == SBG_BF16 || q->dtype == SBG_F16, "conv2d_wgrad: a/b must be bf16 or f16 (fp32 inputs are split by the host)");
@@ -627,6 +656,7 @@ static int fill_args(const sbg_wgrad_params* q, WgradArgs& a)
     SBG_CHECK(sbg_aligned16(q->a) && sbg_aligned16(q->b), "conv2d_wgrad: a and b must be 16-byte aligned");
     SBG_CHECK((q->as_n % 8) == 0 && (q->as_h % 8) == 0 && (q->as_w % 8) == 0 && (q->bs_n % 8) == 0 && (q->bs_h % 8) == 0 && (q->bs_w % 8) == 0,
               "conv2d_wgrad: pixel / row strides must be multiples of 8 elements");
+    pl = wgrad_plan(*q);
     a.a = (const unsigned short*)q->a; a.b = (const unsigned short*)q->b; a.out = q->out; a.ws = (float*)q->workspace;
     a.N = q->N; a.PH = q->PH; a.PW = q->PW; a.Ca = q->Ca; a.BH = q->BH; a.BW = q->BW; a.Cb = q->Cb;
     a.as_n = q->as_n; a.as_h = q->as_h; a.as_w = q->as_w; a.bs_n = q->bs_n; a.bs_h = q->bs_h; a.bs_w = q->bs_w;
@@ -634,113 +664,79 @@ static int fill_args(const sbg_wgrad_params* q, WgradArgs& a)
     for (int t = 0; t < SBG_MAX_TAPS; t++) { a.tap_dy[t] = q->tap_dy[t]; a.tap_dx[t] = q->tap_dx[t]; }
     a.P = (int64_t)q->N * q->PH * q->PW;
     a.tap0 = 0; a.ntaps_total = q->ntaps;
-    if (use_big_tile(q->ntaps)) plan_split(a, 128, 128, 1024); else plan_split(a, 64, 64, 1024);
-    if (rows_kernel_ok(q, a)) plan_split(a, rows_bca(a), 64, 512);      // one resident workgroup per CU: two waves of workgroups, half the slab traffic
-    const ThinPlan tp = thin_plan(q);
-    if (tp.ok) { a.atiles = a.btiles = 1; a.nsplit = 4 * tp.nwg; a.chunks_per_split = 0; }      // one slab per wave (conv_wgrad_thin_kernel)
+    a.nchunks = pl.nchunks; a.nsplit = pl.nsplit; a.chunks_per_split = pl.chunks_per_split; a.atiles = pl.atiles; a.btiles = pl.btiles;
     return SBG_OK;
 }
 
-template <class MF, int BCA, int BCB, int NT>
-static int launch_wgrad(const WgradArgs& a, hipStream_t stream)
+// One kernel launch of the plan over the taps of `g`: the whole call, or one of its tap groups.
+template <auto Kern, class... Extra>
+static int launch(const WgradPlan& pl, const WgradArgs& g, hipStream_t s, const Extra&... extra)
 {
-    constexpr int lds = 32 * (BCA * 2 + 32) + NT * 32 * (BCB * 2 + 32);
-    auto kern = conv_wgrad_kernel<MF, BCA, BCB, NT>;
-    if (lds > 64 * 1024 && !SBG_RAISE_LDS_ONCE(kern, lds))
-        return sbg_fail(SBG_ERR_LAUNCH, "conv2d_wgrad: cannot raise the dynamic LDS limit to %d bytes", lds);
-    SbgProfScope prof(stream, SBG_K_CONV_WGRAD, 2.0 * (double)a.P * a.Ca * (double)a.Cb * a.ntaps,
-                      2.0 * (double)a.P * a.Ca + 2.0 * (double)a.N * a.BH * a.BW * a.Cb + 4.0 * a.ntaps * (double)a.Ca * a.Cb * (a.nsplit > 1 ? a.nsplit : 1),
-                      {(int)(a.P > INT32_MAX ? INT32_MAX : a.P), a.Ca, a.Cb, a.ntaps, a.stride, a.nsplit, BCA * 1000 + BCB});
-    SBG_LAUNCH(kern, dim3(wgrad_grid(a)), dim3(256), lds, stream, a);
-    SBG_HIP_LAUNCH_CHECK();
-    return SBG_OK;
+    return sbgconv::launch_as<Kern>(SBG_K_CONV_WGRAD, "conv2d_wgrad", pl.grid, 1, pl.block, pl.lds, s,
+                                    pl.flops_per_tap * g.ntaps, pl.bytes_ab + pl.bytes_out_per_tap * g.ntaps,
+                                    {(int)(g.P > INT32_MAX ? INT32_MAX : g.P), g.Ca, g.Cb, g.ntaps, g.stride, g.nsplit, pl.code}, g, extra...);
+}
+
+template <class MF, int TA, int TB>
+static int thin(const WgradPlan& pl, const WgradArgs& a, hipStream_t s) { return launch<conv_wgrad_thin_kernel<MF, TA, TB>>(pl, a, s, pl.dymin, pl.dxmin, pl.RY, pl.PCOLS, pl.wave_lds); }
+template <class MF, int S, int BCA>
+static int rows(const WgradPlan& pl, const WgradArgs& a, hipStream_t s) { return launch<conv_wgrad_rows_kernel<MF, S, BCA, rows_nstage(S, BCA)>>(pl, a, s, pl.a_bytes, pl.b_bytes); }
+
+// out (+)= the slabs of the workspace, summed in slab order, LANES lanes per element
+template <int LANES>
+static int reduce_slabs(const WgradArgs& a, int64_t n, hipStream_t s)
+{
+    return sbgconv::launch_as<wgrad_reduce_kernel<LANES>>(SBG_K_WGRAD_REDUCE, "conv2d_wgrad", sbg_stream_grid(n * LANES, 256), 1, 256, 0, s, 0.0,
+                                                          4.0 * n * (a.nsplit + 1), {(int)n, a.nsplit}, a.ws, a.out, n, a.nsplit, a.accumulate);
+}
+static int reduce_slabs(const WgradArgs& a, hipStream_t s)
+{
+    const int64_t n = (int64_t)a.ntaps_total * a.Ca * a.Cb;
+    if (n >= (1 << 18) || a.nsplit < 16) return reduce_slabs<1>(a, n, s);      // plenty of elements: one lane each, coalesced across lanes
+    return n >= (1 << 14) ? reduce_slabs<4>(a, n, s) : reduce_slabs<64>(a, n, s);
+}
+
+template <class MF>
+static int run(const WgradPlan& pl, const WgradArgs& a, hipStream_t s)
+{
+    int rc = SBG_OK;
+    if (pl.family == WG_THIN)
+        rc = pl.bca == 1 ? (pl.bcb == 1 ? thin<MF, 1, 1>(pl, a, s) : thin<MF, 1, 2>(pl, a, s)) : (pl.bcb == 1 ? thin<MF, 2, 1>(pl, a, s) : thin<MF, 2, 2>(pl, a, s));
+    else if (pl.family == WG_ROWS)
+        rc = a.stride == 1 ? (pl.bca == 64 ? rows<MF, 1, 64>(pl, a, s) : rows<MF, 1, 128>(pl, a, s)) : (pl.bca == 64 ? rows<MF, 2, 64>(pl, a, s) : rows<MF, 2, 128>(pl, a, s));
+    else if (pl.family == WG_BIG)
+        rc = launch<conv_wgrad_kernel<MF, 128, 128, 1>>(pl, a, s);
+    else
+        for (int t0 = 0; t0 < a.ntaps && rc == SBG_OK; t0 += 9) {      // taps in groups of 9 accumulator sets
+            WgradArgs g = a;
+            g.tap0 = t0; g.ntaps = (a.ntaps - t0 < 9) ? a.ntaps - t0 : 9;
+            for (int t = 0; t < g.ntaps; t++) { g.tap_dy[t] = a.tap_dy[t0 + t]; g.tap_dx[t] = a.tap_dx[t0 + t]; }
+            rc = launch<conv_wgrad_kernel<MF, 64, 64, 9>>(pl, g, s);
+        }
+    return rc != SBG_OK || pl.nsplit == 1 ? rc : reduce_slabs(a, s);
 }
 
 } // namespace
 
 extern "C" int64_t sbg_conv2d_wgrad_workspace(const sbg_wgrad_params* q)
 {
-    WgradArgs a;
-    if (fill_args(q, a) != SBG_OK) return -1;
-    if (a.nsplit <= 1) return 0;
-    return (int64_t)a.nsplit * a.ntaps_total * a.Ca * a.Cb * (int64_t)sizeof(float);
+    WgradPlan pl; WgradArgs a;
+    if (fill_args(q, pl, a) != SBG_OK) return -1;
+    if (pl.nsplit <= 1) return 0;
+    return (int64_t)pl.nsplit * q->ntaps * q->Ca * q->Cb * (int64_t)sizeof(float);
 }
 
 extern "C" int sbg_conv2d_wgrad(const sbg_wgrad_params* q, sbg_stream_t stream)
 {
-    WgradArgs a;
-    int rc = fill_args(q, a);
+    WgradPlan pl; WgradArgs a;
+    const int rc = fill_args(q, pl, a);
     if (rc != SBG_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const int64_t out_n = (int64_t)a.ntaps_total * a.Ca * a.Cb;
-    if (a.P == 0) {
-        if (!a.accumulate) { if (hipMemsetAsync(a.out, 0, out_n * sizeof(float), s) != hipSuccess) return sbg_fail(SBG_ERR_LAUNCH, "conv2d_wgrad: memset failed"); }
+    if (pl.family == WG_EMPTY) {                         // no pixels: the sum is zero
+        if (!a.accumulate && hipMemsetAsync(a.out, 0, (size_t)a.ntaps_total * a.Ca * a.Cb * sizeof(float), s) != hipSuccess)
+            return sbg_fail(SBG_ERR_LAUNCH, "conv2d_wgrad: memset failed");
         return SBG_OK;
     }
-    SBG_CHECK(a.nsplit == 1 || a.ws != nullptr, "conv2d_wgrad: workspace required (%d pixel splits)", a.nsplit);
-    const bool bf = (q->dtype == SBG_BF16);
-    const ThinPlan tp = thin_plan(q);
-    if (tp.ok) {
-        const int ta = (a.Ca + 15) / 16, tb = (a.Cb + 15) / 16;
-        const int lds = 4 * tp.wave_lds;
-        SbgProfScope prof(s, SBG_K_CONV_WGRAD, 2.0 * (double)a.P * a.Ca * (double)a.Cb * a.ntaps,
-                          2.0 * (double)a.P * a.Ca + 2.0 * (double)a.N * a.BH * a.BW * a.Cb + 4.0 * a.ntaps * (double)a.Ca * a.Cb * a.nsplit,
-                          {(int)(a.P > INT32_MAX ? INT32_MAX : a.P), a.Ca, a.Cb, a.ntaps, a.stride, a.nsplit, 3000000 + ta * 10 + tb});
-#define SBG_THIN_LAUNCH(MFT, A_, B_) do { auto kern = conv_wgrad_thin_kernel<MFT, A_, B_>; \
-        if (lds > 64 * 1024 && !SBG_RAISE_LDS_ONCE(kern, lds)) return sbg_fail(SBG_ERR_LAUNCH, "conv2d_wgrad: cannot raise the dynamic LDS limit to %d bytes", lds); \
-        SBG_LAUNCH(kern, dim3((unsigned)tp.nwg), dim3(256), lds, s, a, tp.dymin, tp.dxmin, tp.RY, tp.PCOLS, tp.wave_lds); } while (0)
-        if (bf) { if (ta == 1 && tb == 1) SBG_THIN_LAUNCH(bf16_mfma, 1, 1); else if (ta == 2 && tb == 1) SBG_THIN_LAUNCH(bf16_mfma, 2, 1);
-                  else if (ta == 1) SBG_THIN_LAUNCH(bf16_mfma, 1, 2); else SBG_THIN_LAUNCH(bf16_mfma, 2, 2); }
-        else    { if (ta == 1 && tb == 1) SBG_THIN_LAUNCH(f16_mfma, 1, 1); else if (ta == 2 && tb == 1) SBG_THIN_LAUNCH(f16_mfma, 2, 1);
-                  else if (ta == 1) SBG_THIN_LAUNCH(f16_mfma, 1, 2); else SBG_THIN_LAUNCH(f16_mfma, 2, 2); }
-#undef SBG_THIN_LAUNCH
-        SBG_HIP_LAUNCH_CHECK();
-    } else if (rows_kernel_ok(q, a)) {
-        const unsigned ab = (unsigned)(2 * ((int64_t)(q->N - 1) * q->as_n + (int64_t)(q->PH - 1) * q->as_h + (int64_t)(q->PW - 1) * q->as_w + q->Ca));
-        const unsigned bb = (unsigned)(2 * ((int64_t)(q->N - 1) * q->bs_n + (int64_t)(q->BH - 1) * q->bs_h + (int64_t)(q->BW - 1) * q->bs_w + q->Cb));
-        const int bca = rows_bca(a);
-        const int s_ = q->stride;
-        // stage = a pieces + 3 x patch pieces, 1 KiB each; one more KiB behind the stages takes the spare pieces
-        auto stage_kib = [](int S, int BCA) { const int ppr = (S * 31 + 3 + 7) / 8; return BCA / 16 + 3 * ppr; };
-        // Depth of the L2 -> LDS pipeline.  The stream is latency bound (ablation: the loads alone take 350 us on the 128-channel 256^2 layer whatever
-        // the tile, with 46 or 76 KB in flight per CU: ~1.3 us per round trip), so the kernel wants as many chunks in flight as LDS holds.
-        const int lds = (rows_nstage(s_, bca) * stage_kib(s_, bca) + 1) * 1024;
-        SbgProfScope prof(s, SBG_K_CONV_WGRAD, 2.0 * (double)a.P * a.Ca * (double)a.Cb * a.ntaps,
-                          2.0 * (double)a.P * a.Ca + 2.0 * (double)a.N * a.BH * a.BW * a.Cb + 4.0 * a.ntaps * (double)a.Ca * a.Cb * (a.nsplit > 1 ? a.nsplit : 1),
-                          {(int)(a.P > INT32_MAX ? INT32_MAX : a.P), a.Ca, a.Cb, a.ntaps, a.stride, a.nsplit, 1000000 + bca * 1000 + 64});      // 1xxxxxx = rows kernel (profiles/summarize.py joins the launch log with the kernel trace on this)
-        const dim3 grid(wgrad_grid(a));
-#define SBG_ROWS_LAUNCH(MFT, SS, BB) do { auto kern = conv_wgrad_rows_kernel<MFT, SS, BB, rows_nstage(SS, BB)>; \
-        if (lds > 64 * 1024 && !SBG_RAISE_LDS_ONCE(kern, lds)) return sbg_fail(SBG_ERR_LAUNCH, "conv2d_wgrad: cannot raise the dynamic LDS limit to %d bytes", lds); \
-        SBG_LAUNCH(kern, grid, dim3(512), lds, s, a, ab, bb); } while (0)
-        if (s_ == 1 && bca == 64)       { if (bf) SBG_ROWS_LAUNCH(bf16_mfma, 1, 64);  else SBG_ROWS_LAUNCH(f16_mfma, 1, 64); }
-        else if (s_ == 1)               { if (bf) SBG_ROWS_LAUNCH(bf16_mfma, 1, 128); else SBG_ROWS_LAUNCH(f16_mfma, 1, 128); }
-        else if (bca == 64)             { if (bf) SBG_ROWS_LAUNCH(bf16_mfma, 2, 64);  else SBG_ROWS_LAUNCH(f16_mfma, 2, 64); }
-        else                            { if (bf) SBG_ROWS_LAUNCH(bf16_mfma, 2, 128); else SBG_ROWS_LAUNCH(f16_mfma, 2, 128); }
-#undef SBG_ROWS_LAUNCH
-        SBG_HIP_LAUNCH_CHECK();
-    } else if (use_big_tile(a.ntaps)) {
-        rc = bf ? launch_wgrad<bf16_mfma, 128, 128, 1>(a, s) : launch_wgrad<f16_mfma, 128, 128, 1>(a, s);
-        if (rc != SBG_OK) return rc;
-    } else {
-        // taps in groups of 9 accumulator sets
-        const int total = a.ntaps;
-        for (int t0 = 0; t0 < total; t0 += 9) {
-            WgradArgs g = a;
-            g.tap0 = t0; g.ntaps = (total - t0 < 9) ? total - t0 : 9;
-            for (int t = 0; t < g.ntaps; t++) { g.tap_dy[t] = a.tap_dy[t0 + t]; g.tap_dx[t] = a.tap_dx[t0 + t]; }
-            rc = bf ? launch_wgrad<bf16_mfma, 64, 64, 9>(g, s) : launch_wgrad<f16_mfma, 64, 64, 9>(g, s);
-            if (rc != SBG_OK) return rc;
-        }
-    }
-    if (a.nsplit > 1) {
-        SbgProfScope prof(s, SBG_K_WGRAD_REDUCE, 0.0, 4.0 * out_n * (a.nsplit + 1), {(int)out_n, a.nsplit});
-        if (out_n >= (1 << 18) || a.nsplit < 16)      // plenty of elements: one lane each, coalesced across lanes
-            SBG_LAUNCH(wgrad_reduce_kernel<1>, dim3(sbg_stream_grid(out_n, 256)), dim3(256), 0, s, a.ws, a.out, out_n, a.nsplit, a.accumulate);
-        else if (out_n >= (1 << 14))
-            SBG_LAUNCH(wgrad_reduce_kernel<4>, dim3(sbg_stream_grid(out_n * 4, 256)), dim3(256), 0, s, a.ws, a.out, out_n, a.nsplit, a.accumulate);
-        else
-            SBG_LAUNCH(wgrad_reduce_kernel<64>, dim3(sbg_stream_grid(out_n * 64, 256)), dim3(256), 0, s, a.ws, a.out, out_n, a.nsplit, a.accumulate);
-        SBG_HIP_LAUNCH_CHECK();
-    }
-    return SBG_OK;
+    SBG_CHECK(pl.nsplit == 1 || a.ws != nullptr, "conv2d_wgrad: workspace required (%d pixel splits)", pl.nsplit);
+    return q->dtype == SBG_BF16 ? run<bf16_mfma>(pl, a, s) : run<f16_mfma>(pl, a, s);
 }

@@ -175,6 +175,28 @@ def test_wgrad_support_probes(dev, case):
         _conv_case(dev, case, seed=100 + i, dy_region=reg)
 
 
+def test_wgrad_empty_batch(dev):
+    """sbg_conv2d_wgrad over no images (N = 0): the sum is empty, so `out` becomes zeros -- or stays as it is when accumulating -- the status
+    is 0 and no weight-gradient kernel is launched"""
+    lib = _lib.load()
+    a = torch.zeros(64, dtype=torch.bfloat16, device=dev)          # never read; the entry point wants non-null 16-byte aligned operands
+    p = _lib.WgradParams()
+    p.a, p.b, p.workspace, p.dtype = a.data_ptr(), a.data_ptr(), None, _lib.SBG_BF16
+    p.N, p.PH, p.PW, p.Ca, p.BH, p.BW, p.Cb = 0, 4, 4, 8, 4, 4, 8
+    p.as_n, p.as_h, p.as_w = p.bs_n, p.bs_h, p.bs_w = 128, 32, 8
+    p.stride, p.ntaps = 1, 1
+    _lib.prof_enable(True); _lib.prof_fetch()
+    for accumulate in (0, 1):
+        out = torch.ones(1, 8, 8, device=dev)
+        p.out, p.accumulate = out.data_ptr(), accumulate
+        assert lib.sbg_conv2d_wgrad_workspace(p) == 0
+        assert lib.sbg_conv2d_wgrad(p, _lib.stream_ptr(dev)) == 0
+        torch.cuda.synchronize()
+        assert bool((out == float(accumulate)).all()), (accumulate, out)
+    _lib.prof_enable(False)
+    assert not [r for r in _lib.prof_fetch() if r["kind"] in ("conv_wgrad", "wgrad_reduce")]
+
+
 # ---------------------------------------------------------------------------------------------------------------- accumulate / split K / generic
 
 def _packed(wt, dtype, dev):
