@@ -120,8 +120,10 @@ int sbg_upfirdn2d_separable(const float* x, const float* f, float* y, int M, int
  *   y = clamp( act( acc * oscale[n*Cout + co] + noise[n*noise_stride_n + pixel] + bias[co] ) * gain )
  * with fp32 oscale / noise / bias, pixel = oy*OW + ox of the launch grid, act in {linear, relu, lrelu}.
  * `accumulate` adds into the existing y (fp32 y only, no epilogue).
- * Kernel choice is internal (csrc/conv_k64.hip): stride-1 launches with the nine taps of a 3x3 window on a tile-aligned grid
- * take the persistent halo-staged kernel, everything else the gather (im2col-on-the-fly) kernel. */
+ * Kernel choice is internal: one host-side plan per call (csrc/conv_igemm.hip: conv_plan).  Precedence: the thin streaming kernel (few
+ * channels) -> for phased calls the one-pass up2 kernel plus its border, the multi-phase gather, or one launch per phase -> the K-step-64
+ * kernels (halo-staged 3x3, 64x256 / 128x128 tiles, persistent gather, 256x256, 128x256), with the K split -> the generic kernel for operands
+ * of 2 GiB or more and negative strides.  sbg_conv2d_igemm_plan() prints the plan of a block without touching a device. */
 #define SBG_MAX_TAPS 16
 typedef struct sbg_conv_params {
     const void* x; const void* w; void* y;
@@ -141,16 +143,27 @@ typedef struct sbg_conv_params {
      * output tiles to fill the chip (the 4x4 / 8x8 blocks): partial fp32 results go to `workspace`
      * (>= sbg_conv2d_igemm_workspace() bytes) and a second kernel sums them in a fixed order into y (bitwise reproducible).
      * Needs a dense channel-minor y; a fused epilogue and a 16-bit output are applied by that second kernel (then without `accumulate`,
-     * Cout % 8 == 0); ksplit <= 1 or workspace == NULL = off. */
+     * Cout % 8 == 0, y 16-byte aligned).  Whether and how far to split is the library's decision (fewer than 128 output tiles of 128 x 128,
+     * at least 16 K-steps of 64 channels, Cout > 64: about 256 workgroups of at least four K-steps): ksplit 0 = the library chooses, 1 = never,
+     * k > 1 = at most k; workspace == NULL = no split.  sbg_conv2d_igemm_workspace() returns the bytes of the split sbg_conv2d_igemm() will
+     * use for the block when given a workspace (0 = none, -1 = a refused block). */
     void* workspace; int ksplit;
     /* Optional phases: nphase in 2..4 makes ONE launch compute several output sub-grids of the same input -- the s x s phases of a
      * stride-s transposed convolution, whose tiles then share the input through L2 instead of streaming it from HBM once per phase.
      * Phase i uses the next ph_ntaps[i] taps of the tap list (sum <= ntaps), the output grid ph_oh[i] x ph_ow[i] (instead of OH x OW)
-     * and writes at y + ph_yoff[i] elements with the common ys_* strides.  nphase <= 1 = off.  No fused epilogue / split with phases. */
+     * and writes at y + ph_yoff[i] elements with the common ys_* strides.  nphase <= 1 = off.  No fused epilogue with phases, and they never split. */
     int nphase; int ph_ntaps[4], ph_oh[4], ph_ow[4]; int64_t ph_yoff[4];
 } sbg_conv_params;
 int64_t sbg_conv2d_igemm_workspace(const sbg_conv_params* p);
 int     sbg_conv2d_igemm(const sbg_conv_params* p, sbg_stream_t stream);
+/* The plan of a call, host only: one record per kernel launch sbg_conv2d_igemm(p) would make, in order (at most five; the slab reduction of a
+ * split call is not one), as many as fit `max`; returns their number, or -1 for a refused block (sbg_last_error).  dims / flops / bytes are
+ * what the launch log records (dims[6] = the code of the kernel and tile). */
+typedef struct sbg_conv_launch_info {
+    int dims[7]; double flops, bytes;
+    int64_t grid_x; int grid_y, block, lds;
+} sbg_conv_launch_info;
+int     sbg_conv2d_igemm_plan(const sbg_conv_params* p, sbg_conv_launch_info* out, int max);
 
 
 /* ------------------------------------------------------------------------------------------

@@ -62,6 +62,12 @@ class ConvParams(ctypes.Structure):
     ]
 
 
+class ConvLaunchInfo(ctypes.Structure):
+    """sbg_conv_launch_info: one planned kernel launch of sbg_conv2d_igemm (sbg_conv2d_igemm_plan)"""
+    _fields_ = [("dims", ctypes.c_int * 7), ("flops", ctypes.c_double), ("bytes", ctypes.c_double),
+                ("grid_x", ctypes.c_int64), ("grid_y", ctypes.c_int), ("block", ctypes.c_int), ("lds", ctypes.c_int)]
+
+
 class WgradParams(ctypes.Structure):
     _fields_ = [
         ("a", ctypes.c_void_p), ("b", ctypes.c_void_p), ("out", ctypes.c_void_p), ("workspace", ctypes.c_void_p),
@@ -140,6 +146,7 @@ SYMBOLS = [
     ("sbg_upfirdn2d_separable", _c.c_int, [_c.c_void_p] * 3 + [_c.c_int] * 11 + [_c.c_float, _c.c_void_p]),
     ("sbg_conv2d_igemm_workspace", _c.c_int64, [_c.POINTER(ConvParams)]),
     ("sbg_conv2d_igemm", _c.c_int, [_c.POINTER(ConvParams), _c.c_void_p]),
+    ("sbg_conv2d_igemm_plan", _c.c_int, [_c.POINTER(ConvParams), _c.POINTER(ConvLaunchInfo), _c.c_int]),
     ("sbg_conv2d_wgrad_workspace", _c.c_int64, [_c.POINTER(WgradParams)]),
     ("sbg_conv2d_wgrad", _c.c_int, [_c.POINTER(WgradParams), _c.c_void_p]),
     ("sbg_scale_nc", _c.c_int, [_c.c_void_p] * 4 + [_c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int64, _c.c_int64, _c.c_void_p]),

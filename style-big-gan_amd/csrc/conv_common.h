@@ -1,7 +1,8 @@
 // conv_common.h -- what the convolution kernels (conv_k64.hip, conv_up2.hip, conv_igemm.hip, conv_thin.hip, conv_wgrad.hip) share on the
 // host side: the LDS-DMA sentinel, the MFMA wrappers, the one launch function launch_as (these three are all conv_wgrad.hip takes: it has
-// its own argument block and byte model), the kernel argument block ConvArgs, the forward launch layer (conv_is_plain, conv_prof_bytes,
-// conv_launch) and the entry points of the per-file dispatchers.  The device-side pieces are in conv_device.h.
+// its own argument block and byte model), the kernel argument block ConvArgs, the forward launch layer (conv_is_plain, the planned launch
+// ConvLaunch / ConvPlan, the profiler model conv_prof, conv_launch) and the per-file fit / launch functions the plan of conv_igemm.hip calls.
+// The device-side pieces are in conv_device.h.
 #pragma once
 #include "sbg_common.h"
 #include <cstdlib>
@@ -61,13 +62,6 @@ static inline bool conv_is_plain(const sbg_conv_params& q)
     return (q.act == 0 || q.act == SBG_ACT_LINEAR) && (q.gain == 1.f || q.gain == 0.f) && q.clamp < 0.f && !q.bias && !q.noise && !q.oscale;
 }
 
-// bytes a launch moves, as the profiler counts them: the input once, the weights once, `outpix` output pixels (read back when accumulating)
-static inline double conv_prof_bytes(const ConvArgs& a, double outpix)
-{
-    const double ys = a.ydtype == SBG_F32 ? 4.0 : 2.0;
-    return 2.0 * a.N * a.IH * a.IW * (double)a.Cin + 2.0 * a.ntaps * a.Cout * (double)a.Cin + ys * outpix * (double)a.Cout * (a.accumulate ? 2 : 1);
-}
-
 // One launch of a kernel of the family: grid bound, dynamic-LDS limit (raised once per kernel), profiler scope, launch, error check.
 // kind = the profiler's kernel kind, who = the entry point named in the error texts.
 // dims = the profiler's shape key; its last entry is the code that names the kernel (bench.py, profiles/summarize.py, tests read it).
@@ -83,25 +77,76 @@ static int launch_as(int kind, const char* who, int64_t nblk, unsigned grid_y, u
     SBG_HIP_LAUNCH_CHECK();
     return SBG_OK;
 }
-// the forward / data-gradient convolutions (conv_wgrad.hip calls launch_as with its own kinds)
-template <auto Kern, class... Args>
-static int conv_launch(int64_t nblk, unsigned grid_y, unsigned block, int lds, hipStream_t stream, double flops, double bytes,
-                       std::initializer_list<int> dims, const Args&... args)
+
+// ---- the forward / data-gradient launch plan (conv_wgrad.hip has its own) ------------------------------------------------------------
+// One kernel launch as conv_plan (conv_igemm.hip) decided it: the kernel family and tile, the launch geometry, the kernel's argument block and
+// the profiler's record.  The per-file *_fit functions fill it (pure host arithmetic), the per-file *_launch functions launch it as it stands.
+enum ConvFamily { CONV_THIN, CONV_UP2, CONV_GATHER, CONV_HALO, CONV_K64, CONV_GENERIC };
+struct ConvLaunch {
+    ConvFamily family;
+    int bc, bp;                                  // tile: BC x BP (k64, generic), TH x TW (halo), 16-channel fragments x 1 (thin)
+    int64_t grid_x; unsigned grid_y, block; int lds;
+    ConvArgs a;
+    unsigned x_bytes, w_bytes;                   // operand extents, for the buffer descriptors of the LDS-DMA kernels
+    int pitch;                                   // thin: LDS row pitch of the weights
+    int tiles_y, tiles_x, dymin, dxmin;          // up2: 8 x 32 tiles of the common phase grid, origin of the 2 x 2 tap window
+    double flops, bytes; int dims[7];            // the profiler's figures and shape key
+};
+// A call = up to five launches (up2 + four border rectangles, or four phases), then the slab reduction when K was split.
+struct ConvPlan {
+    int nlaunch; ConvLaunch launch[5];
+    ConvArgs call;                               // the call as the caller described it (what the slab reduction finishes)
+    int ksplit; bool reduce_epi;                 // K split of launch[0] (1 = none); the reduction applies the fused epilogue / output cast
+    int64_t workspace_bytes;
+};
+
+// The profiler's model of a forward launch, every family: 2 flops per multiply-add (macs = output pixels x taps, per channel pair); bytes = the
+// input once, the weights once, `outpix` output pixels (read back when accumulating); shape key {pixels, Cout, Cin, taps, stride, rows, kernel code}.
+static inline void conv_prof(ConvLaunch& l, double macs, double outpix, int ntaps, int stride, int rows, int code)
 {
-    return launch_as<Kern>(SBG_K_CONV_IGEMM, "conv2d_igemm", nblk, grid_y, block, lds, stream, flops, bytes, dims, args...);
+    const ConvArgs& a = l.a;
+    const double ys = a.ydtype == SBG_F32 ? 4.0 : 2.0;
+    l.flops = 2.0 * macs * a.Cout * (double)a.Cin;
+    l.bytes = 2.0 * a.N * a.IH * a.IW * (double)a.Cin + 2.0 * ntaps * a.Cout * (double)a.Cin + ys * outpix * (double)a.Cout * (a.accumulate ? 2 : 1);
+    const int dims[7] = {(int)outpix, a.Cout, a.Cin, ntaps, stride, rows, code};
+    for (int i = 0; i < 7; i++) l.dims[i] = dims[i];
+}
+// ... of a launch whose phases (or whose one grid) each run their own taps
+static inline void conv_prof_phases(ConvLaunch& l, int code)
+{
+    const ConvArgs& a = l.a;
+    double macs = (double)a.P * a.ntaps, outpix = a.P;
+    if (a.nphase > 1) {
+        macs = outpix = 0.0;
+        for (int i = 0; i < a.nphase; i++) { macs += (double)a.ph_P[i] * a.ph_ntaps[i]; outpix += a.ph_P[i]; }
+    }
+    conv_prof(l, macs, outpix, a.ntaps, a.stride, a.OH, code);
+}
+
+template <auto Kern, class... Extra>
+static int conv_launch(const ConvLaunch& l, hipStream_t stream, const Extra&... extra)
+{
+    const int* d = l.dims;
+    return launch_as<Kern>(SBG_K_CONV_IGEMM, "conv2d_igemm", l.grid_x, l.grid_y, l.block, l.lds, stream, l.flops, l.bytes,
+                           {d[0], d[1], d[2], d[3], d[4], d[5], d[6]}, l.a, extra...);
 }
 
 } // namespace sbgconv
 
-// conv_k64.hip: K-step-64 LDS-DMA kernels (gather and halo-staged).  Returns SBG_OK / an error, or -1 when the launch does not
-// fit these kernels (the caller then uses the kernels of conv_igemm.hip).
-int sbg_conv_k64_dispatch(sbgconv::ConvArgs& a, bool bf16, int64_t x_bytes, int64_t w_bytes, void* workspace, int ksplit, hipStream_t stream);
-// conv_thin.hip: few-channel convolutions (Cin, Cout <= 64, one of them <= 32) as a streaming kernel with the reduction axis packed
-// over (tap, channel).  Returns SBG_OK / an error, or -1 when the launch is not a thin one.
-int sbg_conv_thin_dispatch(sbgconv::ConvArgs& a, bool bf16, hipStream_t stream);
-// conv_up2.hip: puts the taps of a 4 / 2 / 2 / 1-tap stride-2 transposed convolution in canonical order (inside every phase by (dy, dx)), all of them
-// or none; false when the launch is not of that form.  Called before any kernel is offered the launch, so every kernel sums a phase in one order.
-bool sbg_conv_up2_canonical_taps(sbgconv::ConvArgs& a, int64_t x_bytes, int64_t w_bytes);
-// conv_up2.hip: all four phases of a stride-2 3x3 transposed convolution from one staged input halo.  Returns SBG_OK / an error, or -1 when the
-// launch is not of that form; on SBG_OK `border` describes the remaining last row / column rectangles as an ordinary phased launch.
-int sbg_conv_up2_dispatch(sbgconv::ConvArgs& a, bool bf16, int64_t x_bytes, int64_t w_bytes, sbg_conv_params* border, const sbg_conv_params* q, hipStream_t stream);
+// Per file: *_fit = does this launch (l.a, l.x_bytes, l.w_bytes set by the plan) fit the file's kernels, and with what parameters -- no HIP call;
+// *_launch = launch a leaf that *_fit filled.
+// conv_thin.hip: few-channel convolutions (Cin, Cout <= 64, one of them <= 32), single or phased; false when the launch is not a thin one.
+bool sbg_conv_thin_fit(sbgconv::ConvLaunch& l);
+int  sbg_conv_thin_launch(const sbgconv::ConvLaunch& l, bool bf16, hipStream_t stream);
+// conv_up2.hip: all four phases of a stride-2 3x3 transposed convolution from one staged input halo.  A launch of that form (4 / 2 / 2 / 1 taps in
+// one 2 x 2 window) gets its taps put in canonical order, inside every phase by (dy, dx), whichever kernel then runs it, so every kernel sums a
+// phase in one order.  UP2_FITS: the kernel covers [0, Hm) x [0, Wm) of every phase grid and `border` describes the remaining last row / column
+// rectangles as an ordinary phased call (nphase 0: none).
+enum Up2Fit { UP2_OTHER_FORM, UP2_ORDERED, UP2_FITS };
+Up2Fit sbg_conv_up2_fit(sbgconv::ConvLaunch& l, const sbg_conv_params& q, sbg_conv_params& border);
+int    sbg_conv_up2_launch(const sbgconv::ConvLaunch& l, bool bf16, hipStream_t stream);
+// conv_k64.hip: the K-step-64 LDS-DMA kernels take every launch whose operands a buffer descriptor can address; _fit chooses the kernel and tile.
+// sbg_conv_ksplit_reduce sums the k fp32 slabs of a K-split launch into the call's y (reduce_epi: with the fused epilogue and the output cast).
+void sbg_conv_k64_fit(sbgconv::ConvLaunch& l);
+int  sbg_conv_k64_launch(const sbgconv::ConvLaunch& l, bool bf16, hipStream_t stream);
+int  sbg_conv_ksplit_reduce(const sbgconv::ConvArgs& call, const void* workspace, int ksplit, bool reduce_epi, hipStream_t stream);

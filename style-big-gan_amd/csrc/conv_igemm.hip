@@ -17,9 +17,11 @@
 // rows that are distinct mod 16 -> 16 distinct 16-B slots of the 256-B bank row: conflict-free; the staging writes put 8
 // consecutive rows of one k-group in each 8-lane store group: 128 contiguous bytes, conflict-free.
 //
-// What this file holds: the entry point sbg_conv2d_igemm, which offers every launch to the specialised kernels first (conv_thin.hip,
-// conv_up2.hip, conv_k64.hip), and the kernel described above as the generic fallback -- operands of 2 GiB or more and negative strides,
-// which the buffer descriptors of the LDS-DMA kernels cannot address.
+// What this file holds: the kernel described above, which is the generic fallback -- operands of 2 GiB or more and negative strides, which
+// the buffer descriptors of the LDS-DMA kernels cannot address -- and the host side of the family: conv_plan decides everything about a call
+// once (which kernels, tiles, grids, K split, tap order, profiler records; it asks conv_thin.hip, conv_up2.hip and conv_k64.hip whether a
+// launch fits them), and the three entry points read it: sbg_conv2d_igemm launches what it lists, sbg_conv2d_igemm_workspace returns the size of
+// the split it chose, sbg_conv2d_igemm_plan prints it.
 #include "conv_device.h"
 
 using namespace sbgconv;
@@ -197,31 +199,29 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvArgs p)
     conv_epilogue<TC, TP>(p, acc, c0, p0, wc, wp, fr, fg);
 }
 
-template <class MF, int BC, int BP, int WGC, int WGP>
-static int launch_conv(ConvArgs& a, hipStream_t stream)
+template <class MF>
+static int launch_generic(const ConvLaunch& l, hipStream_t stream)
 {
-    a.ptiles = (a.P + BP - 1) / BP;
-    a.ctiles = (a.Cout + BC - 1) / BC;
-    constexpr int lds = 2 * (4 * BC * 16 + 4 * BP * 16);
-    return conv_launch<conv_igemm_kernel<MF, BC, BP, WGC, WGP>>((int64_t)a.ptiles * a.ctiles, 1, 256, lds, stream, 2.0 * a.P * a.Cout * (double)a.Cin * a.ntaps,
-                                                                conv_prof_bytes(a, a.P), {a.P, a.Cout, a.Cin, a.ntaps, a.stride, a.OH, BC * 1000 + BP}, a);
+    if (l.bc == 64) return conv_launch<conv_igemm_kernel<MF, 64, 256, 1, 4>>(l, stream);
+    return conv_launch<conv_igemm_kernel<MF, 128, 128, 2, 2>>(l, stream);
 }
 
 // tile choice: few output channels -> pixel-heavy tile; otherwise 128 x 128.
-template <class MF>
-static int dispatch_conv(ConvArgs& a, hipStream_t stream)
+static void fit_generic(ConvLaunch& l)
 {
-    if (a.Cout <= 64)  return launch_conv<MF, 64, 256, 1, 4>(a, stream);
-    return launch_conv<MF, 128, 128, 2, 2>(a, stream);
+    ConvArgs& a = l.a;
+    l.family = CONV_GENERIC; l.bc = a.Cout <= 64 ? 64 : 128; l.bp = a.Cout <= 64 ? 256 : 128;
+    a.ptiles = (a.P + l.bp - 1) / l.bp;
+    a.ctiles = (a.Cout + l.bc - 1) / l.bc;
+    l.grid_x = (int64_t)a.ptiles * a.ctiles; l.grid_y = 1; l.block = 256; l.lds = 2 * (4 * l.bc * 16 + 4 * l.bp * 16);
+    conv_prof_phases(l, l.bc * 1000 + l.bp);
 }
-
-} // namespace
 
 // Smallest tile count for which a transposed convolution runs as ONE multi-phase launch.  256 -> 16: the 4x4 .. 32x32 up-sampling layers
 // as one launch instead of four latency-bound ones (-1.4 ms per step).
-static constexpr int kPhaseMinTiles = 16;
+constexpr int kPhaseMinTiles = 16;
 
-extern "C" int sbg_conv2d_igemm(const sbg_conv_params* q, sbg_stream_t stream)
+int conv_validate(const sbg_conv_params* q)
 {
     SBG_CHECK(q && q->x && q->w && q->y, "conv2d_igemm: null pointer");
     SBG_CHECK(q->xdtype == SBG_BF16 || q->xdtype == SBG_F16, "conv2d_igemm: x/w must be bf16 or f16 (fp32 inputs are split by the host)");
@@ -231,88 +231,177 @@ extern "C" int sbg_conv2d_igemm(const sbg_conv_params* q, sbg_stream_t stream)
     SBG_CHECK(q->ntaps >= 1 && q->ntaps <= SBG_MAX_TAPS, "conv2d_igemm: 1..%d taps", SBG_MAX_TAPS);
     SBG_CHECK(q->stride >= 1, "conv2d_igemm: stride must be >= 1");
     SBG_CHECK(!q->accumulate || q->ydtype == SBG_F32, "conv2d_igemm: accumulate needs an fp32 output");
-    SBG_CHECK(q->ksplit <= 1 || q->workspace != nullptr, "conv2d_igemm: ksplit > 1 needs a workspace");
+    SBG_CHECK(q->ksplit >= 0, "conv2d_igemm: ksplit must be 0 (the library chooses), 1 (never) or a cap");
     SBG_CHECK(q->act == 0 || q->act == SBG_ACT_LINEAR || q->act == SBG_ACT_RELU || q->act == SBG_ACT_LRELU, "conv2d_igemm: fused activation must be linear, relu or lrelu");
     SBG_CHECK(sbg_aligned16(q->x) && sbg_aligned16(q->w), "conv2d_igemm: x and w must be 16-byte aligned");
     SBG_CHECK((q->xs_n % 8) == 0 && (q->xs_h % 8) == 0 && (q->xs_w % 8) == 0 && (q->ws_slab % 8) == 0 && (q->ws_co % 8) == 0,
               "conv2d_igemm: pixel / row strides must be multiples of 8 elements");
     const int64_t P = (int64_t)q->N * q->OH * q->OW;
     SBG_CHECK(P <= INT32_MAX, "conv2d_igemm: too many output pixels");
-    if (P == 0) return SBG_OK;
-
-    ConvArgs a;
-    a.x = (const unsigned short*)q->x; a.w = (const unsigned short*)q->w; a.y = q->y; a.oscale = q->oscale;
-    a.bias = q->bias; a.noise = q->noise; a.noise_sn = q->noise_stride_n;
-    a.act = q->act; a.alpha = q->alpha; a.gain = (q->act == 0 && q->gain == 0.f) ? 1.f : q->gain; a.clamp = (q->act == 0 && q->clamp == 0.f && q->gain == 0.f) ? -1.f : q->clamp;
-    a.ydtype = q->ydtype;
-    a.N = q->N; a.IH = q->IH; a.IW = q->IW; a.Cin = q->Cin; a.Cout = q->Cout; a.OH = q->OH; a.OW = q->OW;
-    a.xs_n = q->xs_n; a.xs_h = q->xs_h; a.xs_w = q->xs_w; a.ys_n = q->ys_n; a.ys_h = q->ys_h; a.ys_w = q->ys_w;
-    a.ws_slab = q->ws_slab; a.ws_co = q->ws_co;
-    a.stride = q->stride; a.ntaps = q->ntaps;
-    for (int t = 0; t < SBG_MAX_TAPS; t++) { a.tap_dy[t] = q->tap_dy[t]; a.tap_dx[t] = q->tap_dx[t]; a.tap_slab[t] = q->tap_slab[t]; }
-    a.accumulate = q->accumulate;
-    a.P = (int)P; a.ptiles = a.ctiles = 0; a.lds_params = 0; a.ksplit = 1; a.y_split_stride = 0;
-    a.nphase = 1; a.ph_rot_div = 1;
-    for (int i = 0; i < 4; i++) { a.ph_tap0[i] = 0; a.ph_ntaps[i] = 0; a.ph_OH[i] = 0; a.ph_OW[i] = 0; a.ph_P[i] = 0; a.ph_yoff[i] = 0; }
-    hipStream_t s = (hipStream_t)stream;
-    int maxslab = 0;
-    for (int t = 0; t < q->ntaps; t++) { SBG_CHECK(q->tap_slab[t] >= 0, "conv2d_igemm: negative weight slab"); if (q->tap_slab[t] > maxslab) maxslab = q->tap_slab[t]; }
-    const int64_t x_bytes = 2 * ((int64_t)(q->N - 1) * q->xs_n + (int64_t)(q->IH - 1) * q->xs_h + (int64_t)(q->IW - 1) * q->xs_w + q->Cin);
-    const int64_t w_bytes = 2 * ((int64_t)maxslab * q->ws_slab + (int64_t)(q->Cout - 1) * q->ws_co + q->Cin);
-    const bool fwd_strides = q->xs_n >= 0 && q->xs_h >= 0 && q->xs_w >= 0 && q->ws_slab >= 0 && q->ws_co >= 0;
+    if (P == 0) return SBG_OK;                           // nothing to do (and nothing planned)
+    for (int t = 0; t < q->ntaps; t++) SBG_CHECK(q->tap_slab[t] >= 0, "conv2d_igemm: negative weight slab");
     if (q->nphase > 1) {
-        // phases: one persistent launch when the shape fits that kernel, otherwise one launch per phase through this same entry point
         SBG_CHECK(q->nphase <= 4, "conv2d_igemm: at most 4 phases");
         SBG_CHECK(conv_is_plain(*q) && (q->ksplit <= 1), "conv2d_igemm: phases exclude the fused epilogue and the K split");
-        int t0 = 0; int64_t ptot = 0;
+        int t0 = 0;
         for (int i = 0; i < q->nphase; i++) {
             SBG_CHECK(q->ph_ntaps[i] >= 1 && q->ph_oh[i] >= 1 && q->ph_ow[i] >= 1, "conv2d_igemm: bad phase %d", i);
-            a.ph_tap0[i] = t0; a.ph_ntaps[i] = q->ph_ntaps[i]; a.ph_OH[i] = q->ph_oh[i]; a.ph_OW[i] = q->ph_ow[i];
-            a.ph_P[i] = q->N * q->ph_oh[i] * q->ph_ow[i]; a.ph_yoff[i] = q->ph_yoff[i];
-            t0 += q->ph_ntaps[i]; ptot += a.ph_P[i];
+            t0 += q->ph_ntaps[i];
         }
         SBG_CHECK(t0 <= q->ntaps, "conv2d_igemm: phases use %d taps, %d given", t0, q->ntaps);
-        {   // few channels: one streaming launch over all phases (conv_thin.hip)
-            a.nphase = q->nphase;
-            const int rc = sbg_conv_thin_dispatch(a, q->xdtype == SBG_BF16, s);
-            if (rc >= 0) return rc;
-            a.nphase = 1;
-        }
-        if (fwd_strides && q->nphase == 4) {      // stride-2 3x3 transposed convolution: every phase from one staged halo (conv_up2.hip), then its border
-            a.nphase = 4;
-            if (sbg_conv_up2_canonical_taps(a, x_bytes, w_bytes)) {      // (from here on `a` lists every phase's taps by (dy, dx), whichever kernel runs)
-                sbg_conv_params border;
-                const int rc = sbg_conv_up2_dispatch(a, q->xdtype == SBG_BF16, x_bytes, w_bytes, &border, q, s);
-                if (rc > 0) return rc;
-                if (rc == SBG_OK) return border.nphase > 0 ? sbg_conv2d_igemm(&border, stream) : SBG_OK;
+    }
+    return SBG_OK;
+}
+
+// the kernel argument block of the call as the caller described it
+void conv_fill(const sbg_conv_params& q, ConvArgs& a)
+{
+    a.x = (const unsigned short*)q.x; a.w = (const unsigned short*)q.w; a.y = q.y; a.oscale = q.oscale;
+    a.bias = q.bias; a.noise = q.noise; a.noise_sn = q.noise_stride_n;
+    a.act = q.act; a.alpha = q.alpha; a.gain = (q.act == 0 && q.gain == 0.f) ? 1.f : q.gain; a.clamp = (q.act == 0 && q.clamp == 0.f && q.gain == 0.f) ? -1.f : q.clamp;
+    a.ydtype = q.ydtype;
+    a.N = q.N; a.IH = q.IH; a.IW = q.IW; a.Cin = q.Cin; a.Cout = q.Cout; a.OH = q.OH; a.OW = q.OW;
+    a.xs_n = q.xs_n; a.xs_h = q.xs_h; a.xs_w = q.xs_w; a.ys_n = q.ys_n; a.ys_h = q.ys_h; a.ys_w = q.ys_w;
+    a.ws_slab = q.ws_slab; a.ws_co = q.ws_co;
+    a.stride = q.stride; a.ntaps = q.ntaps;
+    for (int t = 0; t < SBG_MAX_TAPS; t++) { a.tap_dy[t] = q.tap_dy[t]; a.tap_dx[t] = q.tap_dx[t]; a.tap_slab[t] = q.tap_slab[t]; }
+    a.accumulate = q.accumulate;
+    a.P = q.N * q.OH * q.OW; a.ptiles = a.ctiles = 0; a.lds_params = 0; a.ksplit = 1; a.y_split_stride = 0;
+    a.nphase = q.nphase > 1 ? q.nphase : 1; a.ph_rot_div = 1;
+    for (int i = 0, t0 = 0; i < 4; i++) {
+        const bool on = q.nphase > 1 && i < q.nphase;
+        a.ph_tap0[i] = on ? t0 : 0; a.ph_ntaps[i] = on ? q.ph_ntaps[i] : 0; a.ph_OH[i] = on ? q.ph_oh[i] : 0; a.ph_OW[i] = on ? q.ph_ow[i] : 0;
+        a.ph_P[i] = on ? q.N * q.ph_oh[i] * q.ph_ow[i] : 0; a.ph_yoff[i] = on ? q.ph_yoff[i] : 0;
+        if (on) t0 += q.ph_ntaps[i];
+    }
+}
+
+// The K split of a single launch that the K-step-64 kernels take: worth it when the output tiles alone leave most CUs idle and the reduction is
+// long (the 4x4 fp32 block: 16 tiles x 432 K-steps; the 16-bit 4x4 .. 8x8 layers: 16-64 tiles x 72).  q.ksplit: 0 = as computed here, 1 = never,
+// k = at most k.  The slabs need a dense channel-minor y; a plain fp32 sum may accumulate and have any channel count (the 513-channel data gradient
+// of the discriminator's epilogue convolution); otherwise the reduction applies the epilogue / output cast, storing 16-B vectors of 8 channels
+// (reduce_epi, which means something only when the result is > 1).
+int conv_ksplit(const sbg_conv_params& q, const ConvArgs& a, bool have_ws, bool& reduce_epi)
+{
+    const bool dense_y = a.ys_w == a.Cout && a.ys_h == (int64_t)a.OW * a.Cout && a.ys_n == (int64_t)a.OH * a.OW * a.Cout;
+    const bool simple = a.ydtype == SBG_F32 && conv_is_plain(a);
+    const bool epi_ok = !a.accumulate && (a.Cout & 7) == 0 && sbg_aligned16(a.y);
+    reduce_epi = !simple;
+    if (!have_ws || q.ksplit == 1 || a.Cout <= 64 || !dense_y || !(simple || epi_ok)) return 1;
+    const int64_t tiles = (int64_t)((a.P + 127) / 128) * ((a.Cout + 127) / 128);       // 128 x 128 output tiles
+    const int ksteps = a.ntaps * ((a.Cin + 63) >> 6);
+    if (tiles >= 128 || ksteps < 16) return 1;
+    int k = (int)((256 + tiles - 1) / tiles);           // about 256 workgroups ...
+    if (k > ksteps / 4) k = ksteps / 4;                 // ... of at least four K-steps each
+    if (q.ksplit > 1 && k > q.ksplit) k = q.ksplit;
+    return k < 2 ? 1 : k;
+}
+
+int push(ConvPlan& pl, const ConvLaunch& l)
+{
+    if (pl.nlaunch >= 5) return sbg_fail(SBG_ERR_INVALID, "conv2d_igemm: more than five launches");
+    pl.launch[pl.nlaunch++] = l;
+    return SBG_OK;
+}
+
+// Appends the launches of one (validated) call to the plan.  Pure host arithmetic.  Precedence: thin -> [phased: up2 (+ its border, planned as a
+// call of its own) -> multi-phase gather -> every phase as a call of its own] -> K-step-64 kernels (sbg_conv_k64_fit has the tile order), with
+// the K split -> generic.  have_ws: the caller has (or, for the size query, will have) a workspace for the K split.
+int conv_plan_add(const sbg_conv_params& q, bool have_ws, ConvPlan& pl)
+{
+    if ((int64_t)q.N * q.OH * q.OW == 0) return SBG_OK;
+    ConvLaunch l = {};
+    ConvArgs& a = l.a;
+    conv_fill(q, a);
+    if (pl.nlaunch == 0) pl.call = a;
+    int maxslab = 0;
+    for (int t = 0; t < q.ntaps; t++) if (q.tap_slab[t] > maxslab) maxslab = q.tap_slab[t];
+    const int64_t x_bytes = 2 * ((int64_t)(q.N - 1) * q.xs_n + (int64_t)(q.IH - 1) * q.xs_h + (int64_t)(q.IW - 1) * q.xs_w + q.Cin);
+    const int64_t w_bytes = 2 * ((int64_t)maxslab * q.ws_slab + (int64_t)(q.Cout - 1) * q.ws_co + q.Cin);
+    const bool fwd_strides = q.xs_n >= 0 && q.xs_h >= 0 && q.xs_w >= 0 && q.ws_slab >= 0 && q.ws_co >= 0;
+    // LDS-DMA addressable: what the buffer descriptors of conv_up2.hip / conv_k64.hip can reach
+    const bool dma = fwd_strides && x_bytes < (int64_t)SBG_OOB_OFFSET && w_bytes < (int64_t)SBG_OOB_OFFSET;
+    l.x_bytes = (unsigned)x_bytes; l.w_bytes = (unsigned)w_bytes;
+    if (q.nphase > 1) {
+        if (fwd_strides && sbg_conv_thin_fit(l)) return push(pl, l);      // few channels: one streaming launch over all phases
+        if (dma && q.nphase == 4) {      // stride-2 3x3 transposed convolution: every phase from one staged halo, then its border
+            sbg_conv_params border;
+            if (sbg_conv_up2_fit(l, q, border) == UP2_FITS) {
+                const int rc = push(pl, l);
+                return rc != SBG_OK || border.nphase == 0 ? rc : conv_plan_add(border, false, pl);
             }
-            a.nphase = 1;
         }
-        const int64_t tiles = ((ptot / q->nphase + 255) / 256) * q->nphase * ((q->Cout + 127) / 128);
-        if (fwd_strides && q->Cout > 64 && tiles >= kPhaseMinTiles && x_bytes < (int64_t)SBG_OOB_OFFSET && w_bytes < (int64_t)SBG_OOB_OFFSET) {
-            a.nphase = q->nphase;
-            const int rc = sbg_conv_k64_dispatch(a, q->xdtype == SBG_BF16, x_bytes, w_bytes, nullptr, 1, s);
-            if (rc >= 0) return rc;
-            a.nphase = 1;
-        }
-        for (int i = 0; i < q->nphase; i++) {
-            sbg_conv_params one = *q;
-            one.nphase = 0; one.OH = q->ph_oh[i]; one.OW = q->ph_ow[i]; one.ntaps = q->ph_ntaps[i];
-            one.y = (char*)q->y + q->ph_yoff[i] * (q->ydtype == SBG_F32 ? 4 : 2);
-            for (int t = 0; t < one.ntaps; t++) { one.tap_dy[t] = q->tap_dy[a.ph_tap0[i] + t]; one.tap_dx[t] = q->tap_dx[a.ph_tap0[i] + t]; one.tap_slab[t] = q->tap_slab[a.ph_tap0[i] + t]; }
-            const int rc = sbg_conv2d_igemm(&one, stream);
+        int64_t ptot = 0;
+        for (int i = 0; i < q.nphase; i++) ptot += a.ph_P[i];
+        const int64_t tiles = ((ptot / q.nphase + 255) / 256) * q.nphase * ((q.Cout + 127) / 128);
+        if (dma && q.Cout > 64 && tiles >= kPhaseMinTiles) { sbg_conv_k64_fit(l); return push(pl, l); }
+        for (int i = 0; i < q.nphase; i++) {      // too few tiles, or operands only the generic kernel reaches: one call per phase (the caller's tap order)
+            sbg_conv_params one = q;
+            one.nphase = 0; one.ksplit = 1; one.OH = q.ph_oh[i]; one.OW = q.ph_ow[i]; one.ntaps = q.ph_ntaps[i];
+            one.y = (char*)q.y + q.ph_yoff[i] * (q.ydtype == SBG_F32 ? 4 : 2);
+            for (int t = 0; t < one.ntaps; t++) { one.tap_dy[t] = q.tap_dy[a.ph_tap0[i] + t]; one.tap_dx[t] = q.tap_dx[a.ph_tap0[i] + t]; one.tap_slab[t] = q.tap_slab[a.ph_tap0[i] + t]; }
+            const int rc = conv_plan_add(one, false, pl);
             if (rc != SBG_OK) return rc;
         }
         return SBG_OK;
     }
-    if (q->ksplit <= 1) {   // few channels on both sides: the streaming kernel of conv_thin.hip
-        const int rc = sbg_conv_thin_dispatch(a, q->xdtype == SBG_BF16, s);
-        if (rc >= 0) return rc;
+    if (q.ksplit <= 1 && fwd_strides && sbg_conv_thin_fit(l)) return push(pl, l);      // few channels on both sides: the streaming kernel
+    if (!dma) { fit_generic(l); return push(pl, l); }
+    const int k = conv_ksplit(q, a, have_ws, pl.reduce_epi);
+    if (k > 1) {       // the launch writes k raw fp32 slabs into the workspace; the reduction finishes the call
+        pl.ksplit = k; pl.workspace_bytes = (int64_t)k * a.P * a.Cout * (int64_t)sizeof(float);
+        a.y = q.workspace; a.accumulate = 0; a.ksplit = k; a.y_split_stride = (int64_t)a.P * a.Cout;
+        a.ydtype = SBG_F32; a.act = SBG_ACT_LINEAR; a.gain = 1.f; a.clamp = -1.f; a.bias = nullptr; a.noise = nullptr; a.oscale = nullptr;
     }
-    if (fwd_strides) {    // K-step-64 kernels (conv_k64.hip) take every launch whose operands fit a 2 GiB buffer descriptor
-        const int rc = sbg_conv_k64_dispatch(a, q->xdtype == SBG_BF16, x_bytes, w_bytes, q->workspace, q->ksplit, s);
-        if (rc >= 0) return rc;
+    sbg_conv_k64_fit(l);
+    return push(pl, l);
+}
+
+int conv_plan(const sbg_conv_params* q, bool have_ws, ConvPlan& pl)
+{
+    const int rc = conv_validate(q);
+    if (rc != SBG_OK) return rc;
+    pl.nlaunch = 0; pl.ksplit = 1; pl.reduce_epi = false; pl.workspace_bytes = 0;
+    return conv_plan_add(*q, have_ws, pl);
+}
+
+} // namespace
+
+extern "C" int64_t sbg_conv2d_igemm_workspace(const sbg_conv_params* q)
+{
+    ConvPlan pl;
+    return conv_plan(q, true, pl) == SBG_OK ? pl.workspace_bytes : -1;
+}
+
+extern "C" int sbg_conv2d_igemm_plan(const sbg_conv_params* q, sbg_conv_launch_info* out, int max)
+{
+    ConvPlan pl;
+    if (conv_plan(q, q && q->workspace, pl) != SBG_OK) return -1;
+    for (int i = 0; i < pl.nlaunch && i < max && out; i++) {
+        const ConvLaunch& l = pl.launch[i];
+        for (int d = 0; d < 7; d++) out[i].dims[d] = l.dims[d];
+        out[i].flops = l.flops; out[i].bytes = l.bytes;
+        out[i].grid_x = l.grid_x; out[i].grid_y = (int)l.grid_y; out[i].block = (int)l.block; out[i].lds = l.lds;
     }
-    if (q->xdtype == SBG_BF16) return dispatch_conv<bf16_mfma>(a, s);
-    return dispatch_conv<f16_mfma>(a, s);
+    return pl.nlaunch;
+}
+
+extern "C" int sbg_conv2d_igemm(const sbg_conv_params* q, sbg_stream_t stream)
+{
+    ConvPlan pl;
+    int rc = conv_plan(q, q && q->workspace, pl);
+    if (rc != SBG_OK) return rc;
+    SBG_CHECK(q->ksplit <= 1 || q->workspace != nullptr, "conv2d_igemm: ksplit > 1 needs a workspace");
+    hipStream_t s = (hipStream_t)stream;
+    const bool bf16 = q->xdtype == SBG_BF16;
+    for (int i = 0; i < pl.nlaunch && rc == SBG_OK; i++) {
+        const ConvLaunch& l = pl.launch[i];
+        switch (l.family) {
+        case CONV_THIN:    rc = sbg_conv_thin_launch(l, bf16, s); break;
+        case CONV_UP2:     rc = sbg_conv_up2_launch(l, bf16, s); break;
+        case CONV_GENERIC: rc = bf16 ? launch_generic<bf16_mfma>(l, s) : launch_generic<f16_mfma>(l, s); break;
+        default:           rc = sbg_conv_k64_launch(l, bf16, s); break;
+        }
+    }
+    return rc != SBG_OK || pl.ksplit == 1 ? rc : sbg_conv_ksplit_reduce(pl.call, q->workspace, pl.ksplit, pl.reduce_epi, s);
 }

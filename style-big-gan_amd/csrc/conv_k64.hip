@@ -19,6 +19,10 @@
 // `buffer_load_dwordx4 ... lds` (lane -> row = lane >> 3, slot = lane & 7).  The k-slot -> slot XOR swizzle
 // slot = kslot ^ (row & 7) is applied on the SOURCE address and on the fragment reads: ds_read_b128 of 16 consecutive
 // rows is conflict-free at any row alignment (SQ_LDS_BANK_CONFLICT = 0 measured), which the shifted halo windows need.
+//
+// Host side: sbg_conv_k64_fit holds the tile precedence (halo 8x32 / 16x16, 64x256, 128x128, persistent gather, 256x256, 128x256) and fills the
+// planned launch; sbg_conv_k64_launch launches that record; sbg_conv_ksplit_reduce finishes a K-split call.  Whether a launch comes here, and
+// whether K is split, is decided by conv_plan in conv_igemm.hip.
 #include "conv_device.h"
 #include <type_traits>
 
@@ -835,10 +839,31 @@ __global__ __launch_bounds__(768, 3) void conv_gather_ld_kernel(ConvArgs p, unsi
     if (!grpY) __builtin_amdgcn_s_barrier();             // 2S
 }
 
+constexpr int kGatherLds = 3 * (128 * 128 + 256 * 128);
+constexpr int halo_lds(int TH, int TW) { return 4 * 128 * 128 + 2 * (((TH + 2) * (TW + 2) + 7) / 8) * 1024 + 2 * 3072; }
+constexpr int k64_lds(int BC, int BP, int NSTAGE) { return NSTAGE * (BC * 128 + BP * 128); }
+static_assert(kGatherLds <= 160 * 1024 && halo_lds(8, 32) <= 160 * 1024 && halo_lds(16, 16) <= 160 * 1024 && k64_lds(256, 256, 2) <= 160 * 1024
+              && k64_lds(128, 256, 3) <= 160 * 1024, "LDS budget");
+
 template <class MF>
-static int launch_gather_ld(ConvArgs& a, unsigned x_bytes, unsigned w_bytes, hipStream_t stream)
+static int launch_leaf(const ConvLaunch& l, hipStream_t stream)
 {
-    constexpr int lds = 3 * (128 * 128 + 256 * 128);
+    if (l.family == CONV_GATHER) return conv_launch<conv_gather_ld_kernel<MF>>(l, stream, l.x_bytes, l.w_bytes);
+    if (l.family == CONV_HALO)
+        return l.bc == 8 ? conv_launch<conv_halo_ld_kernel<MF, 8, 32>>(l, stream, l.x_bytes, l.w_bytes)
+                         : conv_launch<conv_halo_ld_kernel<MF, 16, 16>>(l, stream, l.x_bytes, l.w_bytes);
+    if (l.bc == 64)  return conv_launch<conv_k64_kernel<MF, 64, 256, 1, 8>>(l, stream, l.x_bytes, l.w_bytes);
+    if (l.bp == 128) return conv_launch<conv_k64_kernel<MF, 128, 128, 2, 4>>(l, stream, l.x_bytes, l.w_bytes);
+    if (l.bc == 256) return conv_launch<conv_k64_kernel<MF, 256, 256, 2, 4, 2>>(l, stream, l.x_bytes, l.w_bytes);
+    return conv_launch<conv_k64_kernel<MF, 128, 256, 2, 4>>(l, stream, l.x_bytes, l.w_bytes);
+}
+
+// persistent kernels: one workgroup per CU, each walks tiles b, b + grid, ...  (More tiles than an int counts stay as they are: the launch refuses them.)
+static int64_t persistent_grid(int64_t tiles) { return tiles <= INT32_MAX && tiles > sbg_cu_count() ? sbg_cu_count() : tiles; }
+
+static void fit_gather(ConvLaunch& l)
+{
+    ConvArgs& a = l.a;
     a.ctiles = (a.Cout + 127) / 128;
     if (a.nphase <= 1) {            // the whole launch as one phase
         a.nphase = 1; a.ph_tap0[0] = 0; a.ph_ntaps[0] = a.ntaps; a.ph_OH[0] = a.OH; a.ph_OW[0] = a.OW; a.ph_P[0] = a.P; a.ph_yoff[0] = 0;
@@ -846,22 +871,15 @@ static int launch_gather_ld(ConvArgs& a, unsigned x_bytes, unsigned w_bytes, hip
     int pmax = 0;
     for (int i = 0; i < a.nphase; i++) if (a.ph_P[i] > pmax) pmax = a.ph_P[i];
     a.ptiles = ((pmax + 255) / 256) * a.nphase;      // every phase gets the pixel tiles of the largest one (the others' last tile may be empty)
-    int64_t nblk = (int64_t)a.ptiles * a.ctiles;
-    if (nblk > INT32_MAX) return sbg_fail(SBG_ERR_INVALID, "conv2d_igemm: grid too large");      // (the kernel counts tiles in an int)
-    if (nblk > sbg_cu_count()) nblk = sbg_cu_count();     // persistent: one workgroup per CU, each walks tiles b, b + grid, ...
-    a.ph_rot_div = (int)(nblk / ((int64_t)a.ctiles * a.nphase)); if (a.ph_rot_div < 1) a.ph_rot_div = 1;
-    double macs = 0.0, outpix = 0.0;
-    for (int i = 0; i < a.nphase; i++) { macs += (double)a.ph_P[i] * a.ph_ntaps[i]; outpix += a.ph_P[i]; }
-    return conv_launch<conv_gather_ld_kernel<MF>>(nblk, 1, 768, lds, stream, 2.0 * macs * a.Cout * (double)a.Cin, conv_prof_bytes(a, outpix),
-                                                  {(int)outpix, a.Cout, a.Cin, a.ntaps, a.stride, a.OH, 4128256 + (a.nphase > 1 ? 1000000 * a.nphase : 0)},
-                                                  a, x_bytes, w_bytes);
+    l.family = CONV_GATHER; l.bc = 128; l.bp = 256;
+    l.grid_x = persistent_grid((int64_t)a.ptiles * a.ctiles); l.grid_y = 1; l.block = 768; l.lds = kGatherLds;
+    a.ph_rot_div = (int)(l.grid_x / ((int64_t)a.ctiles * a.nphase)); if (a.ph_rot_div < 1) a.ph_rot_div = 1;
+    conv_prof_phases(l, 4128256 + (a.nphase > 1 ? 1000000 * a.nphase : 0));
 }
 
-template <class MF, int TH, int TW>
-static int launch_halo_ld(ConvArgs& a, unsigned x_bytes, unsigned w_bytes, hipStream_t stream)
+static void fit_halo(ConvLaunch& l, int TH, int TW)
 {
-    constexpr int HPIECES = ((TH + 2) * (TW + 2) + 7) / 8;
-    constexpr int lds = 4 * 128 * 128 + 2 * HPIECES * 1024 + 2 * 3072;
+    ConvArgs& a = l.a;
     {   // the epilogue parameters go through LDS when the epilogue's 16-B fast path applies and the noise rows are 16-B aligned
         const bool plain = conv_is_plain(a);
         const bool fast = ((a.Cout & 7) == 0) && ((((uintptr_t)a.y) & 15) == 0) && (((a.ys_n | a.ys_h | a.ys_w) & 7) == 0)
@@ -870,27 +888,21 @@ static int launch_halo_ld(ConvArgs& a, unsigned x_bytes, unsigned w_bytes, hipSt
                                         && (int64_t)a.N * (a.noise_sn > 0 ? a.noise_sn : 0) + (int64_t)a.OH * a.OW < (1ll << 28));
         a.lds_params = !plain && fast && nz_ok && (int64_t)a.N * a.Cout < (1ll << 28);
     }
-    static_assert(lds <= 160 * 1024, "LDS budget");
     a.ctiles = (a.Cout + 127) / 128;
     a.ptiles = a.N * (a.OH / TH) * (a.OW / TW);
-    int64_t nblk = (int64_t)a.ptiles * a.ctiles;
-    if (nblk > INT32_MAX) return sbg_fail(SBG_ERR_INVALID, "conv2d_igemm: grid too large");      // (the kernel counts tiles in an int)
-    if (nblk > sbg_cu_count()) nblk = sbg_cu_count();     // persistent: one workgroup per CU (the LDS footprint admits no more), each walks tiles b, b + grid, ...
-    return conv_launch<conv_halo_ld_kernel<MF, TH, TW>>(nblk, 1, 768, lds, stream, 2.0 * a.P * a.Cout * (double)a.Cin * a.ntaps, conv_prof_bytes(a, a.P),
-                                                        {a.P, a.Cout, a.Cin, a.ntaps, a.stride, a.OH, 3128256}, a, x_bytes, w_bytes);
+    l.family = CONV_HALO; l.bc = TH; l.bp = TW;
+    l.grid_x = persistent_grid((int64_t)a.ptiles * a.ctiles); l.grid_y = 1; l.block = 768; l.lds = halo_lds(TH, TW);      // (the LDS footprint admits one workgroup per CU)
+    conv_prof_phases(l, 3128256);
 }
 
-template <class MF, int BC, int BP, int WGC, int WGP, int NSTAGE = 3>
-static int launch_k64(ConvArgs& a, unsigned x_bytes, unsigned w_bytes, hipStream_t stream)
+static void fit_tile(ConvLaunch& l, int BC, int BP, int NSTAGE = 3)
 {
-    constexpr int lds = NSTAGE * (BC * 128 + BP * 128);
-    static_assert(lds <= 160 * 1024, "LDS budget");
+    ConvArgs& a = l.a;
     a.ctiles = (a.Cout + BC - 1) / BC;
     a.ptiles = (a.P + BP - 1) / BP;
-    const int64_t nblk = (int64_t)a.ptiles * a.ctiles;
-    return conv_launch<conv_k64_kernel<MF, BC, BP, WGC, WGP, NSTAGE>>(nblk, (unsigned)(a.ksplit > 1 ? a.ksplit : 1), 512, lds, stream,
-                                                              2.0 * a.P * a.Cout * (double)a.Cin * a.ntaps, conv_prof_bytes(a, a.P),
-                                                              {a.P, a.Cout, a.Cin, a.ntaps, a.stride, a.OH, 1000000 + BC * 1000 + BP}, a, x_bytes, w_bytes);
+    l.family = CONV_K64; l.bc = BC; l.bp = BP;
+    l.grid_x = (int64_t)a.ptiles * a.ctiles; l.grid_y = (unsigned)(a.ksplit > 1 ? a.ksplit : 1); l.block = 512; l.lds = k64_lds(BC, BP, NSTAGE);
+    conv_prof_phases(l, 1000000 + BC * 1000 + BP);
 }
 
 // y[i] (+)= sum_k ws[k][i] in a fixed order; 16 lanes share an output element (slabs k, k + 16, ...), then a shuffle tree.
@@ -933,78 +945,51 @@ __global__ __launch_bounds__(256) void conv_ksplit_reduce_epi_kernel(const float
     }
 }
 
-template <class MF>
-static int dispatch_k64(ConvArgs& a, unsigned xb, unsigned wb, hipStream_t stream)
+} // namespace
+
+// The kernel and tile of a launch, in order of precedence.
+void sbg_conv_k64_fit(ConvLaunch& l)
 {
-    if (a.nphase > 1) return launch_gather_ld<MF>(a, xb, wb, stream);       // multi-phase launches exist only in the persistent gather kernel
+    const ConvArgs& a = l.a;
+    if (a.nphase > 1) return fit_gather(l);       // multi-phase launches exist only in the persistent gather kernel
     // halo kernel: stride 1, nine taps with |offset| <= 1, output grid == input grid, tile-aligned, enough tiles to fill the chip
     bool halo = a.stride == 1 && a.ntaps == 9 && a.OH == a.IH && a.OW == a.IW;
     for (int t = 0; halo && t < 9; t++) halo = a.tap_dy[t] >= -1 && a.tap_dy[t] <= 1 && a.tap_dx[t] >= -1 && a.tap_dx[t] <= 1;
     const int64_t tiles256 = (int64_t)((a.P + 255) / 256) * ((a.Cout + 127) / 128);
     if (halo && a.Cout > 64 && tiles256 >= 256) {
-        if (a.OW % 32 == 0 && a.OH % 8 == 0)  return launch_halo_ld<MF, 8, 32>(a, xb, wb, stream);
-        if (a.OW % 16 == 0 && a.OH % 16 == 0) return launch_halo_ld<MF, 16, 16>(a, xb, wb, stream);
+        if (a.OW % 32 == 0 && a.OH % 8 == 0)  return fit_halo(l, 8, 32);
+        if (a.OW % 16 == 0 && a.OH % 16 == 0) return fit_halo(l, 16, 16);
     }
-    if (a.Cout <= 64) return launch_k64<MF, 64, 256, 1, 8>(a, xb, wb, stream);
-    if (a.ksplit > 1) return launch_k64<MF, 128, 128, 2, 4>(a, xb, wb, stream);        // the caller wraps this launch with the slab reduction
-    if (tiles256 < 256) return launch_k64<MF, 128, 128, 2, 4>(a, xb, wb, stream);
+    if (a.Cout <= 64) return fit_tile(l, 64, 256);
+    if (a.ksplit > 1) return fit_tile(l, 128, 128);        // the slab reduction follows this launch
+    if (tiles256 < 256) return fit_tile(l, 128, 128);
     // short reductions (transposed-conv phases: 1-4 taps) gain from the persistent pipeline; measured: +4..10 % at <= 8 K-steps per tile,
     // -5 % at 18+ (the 8-wave kernel's in-wave DMA issue overlaps better there)
     const int ksteps = a.ntaps * ((a.Cin + 63) >> 6);
-    if (ksteps >= 2 && ksteps <= 8) return launch_gather_ld<MF>(a, xb, wb, stream);      // 1 step: store-bound, the plain kernel wins
+    if (ksteps >= 2 && ksteps <= 8) return fit_gather(l);      // 1 step: store-bound, the plain kernel wins
     // 256 x 256 tiles, two stages: 64 DMA pieces per K-step for twice the flops of the 48 below.  Stride-2 launches (D's conv1, the data
     // gradient of G's up-sampling layers) whose 256-channel tiles still give every CU one
     // (the kernel packs a pixel's input row and column into 16 + 16 bits)
     if (a.stride == 2 && a.Cout % 256 == 0 && (a.OH - 1) * 2 + 8 < 32768 && (a.OW - 1) * 2 + 8 < 32768 && (int64_t)((a.P + 255) / 256) * (a.Cout / 256) >= sbg_cu_count())
-        return launch_k64<MF, 256, 256, 2, 4, 2>(a, xb, wb, stream);
-    return launch_k64<MF, 128, 256, 2, 4>(a, xb, wb, stream);
+        return fit_tile(l, 256, 256, 2);
+    return fit_tile(l, 128, 256);
 }
 
-} // namespace
-
-// Split-K is worth it when the output tiles alone leave most CUs idle and the reduction is long: returns the split actually used.
-static int plan_ksplit(const ConvArgs& a, int ksplit)
+int sbg_conv_k64_launch(const ConvLaunch& l, bool bf16, hipStream_t stream)
 {
-    if (ksplit <= 1 || a.Cout <= 64) return 1;
-    const int nsteps = a.ntaps * ((a.Cin + 63) >> 6);
-    int k = ksplit;
-    if (k > nsteps / 4) k = nsteps / 4;             // at least four K-steps per workgroup
-    return k < 2 ? 1 : k;
+    return bf16 ? launch_leaf<bf16_mfma>(l, stream) : launch_leaf<f16_mfma>(l, stream);
 }
 
-extern "C" int64_t sbg_conv2d_igemm_workspace(const sbg_conv_params* q)
+int sbg_conv_ksplit_reduce(const ConvArgs& call, const void* workspace, int ksplit, bool reduce_epi, hipStream_t stream)
 {
-    if (!q || q->ksplit <= 1) return 0;
-    return (int64_t)q->ksplit * q->N * q->OH * q->OW * q->Cout * (int64_t)sizeof(float);
-}
-
-int sbg_conv_k64_dispatch(ConvArgs& a, bool bf16, int64_t x_bytes, int64_t w_bytes, void* workspace, int ksplit, hipStream_t stream)
-{
-    if (x_bytes >= (int64_t)SBG_OOB_OFFSET || w_bytes >= (int64_t)SBG_OOB_OFFSET) return -1;
-    if (a.xs_n < 0 || a.xs_h < 0 || a.xs_w < 0 || a.ws_slab < 0 || a.ws_co < 0) return -1;
-    const unsigned xb = (unsigned)x_bytes, wb = (unsigned)w_bytes;
-    const int64_t y_numel = (int64_t)a.P * a.Cout;
-    const bool dense_y = a.ys_w == a.Cout && a.ys_h == (int64_t)a.OW * a.Cout && a.ys_n == (int64_t)a.OH * a.OW * a.Cout;
-    const bool simple = a.ydtype == SBG_F32 && conv_is_plain(a);                      // plain fp32 sum (may accumulate); otherwise the epilogue rides in the reduction
-    const bool epi_ok = !a.accumulate && (a.Cout & 7) == 0 && (((uintptr_t)a.y) & 15) == 0;
-    const int k = (workspace && dense_y && (simple || epi_ok)) ? plan_ksplit(a, ksplit) : 1;
-    if (k > 1) {
-        ConvArgs b = a;
-        void* y = a.y; const int acc = a.accumulate;
-        b.y = workspace; b.accumulate = 0; b.ksplit = k; b.y_split_stride = y_numel;
-        b.ydtype = SBG_F32; b.act = SBG_ACT_LINEAR; b.gain = 1.f; b.clamp = -1.f; b.bias = nullptr; b.noise = nullptr; b.oscale = nullptr;    // raw fp32 slabs
-        const int rc = bf16 ? dispatch_k64<bf16_mfma>(b, xb, wb, stream) : dispatch_k64<f16_mfma>(b, xb, wb, stream);
-        if (rc != SBG_OK) return rc;
-        if (simple) {
-            unsigned grid = (unsigned)((y_numel + 15) / 16); if (grid > 4096) grid = 4096;
-            SBG_LAUNCH(conv_ksplit_reduce_kernel, dim3(grid), dim3(256), 0, stream, (const float*)workspace, (float*)y, y_numel, k, acc);
-        } else {
-            unsigned grid = (unsigned)((y_numel / 8 + 255) / 256); if (grid > 4096) grid = 4096; if (grid < 1) grid = 1;
-            SBG_LAUNCH(conv_ksplit_reduce_epi_kernel, dim3(grid), dim3(256), 0, stream, (const float*)workspace, a, y_numel, k);
-        }
-        SBG_HIP_LAUNCH_CHECK();
-        return SBG_OK;
+    const int64_t y_numel = (int64_t)call.P * call.Cout;
+    if (!reduce_epi) {
+        unsigned grid = (unsigned)((y_numel + 15) / 16); if (grid > 4096) grid = 4096;
+        SBG_LAUNCH(conv_ksplit_reduce_kernel, dim3(grid), dim3(256), 0, stream, (const float*)workspace, (float*)call.y, y_numel, ksplit, call.accumulate);
+    } else {
+        unsigned grid = (unsigned)((y_numel / 8 + 255) / 256); if (grid > 4096) grid = 4096; if (grid < 1) grid = 1;
+        SBG_LAUNCH(conv_ksplit_reduce_epi_kernel, dim3(grid), dim3(256), 0, stream, (const float*)workspace, call, y_numel, ksplit);
     }
-    if (bf16) return dispatch_k64<bf16_mfma>(a, xb, wb, stream);
-    return dispatch_k64<f16_mfma>(a, xb, wb, stream);
+    SBG_HIP_LAUNCH_CHECK();
+    return SBG_OK;
 }

@@ -15,6 +15,9 @@
 //     ones of sbg_conv_params.
 // Same tap-list contract as the other convolution kernels (include/sbg_hip.h), so forward, data gradient, strided and transposed
 // (phased) launches all take it.
+//
+// Host side: sbg_conv_thin_fit says whether a launch is a thin one and fills its planned launch (pitch, fragments, LDS, grid, profiler record);
+// sbg_conv_thin_launch launches that record.  The plan that calls them is conv_plan in conv_igemm.hip.
 #include "conv_common.h"
 
 using namespace sbgconv;
@@ -168,54 +171,46 @@ __global__ __launch_bounds__(256) void conv_thin_kernel(ConvArgs p, int pitch)  
     }
 }
 
-template <class MF, int TC, int TP>
-static int launch_thin(const ConvArgs& a, int pitch, int lds, hipStream_t stream)
+template <class MF>
+static int launch_thin(const ConvLaunch& l, hipStream_t stream)
 {
-    int maxOH = a.OH, maxOW = a.OW;
-    double macs = (double)a.P * a.ntaps, outpix = a.P;
-    if (a.nphase > 1) {
-        maxOH = maxOW = 0; macs = outpix = 0.0;
-        for (int i = 0; i < a.nphase; i++) {
-            if (a.ph_OH[i] > maxOH) maxOH = a.ph_OH[i];
-            if (a.ph_OW[i] > maxOW) maxOW = a.ph_OW[i];
-            macs += (double)a.ph_P[i] * a.ph_ntaps[i]; outpix += a.ph_P[i];
-        }
-    }
-    const int64_t nblk = (int64_t)a.N * ((maxOH + 4 * TP - 1) / (4 * TP)) * ((maxOW + 15) / 16);     // a phase with a smaller grid leaves its surplus workgroups idle
-    return conv_launch<conv_thin_kernel<MF, TC, TP>>(nblk, (unsigned)(a.nphase > 1 ? a.nphase : 1), 256, lds, stream, 2.0 * macs * a.Cout * (double)a.Cin,
-                                                     conv_prof_bytes(a, outpix), {(int)outpix, a.Cout, a.Cin, a.ntaps, a.stride, a.OH, 6000000 + TC * 16}, a, pitch);
+    // four pixel fragments per wave (eight, sharing the A fragment read and the tap decode over twice the pixels, measured no better: DESIGN.md)
+    if (l.bc == 1) return conv_launch<conv_thin_kernel<MF, 1, 4>>(l, stream, l.pitch);
+    if (l.bc == 2) return conv_launch<conv_thin_kernel<MF, 2, 4>>(l, stream, l.pitch);
+    return conv_launch<conv_thin_kernel<MF, 4, 4>>(l, stream, l.pitch);
 }
 
 } // namespace
 
-// Returns SBG_OK / an error, or -1 when the launch is not a thin one (the caller then uses the wide kernels).
-int sbg_conv_thin_dispatch(ConvArgs& a, bool bf16, hipStream_t stream)
+// Is the launch a thin one (single or phased; the block's alignment rules already make every load a 16-B one)?  Fills the launch when it is.
+bool sbg_conv_thin_fit(ConvLaunch& l)
 {
-    if ((a.Cin & 7) || a.Cin > 64 || a.Cout > 64 || a.Cout < 1) return -1;
-    if (!((a.Cin <= 32) || (a.Cout <= 32))) return -1;                 // 64 x 64 stays with the wide kernels
-    if (a.ksplit > 1 || a.ntaps < 1) return -1;
-    if (a.xs_n < 0 || a.xs_h < 0 || a.xs_w < 0 || a.ws_slab < 0 || a.ws_co < 0) return -1;
-    if ((a.xs_n & 7) || (a.xs_h & 7) || (a.xs_w & 7) || (a.ws_slab & 7) || (a.ws_co & 7)) return -1;      // 16-B loads
-    if ((((uintptr_t)a.x) & 15) || (((uintptr_t)a.w) & 15)) return -1;
-    int maxtaps = a.ntaps, maxP = a.P;
+    const ConvArgs& a = l.a;
+    if (a.Cin > 64 || a.Cout > 64) return false;
+    if (!((a.Cin <= 32) || (a.Cout <= 32))) return false;              // 64 x 64 stays with the wide kernels
+    int maxtaps = a.ntaps, maxOH = a.OH, maxOW = a.OW;
     if (a.nphase > 1) {
-        maxtaps = 0; maxP = 0;
-        for (int i = 0; i < a.nphase; i++) { if (a.ph_ntaps[i] > maxtaps) maxtaps = a.ph_ntaps[i]; if (a.ph_P[i] > maxP) maxP = a.ph_P[i]; }
+        maxtaps = maxOH = maxOW = 0;
+        for (int i = 0; i < a.nphase; i++) {
+            if (a.ph_ntaps[i] > maxtaps) maxtaps = a.ph_ntaps[i];
+            if (a.ph_OH[i] > maxOH) maxOH = a.ph_OH[i];
+            if (a.ph_OW[i] > maxOW) maxOW = a.ph_OW[i];
+        }
     }
-    if (maxP <= 0) return -1;
     const int kpad = ((maxtaps * a.Cin + 31) >> 5) << 5;
-    if (kpad > 640) return -1;
-    const int pitch = (((kpad >> 1) | 4)) << 1;                          // row pitch: (kpad / 2) dwords with bit 2 set -> 16 rows on 16 bank groups
+    if (kpad > 640) return false;
+    l.family = CONV_THIN;
+    l.pitch = (((kpad >> 1) | 4)) << 1;                                  // row pitch: (kpad / 2) dwords with bit 2 set -> 16 rows on 16 bank groups
     const int tc = (a.Cout + 15) >> 4;
-    const int TCs = tc <= 1 ? 1 : (tc <= 2 ? 2 : 4);
-    const int lds = 16 * TCs * pitch * 2;
-    // four pixel fragments per wave (eight, sharing the A fragment read and the tap decode over twice the pixels, measured no better: DESIGN.md)
-    if (bf16) {
-        if (TCs == 1) return launch_thin<bf16_mfma, 1, 4>(a, pitch, lds, stream);
-        if (TCs == 2) return launch_thin<bf16_mfma, 2, 4>(a, pitch, lds, stream);
-        return launch_thin<bf16_mfma, 4, 4>(a, pitch, lds, stream);
-    }
-    if (TCs == 1) return launch_thin<f16_mfma, 1, 4>(a, pitch, lds, stream);
-    if (TCs == 2) return launch_thin<f16_mfma, 2, 4>(a, pitch, lds, stream);
-    return launch_thin<f16_mfma, 4, 4>(a, pitch, lds, stream);
+    l.bc = tc <= 1 ? 1 : (tc <= 2 ? 2 : 4); l.bp = 1;
+    l.lds = 16 * l.bc * l.pitch * 2;
+    l.grid_x = (int64_t)a.N * ((maxOH + 15) / 16) * ((maxOW + 15) / 16);      // 16 x 16 pixel tiles; a phase with a smaller grid leaves its surplus workgroups idle
+    l.grid_y = (unsigned)a.nphase; l.block = 256;
+    conv_prof_phases(l, 6000000 + l.bc * 16);
+    return true;
+}
+
+int sbg_conv_thin_launch(const ConvLaunch& l, bool bf16, hipStream_t stream)
+{
+    return bf16 ? launch_thin<bf16_mfma>(l, stream) : launch_thin<f16_mfma>(l, stream);
 }

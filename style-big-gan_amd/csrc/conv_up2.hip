@@ -21,6 +21,9 @@
 //
 // Accumulator layout and channel permutation of the weight rows are those of conv_k64.hip (conv_device.h); the store is this file's own
 // (store_phase: no fused tail, bounds tests of the phase grids).
+//
+// Host side: sbg_conv_up2_fit recognises the form, puts its taps in canonical order, says whether this kernel covers the call, and then fills the
+// planned launch and the border rectangles; sbg_conv_up2_launch launches that record.  The plan that calls them is conv_plan in conv_igemm.hip.
 #include "conv_device.h"
 
 using namespace sbgconv;
@@ -227,31 +230,24 @@ __global__ __launch_bounds__(512) void conv_up2_kernel(ConvArgs p, unsigned x_by
 }
 
 template <class MF>
-static int launch_up2(const ConvArgs& a, unsigned x_bytes, unsigned w_bytes, int Hm, int Wm, int dymin, int dxmin, hipStream_t stream)
+static int launch_up2(const ConvLaunch& l, hipStream_t stream)
 {
-    constexpr int lds = 2 * 38 * 1024 + 4 * 16384 + 1024;
-    const int tiles_y = Hm / 8, tiles_x = Wm / 32;
-    const int64_t nblk = (int64_t)a.N * tiles_y * tiles_x * a.ctiles;
-    const double ys = a.ydtype == SBG_F32 ? 4.0 : 2.0, pix = (double)a.N * Hm * Wm;
-    const double flops = 2.0 * 9.0 * pix * a.Cout * (double)a.Cin;
-    const double bytes = 2.0 * a.N * a.IH * a.IW * (double)a.Cin + 2.0 * 9 * a.Cout * (double)a.Cin + ys * 4.0 * pix * (double)a.Cout;
-#define SBG_UP2_LAUNCH(YDT) conv_launch<conv_up2_kernel<MF, YDT>>(nblk, 1, 512, lds, stream, flops, bytes, {(int)(4.0 * pix), a.Cout, a.Cin, 9, 2, Hm, 9064256}, \
-                                                                  a, x_bytes, w_bytes, tiles_y, tiles_x, dymin, dxmin)      // 9xxxxxx = conv_up2_kernel (profiles/summarize.py)
-    if (a.ydtype == SBG_F32) return SBG_UP2_LAUNCH(SBG_F32);
-    if (a.ydtype == SBG_BF16) return SBG_UP2_LAUNCH(SBG_BF16);
+#define SBG_UP2_LAUNCH(YDT) conv_launch<conv_up2_kernel<MF, YDT>>(l, stream, l.x_bytes, l.w_bytes, l.tiles_y, l.tiles_x, l.dymin, l.dxmin)
+    if (l.a.ydtype == SBG_F32) return SBG_UP2_LAUNCH(SBG_F32);
+    if (l.a.ydtype == SBG_BF16) return SBG_UP2_LAUNCH(SBG_BF16);
     return SBG_UP2_LAUNCH(SBG_F16);
 #undef SBG_UP2_LAUNCH
 }
 
 } // namespace
 
-// Is the launch a 4 / 2 / 2 / 1-tap stride-2 transposed convolution whose nine taps lie in one 2 x 2 window, in tensors this file's kernel can address?
-static bool up2_form(const ConvArgs& a, int64_t x_bytes, int64_t w_bytes, int& dymin, int& dxmin)
+// Is the launch a 4 / 2 / 2 / 1-tap stride-2 transposed convolution whose nine taps lie in one 2 x 2 window?  (The plan offers only launches whose
+// operands this file's kernel can address.)
+static bool up2_form(const ConvArgs& a, int& dymin, int& dxmin)
 {
     if (a.nphase != 4 || a.stride != 1 || a.ksplit > 1 || a.accumulate) return false;
     if (a.ph_ntaps[0] != 4 || a.ph_ntaps[1] != 2 || a.ph_ntaps[2] != 2 || a.ph_ntaps[3] != 1) return false;
     if ((a.Cout % 8) != 0 || (a.Cin % 8) != 0 || a.Cout < 64 || a.Cin < 64) return false;
-    if (x_bytes >= (int64_t)SBG_OOB_OFFSET || w_bytes >= (int64_t)SBG_OOB_OFFSET) return false;
     if ((((uintptr_t)a.y) & 15) != 0 || ((a.ys_n | a.ys_h | a.ys_w) & 7) != 0) return false;
     dymin = a.tap_dy[0]; dxmin = a.tap_dx[0];
     for (int t = 0; t < 9; t++) { if (a.tap_dy[t] < dymin) dymin = a.tap_dy[t]; if (a.tap_dx[t] < dxmin) dxmin = a.tap_dx[t]; }
@@ -260,69 +256,67 @@ static bool up2_form(const ConvArgs& a, int64_t x_bytes, int64_t w_bytes, int& d
     return true;
 }
 
-// Canonical tap order of such a launch: inside every phase by (dy, dx).  The entry point calls this BEFORE it offers the launch to any kernel, and
-// it either orders the whole table or leaves it alone: the order in which a phase's taps are accumulated (and so the rounding of the sum) is then
-// the same whichever kernel takes the launch -- sbg_conv_up2_dispatch below, which relies on it, or the multi-phase gather kernel of conv_k64.hip
-// when that one declines (grids under 8 x 32).  Returns whether the launch is of the form.
-bool sbg_conv_up2_canonical_taps(ConvArgs& a, int64_t x_bytes, int64_t w_bytes)
+// See conv_common.h.  The taps of a launch of the form are ordered before anything else is decided, all of them or none: the order in which a phase's
+// taps are accumulated (and so the rounding of the sum) is then the same whether this file's kernel takes the launch or, when it declines (grids
+// under 8 x 32), the multi-phase gather kernel of conv_k64.hip.
+Up2Fit sbg_conv_up2_fit(ConvLaunch& l, const sbg_conv_params& q, sbg_conv_params& border)
 {
+    ConvArgs& a = l.a;
     int dymin, dxmin;
-    if (!up2_form(a, x_bytes, w_bytes, dymin, dxmin)) return false;
+    if (!up2_form(a, dymin, dxmin)) return UP2_OTHER_FORM;
     for (int i = 0; i < 4; i++)
         for (int u = a.ph_tap0[i]; u < a.ph_tap0[i] + a.ph_ntaps[i]; u++)
             for (int v = u + 1; v < a.ph_tap0[i] + a.ph_ntaps[i]; v++)
                 if (a.tap_dy[v] < a.tap_dy[u] || (a.tap_dy[v] == a.tap_dy[u] && a.tap_dx[v] < a.tap_dx[u])) {
                     std::swap(a.tap_dy[u], a.tap_dy[v]); std::swap(a.tap_dx[u], a.tap_dx[v]); std::swap(a.tap_slab[u], a.tap_slab[v]);
                 }
-    return true;
-}
-
-// Returns SBG_OK / an error, or -1 when the launch is not a 4 / 2 / 2 / 1-tap stride-2 transposed convolution this kernel covers (it reads the
-// tap table and never reorders it: a launch whose taps are not in canonical order is declined).  On
-// success the region [0, Hm) x [0, Wm) of every phase grid has been written; `border` receives the (up to four) rectangles that remain --
-// the last row of the phases that have Hm + 1 rows, the last column of those with Wm + 1 columns -- as phases of an ordinary launch.
-int sbg_conv_up2_dispatch(ConvArgs& a, bool bf16, int64_t x_bytes, int64_t w_bytes, sbg_conv_params* border, const sbg_conv_params* q, hipStream_t stream)
-{
-    int dymin, dxmin;
-    if (!up2_form(a, x_bytes, w_bytes, dymin, dxmin)) return -1;
     {   // the window shifts must read 0 1 2 3 | 1 3 | 2 3 | 3 (the kernel hard-codes them)
         static const int want[9] = {0, 1, 2, 3, 1, 3, 2, 3, 3};
-        for (int t = 0; t < 9; t++) if ((a.tap_dy[t] - dymin) * 2 + (a.tap_dx[t] - dxmin) != want[t]) return -1;
+        for (int t = 0; t < 9; t++) if ((a.tap_dy[t] - dymin) * 2 + (a.tap_dx[t] - dxmin) != want[t]) return UP2_ORDERED;
     }
     int Hm = a.ph_OH[0], Wm = a.ph_OW[0];
     for (int i = 1; i < 4; i++) { if (a.ph_OH[i] < Hm) Hm = a.ph_OH[i]; if (a.ph_OW[i] < Wm) Wm = a.ph_OW[i]; }
-    if (Hm < 8 || Wm < 32 || (Hm % 8) != 0 || (Wm % 32) != 0) return -1;
+    if (Hm < 8 || Wm < 32 || (Hm % 8) != 0 || (Wm % 32) != 0) return UP2_ORDERED;
     for (int i = 0; i < 4; i++) {
-        if (a.ph_OH[i] > Hm + 1 || a.ph_OW[i] > Wm + 1) return -1;
-        if ((a.ph_yoff[i] & 7) != 0) return -1;
+        if (a.ph_OH[i] > Hm + 1 || a.ph_OW[i] > Wm + 1) return UP2_ORDERED;
+        if ((a.ph_yoff[i] & 7) != 0) return UP2_ORDERED;
     }
-    // ---- the border rectangles, as phases of a second launch: pixel (u, v) of rectangle (r0, c0) of phase i is pixel (r0 + u, c0 + v) of
+    // ---- the border rectangles, as phases of a second call: pixel (u, v) of rectangle (r0, c0) of phase i is pixel (r0 + u, c0 + v) of
     // that phase's grid, so its taps are the phase's taps shifted by (r0, c0) and its outputs start r0 rows / c0 columns further
-    *border = *q;
-    border->nphase = 0; border->ntaps = 0;
+    border = q;
+    border.nphase = 0; border.ntaps = 0; border.ksplit = 1;
     for (int i = 0; i < 4; i++) {
         for (int side = 0; side < 2; side++) {
             int r0, c0, rh, rw;
             if (side == 0) { if (a.ph_OH[i] == Hm) continue; r0 = Hm; c0 = 0; rh = 1; rw = a.ph_OW[i]; }          // the extra row, all columns
             else           { if (a.ph_OW[i] == Wm) continue; r0 = 0; c0 = Wm; rh = Hm; rw = 1; }                  // the extra column, the main rows
-            if (border->nphase >= 4) return -1;
-            const int ph = border->nphase;
+            if (border.nphase >= 4) return UP2_ORDERED;
+            const int ph = border.nphase;
             int nt = 0;
             for (int t = 0; t < a.ph_ntaps[i]; t++) {
                 const int dy = a.tap_dy[a.ph_tap0[i] + t] + r0, dx = a.tap_dx[a.ph_tap0[i] + t] + c0;
                 if (dy + rh - 1 < 0 || dy >= a.IH || dx + rw - 1 < 0 || dx >= a.IW) continue;                     // reads only zeros
-                if (border->ntaps >= SBG_MAX_TAPS) return -1;
-                border->tap_dy[border->ntaps] = dy; border->tap_dx[border->ntaps] = dx; border->tap_slab[border->ntaps] = a.tap_slab[a.ph_tap0[i] + t];
-                border->ntaps++; nt++;
+                if (border.ntaps >= SBG_MAX_TAPS) return UP2_ORDERED;
+                border.tap_dy[border.ntaps] = dy; border.tap_dx[border.ntaps] = dx; border.tap_slab[border.ntaps] = a.tap_slab[a.ph_tap0[i] + t];
+                border.ntaps++; nt++;
             }
-            if (nt == 0) return -1;                      // (would need a zero fill: not a shape this path meets)
-            border->ph_ntaps[ph] = nt; border->ph_oh[ph] = rh; border->ph_ow[ph] = rw;
-            border->ph_yoff[ph] = a.ph_yoff[i] + (int64_t)r0 * a.ys_h + (int64_t)c0 * a.ys_w;
-            border->nphase++;
+            if (nt == 0) return UP2_ORDERED;             // (would need a zero fill: not a shape this path meets)
+            border.ph_ntaps[ph] = nt; border.ph_oh[ph] = rh; border.ph_ow[ph] = rw;
+            border.ph_yoff[ph] = a.ph_yoff[i] + (int64_t)r0 * a.ys_h + (int64_t)c0 * a.ys_w;
+            border.nphase++;
         }
     }
     a.ctiles = (a.Cout + 63) / 64;
-    const int rc = bf16 ? launch_up2<bf16_mfma>(a, (unsigned)x_bytes, (unsigned)w_bytes, Hm, Wm, dymin, dxmin, stream)
-                        : launch_up2<f16_mfma>(a, (unsigned)x_bytes, (unsigned)w_bytes, Hm, Wm, dymin, dxmin, stream);
-    return rc;
+    l.family = CONV_UP2; l.bc = 64; l.bp = 256;
+    l.tiles_y = Hm / 8; l.tiles_x = Wm / 32; l.dymin = dymin; l.dxmin = dxmin;
+    l.grid_x = (int64_t)a.N * l.tiles_y * l.tiles_x * a.ctiles; l.grid_y = 1; l.block = 512;
+    l.lds = 2 * 38 * 1024 + 4 * 16384 + 1024;
+    const double pix = (double)a.N * Hm * Wm;            // per phase; all nine taps run over it
+    conv_prof(l, 9.0 * pix, 4.0 * pix, 9, 2, Hm, 9064256);      // 9xxxxxx = conv_up2_kernel (profiles/summarize.py)
+    return UP2_FITS;
+}
+
+int sbg_conv_up2_launch(const ConvLaunch& l, bool bf16, hipStream_t stream)
+{
+    return bf16 ? launch_up2<bf16_mfma>(l, stream) : launch_up2<f16_mfma>(l, stream);
 }

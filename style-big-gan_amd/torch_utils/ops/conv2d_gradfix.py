@@ -109,9 +109,6 @@ class Epilogue:
         p.act, p.alpha, p.gain, p.clamp = self.act, self.alpha, self.gain, self.clamp
 
 
-_KSPLIT_MAX_TILES = 128    # K split: a launch of fewer output tiles than this ...
-_KSPLIT_TARGET = 256       # ... spreads its reduction over about this many workgroups
-
 # fp32 operands up to this many elements run as ONE launch over the concatenated hi / mid / lo parts (each operand built by one pass of
 # sbg_split_bf16_cat: 4 B read + 12 B written per element).  The alternative -- six launches that read-modify-write the fp32 output five times,
 # fed by parts split with framework ops -- moves ~4x the bytes on large activations (BigGAN at 128x128: [48, 64, 128, 128] tensors; half of
@@ -248,46 +245,43 @@ def _unpack_wgrad(out, ca, cb, wshape, wstride, rows_dim, gain, w=None, dw2=None
     return dw
 
 
+def _conv_params(x, wp, y, y_step):
+    """the part of the parameter block every launch fills alike: operands, dtypes, sizes, strides, identity epilogue"""
+    p = _lib.ConvParams()
+    n, cin, ih, iw = x.shape
+    assert wp.shape[2] == cin and x.stride(1) == 1 and y.stride(1) == 1 and wp.is_contiguous() and x.dtype == wp.dtype
+    p.x, p.w, p.y = x.data_ptr(), wp.data_ptr(), y.data_ptr()
+    p.xdtype, p.ydtype = _lib.dtype_code(x.dtype), _lib.dtype_code(y.dtype)
+    p.N, p.IH, p.IW, p.Cin, p.Cout = n, ih, iw, cin, wp.shape[1]
+    p.xs_n, p.xs_h, p.xs_w = x.stride(0), x.stride(2), x.stride(3)
+    p.ys_n, p.ys_h, p.ys_w = y.stride(0), y.stride(2) * y_step[0], y.stride(3) * y_step[1]
+    p.ws_slab, p.ws_co = wp.stride(0), wp.stride(1)
+    p.act, p.alpha, p.gain, p.clamp = 1, 0.0, 1.0, -1.0
+    return p
+
+
 def _igemm(x, wp, y, taps, stride, oh, ow, y_off=(0, 0), y_step=(1, 1), oscale=None, accumulate=False, epi=None):
     """x: [N, Cin, IH, IW] channel-minor 16-bit; wp: packed [slabs, Cout, Cin]; y: [N, Cout, YH, YW] channel-minor.
     Writes y[:, :, y_off[0] + y_step[0]*oy, y_off[1] + y_step[1]*ox] for oy < oh, ox < ow."""
     lib = _lib.load()
-    p = _lib.ConvParams()
-    n, cin, ih, iw = x.shape
-    cout = wp.shape[1]
-    assert wp.shape[2] == cin and x.stride(1) == 1 and y.stride(1) == 1 and wp.is_contiguous() and x.dtype == wp.dtype
-    es = y.element_size()
-    p.x, p.w = x.data_ptr(), wp.data_ptr()
-    p.y = y.data_ptr() + (y_off[0] * y.stride(2) + y_off[1] * y.stride(3)) * es
+    p = _conv_params(x, wp, y, y_step)
+    p.y = y.data_ptr() + (y_off[0] * y.stride(2) + y_off[1] * y.stride(3)) * y.element_size()
     p.oscale = oscale.data_ptr() if oscale is not None else None
-    p.xdtype, p.ydtype = _lib.dtype_code(x.dtype), _lib.dtype_code(y.dtype)
-    p.N, p.IH, p.IW, p.Cin, p.Cout, p.OH, p.OW = n, ih, iw, cin, cout, oh, ow
-    p.xs_n, p.xs_h, p.xs_w = x.stride(0), x.stride(2), x.stride(3)
-    p.ys_n, p.ys_h, p.ys_w = y.stride(0), y.stride(2) * y_step[0], y.stride(3) * y_step[1]
-    p.ws_slab, p.ws_co = wp.stride(0), wp.stride(1)
+    p.OH, p.OW = oh, ow
     p.stride, p.ntaps = stride, len(taps)
     assert 1 <= len(taps) <= _lib.SBG_MAX_TAPS
     for i, (dy, dx, slab) in enumerate(taps):
         p.tap_dy[i], p.tap_dx[i], p.tap_slab[i] = dy, dx, slab
     p.accumulate = int(accumulate)
-    p.act, p.alpha, p.gain, p.clamp = 1, 0.0, 1.0, -1.0
     if epi is not None:
         assert not accumulate and y_step == (1, 1)
-        epi.fill(p, n, cout, oh, ow)
-    # few output tiles but a long reduction (the 4x4 fp32 block: 16 tiles x 432 K-steps; the 16-bit 4x4 .. 8x8 layers: 16-64 tiles x 72): split K over
-    # workgroups; the fixed-order slab reduction applies the fused epilogue and the output cast
-    ws = None
-    tiles = -(-(n * oh * ow) // 128) * -(-cout // 128)
-    ksteps = len(taps) * -(-cin // 64)
-    # (an odd channel count -- the 513-channel data gradient of the discriminator's epilogue convolution -- splits too when the result is a plain
-    # fp32 sum: only the fused-epilogue reduction stores 8-channel vectors)
-    plain_f32 = epi is None and y.dtype == torch.float32
-    if ((epi is None or not accumulate) and (y.dtype == torch.float32 or not accumulate) and y_step == (1, 1) and y_off == (0, 0) and cout > 64
-            and (cout % 8 == 0 or plain_f32) and tiles < _KSPLIT_MAX_TILES and ksteps >= 16 and y.is_contiguous(memory_format=torch.channels_last)):
-        p.ksplit = max(1, min(ksteps // 4, -(-_KSPLIT_TARGET // tiles)))
-        if p.ksplit > 1:
-            ws = torch.empty([lib.sbg_conv2d_igemm_workspace(p) // 4], dtype=torch.float32, device=x.device)
-            p.workspace = ws.data_ptr()
+        epi.fill(p, x.shape[0], wp.shape[1], oh, ow)
+    # few output tiles but a long reduction: the library splits K over workgroups (ksplit stays 0: its choice) when it is handed the scratch for it
+    nbytes = lib.sbg_conv2d_igemm_workspace(p)
+    if nbytes < 0:
+        _lib.check(1, "sbg_conv2d_igemm_workspace")
+    ws = torch.empty([nbytes // 4], dtype=torch.float32, device=x.device) if nbytes > 0 else None
+    p.workspace = ws.data_ptr() if ws is not None else None
     _lib.check(lib.sbg_conv2d_igemm(p, _lib.stream_ptr(x.device)), "sbg_conv2d_igemm")
 
 
@@ -295,18 +289,9 @@ def _igemm_phases(x, wp, y, phases, s):
     """ONE launch for all phases of a stride-s transposed convolution (sbg_conv_params.nphase): phase (a, b) writes
     y[:, :, a::s, b::s] from its own run of taps; the phases' tiles share the input through L2."""
     lib = _lib.load()
-    p = _lib.ConvParams()
-    n, cin, ih, iw = x.shape
-    cout = wp.shape[1]
-    p.x, p.w, p.y = x.data_ptr(), wp.data_ptr(), y.data_ptr()
-    p.xdtype, p.ydtype = _lib.dtype_code(x.dtype), _lib.dtype_code(y.dtype)
-    p.N, p.IH, p.IW, p.Cin, p.Cout = n, ih, iw, cin, cout
+    p = _conv_params(x, wp, y, (s, s))
     p.OH, p.OW = max(ph[2] for ph in phases), max(ph[3] for ph in phases)
-    p.xs_n, p.xs_h, p.xs_w = x.stride(0), x.stride(2), x.stride(3)
-    p.ys_n, p.ys_h, p.ys_w = y.stride(0), y.stride(2) * s, y.stride(3) * s
-    p.ws_slab, p.ws_co = wp.stride(0), wp.stride(1)
     p.stride = 1
-    p.act, p.alpha, p.gain, p.clamp = 1, 0.0, 1.0, -1.0
     t = 0
     for i, (a, b, goh, gow, taps) in enumerate(phases):
         p.ph_ntaps[i], p.ph_oh[i], p.ph_ow[i] = len(taps), goh, gow

@@ -25,6 +25,7 @@ import style_big_gan_amd  # noqa: F401
 from style_big_gan_amd import _lib
 from style_big_gan_amd.torch_utils.ops import conv2d_gradfix as CG, conv_bias_act, upfirdn2d as UP
 
+import conv_plan_cases as PLAN
 from exact_util import U32, U_OUT, assert_exact, assert_range, expect_launch, qgrid, qint, qpow2, within_bound
 
 pytestmark = pytest.mark.gpu
@@ -243,6 +244,26 @@ def test_accumulate_into_prefilled_fp32(dev, case):
         assert any(r["dims"][6] == 1128128 and r["bytes"] == _slab_bytes(r["dims"], n, h, w, cin) for r in log if r["kind"] == "conv_igemm"), \
             f"{tag}: no split-K slab launch: {[(r['dims'], r['bytes']) for r in log]}"
     assert_exact(y, pre + ref, tag)
+
+
+@pytest.mark.parametrize("name", PLAN.LAUNCHABLE)
+def test_launch_log_equals_the_plan(dev, name):
+    """every launchable row of the plan table (conv_plan_cases.py), as a real call on zero operands: the launch log must equal, record for
+    record in dims, flops and bytes, both what sbg_conv2d_igemm_plan says the call will launch and golden/conv_plan.json, the launches of the
+    library before the plan became one function.  (The host-only half is tests/test_conv_plan_cpu.py.)"""
+    import json
+    import os
+    lib = _lib.load()
+    c = PLAN.CASES[name]
+    x, wp, y, bias, store = PLAN.tensors(c, dev)
+    p = PLAN.block(c, x=x.data_ptr(), w=wp.data_ptr(), y=store.data_ptr(), workspace=None, bias=bias.data_ptr())
+    want = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "conv_plan.json")))[name]
+    assert lib.sbg_conv2d_igemm_workspace(p) == want["workspace"]
+    log = PLAN.launch_log(lib, p, dev)                  # (sets p.workspace)
+    planned = [dict(dims=r["dims"], flops=r["flops"], bytes=r["bytes"]) for r in PLAN.plan(lib, p)]
+    assert log == planned, (name, log, planned)
+    assert log == want["launches"], (name, log, want["launches"])
+    assert not bool(torch.isnan(store.float()).any()) and not bool(store.any())         # zero operands: zeros, whatever the epilogue
 
 
 def test_generic_kernels_beyond_2GiB(dev):
