@@ -698,6 +698,27 @@ int sbg_msssim_level(const void* x, const void* y, int is_u8, const double* wind
 int sbg_msssim_down(const void* x, int is_u8, float* y, int64_t BC, int S, sbg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Latent directions (directions.py: GANSpace, Harkonen et al., NeurIPS 2020, and SeFa, Shen & Zhou, CVPR 2021; the reference has no
+ * counterpart): the column mean and the Gram matrix of a table of latents x fp32 [N, D], and the table of edited latents.  The orders are
+ * stated in csrc/directions.hip and DESIGN.md section 25; torch_utils/ops/directions.py evaluates them for CPU tensors to the same bits.
+ * Dense tensors, fp32 4-byte and float64 8-byte aligned; N >= 1, 1 <= D <= 1024; no atomics: two runs give the same bits.
+ *   sbg_directions_mean:  out (float64 [D]) = the float64 column sums of x in an order fixed by N alone, divided once by N;
+ *                         sbg_directions_mean_workspace(N, D) bytes of workspace (-1: unsupported sizes).  Two launches.
+ *   sbg_directions_gram:  out (float64 [D, D]) = c^T c of c = x - mean (one fp32 subtraction; mean NULL: c = x): fp32 fmaf chains over chunks
+ *                         of 256 rows on the matrix cores, float64 sums of 16 chunks in registers, the group sums added by the merge kernel;
+ *                         symmetric bit for bit.  sbg_directions_gram_workspace(N, D) bytes = 8 * groups * D * D (-1: unsupported sizes).
+ *                         Two launches.
+ *   sbg_directions_edit:  out (fp32 [S K T, L, D]), row (s K + k) T + t = ws[s] (fp32 [S, L, D]) with fmaf(sigmas[t] * scale[k], comps[k, d],
+ *                         ws[s, l, d]) on the layers whose layer_mask (int32 [L]) entry is nonzero, a copy on the others.  One launch;
+ *                         S K T = 0 writes nothing. */
+int64_t sbg_directions_mean_workspace(int64_t N, int D);
+int sbg_directions_mean(const float* x, double* out, void* workspace, int64_t N, int D, sbg_stream_t stream);
+int64_t sbg_directions_gram_workspace(int64_t N, int D);
+int sbg_directions_gram(const float* x, const float* mean, double* out, void* workspace, int64_t N, int D, sbg_stream_t stream);
+int sbg_directions_edit(const float* ws, const float* comps, const float* scale, const float* sigmas, const int32_t* layer_mask, float* out,
+                        int S, int L, int D, int K, int T, sbg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * In-process launch timing (measurement only; bench.py's roofline figures come from here).
  * While enabled, every kernel launch of this library is bracketed by two hipEvents recorded on the launch stream
  * and logged with its algorithmic flops / bytes.  sbg_prof_fetch() synchronises the logged events, writes up to `max`
@@ -724,7 +745,9 @@ enum sbg_kernel_kind {
     SBG_K_SWD = 27,             /* dims[0] = variant: 0 pyr_down (B, C, S) / 1 pyr_lap (B, C, S) / 2 gather (B, C, S, P) / 3 moments (M, C, chunks) /
                                  * 4 project (M, K, D) / 5 l1 (D, M, chunks) / 6 merge of the float64 partials (values, chunks); M clipped to INT32_MAX */
     SBG_K_SPECTRUM = 28,        /* dims[0] = variant: 0 rows / 1 cols; then BC (image-channels of the call), R, S */
-    SBG_K_MSSSIM = 29           /* dims[0] = variant: 0 level / 1 down / 2 merge; then BC (image-channels of the call, clipped to INT32_MAX), S */
+    SBG_K_MSSSIM = 29,          /* dims[0] = variant: 0 level / 1 down / 2 merge; then BC (image-channels of the call, clipped to INT32_MAX), S */
+    SBG_K_DIRECTIONS = 30       /* dims[0] = variant: 0 mean (N, D, chunks) / 1 gram (N, D, groups) / 2 merge (N, D, chunks or groups: the launch
+                                 * it finishes) / 3 edit (S, K, T, L, D); N clipped to INT32_MAX */
 };
 /* Kernel-variant codes in the records of the streaming kernels (which kernel served the launch):
  *   bias_act     dims[4] = 1 vec8 / 2 scalar,  dims[5] = bias mode (0 none, 1 channel-minor vector, 2 one per 8-vector, 3 generic)

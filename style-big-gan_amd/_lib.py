@@ -112,7 +112,8 @@ class ProfRecord(ctypes.Structure):
 KERNEL_KINDS = {1: "bias_act", 2: "upfirdn2d", 3: "conv_igemm", 4: "conv_wgrad", 5: "wgrad_reduce", 6: "scale_nc", 7: "dot_hw", 9: "sn_power", 10: "attention",
                 11: "grid_sample", 12: "filter1d", 13: "color", 14: "weight_prep", 15: "torgb", 16: "fromrgb", 17: "grouped_gemm", 18: "ppl",
                 19: "projector", 20: "image_export", 21: "resample", 22: "pr", 23: "grad_finish", 24: "resident", 25: "diffaug", 26: "nn_u8", 27: "swd", 28: "spectrum",
-                29: "msssim"}
+                29: "msssim", 30: "directions"}
+DIRECTIONS_VARIANTS = {0: "mean", 1: "gram", 2: "merge", 3: "edit"}     # dims[0] of a "directions" launch record
 MSSSIM_VARIANTS = {0: "level", 1: "down", 2: "merge"}      # dims[0] of an "msssim" launch record (then BC, S)
 SWD_VARIANTS = {0: "pyr_down", 1: "pyr_lap", 2: "gather", 3: "moments", 4: "project", 5: "l1", 6: "merge"}      # dims[0] of an "swd" launch record
 SPECTRUM_VARIANTS = {0: "rows", 1: "cols"}                 # dims[0] of a "spectrum" launch record (then BC, R, S)
@@ -243,6 +244,11 @@ SYMBOLS = [
     ("sbg_msssim_level", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_double, _c.c_double, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int,
                                     _c.c_void_p]),
     ("sbg_msssim_down", _c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int64, _c.c_int, _c.c_void_p]),
+    ("sbg_directions_mean_workspace", _c.c_int64, [_c.c_int64, _c.c_int]),
+    ("sbg_directions_mean", _c.c_int, [_c.c_void_p] * 3 + [_c.c_int64, _c.c_int, _c.c_void_p]),
+    ("sbg_directions_gram_workspace", _c.c_int64, [_c.c_int64, _c.c_int]),
+    ("sbg_directions_gram", _c.c_int, [_c.c_void_p] * 4 + [_c.c_int64, _c.c_int, _c.c_void_p]),
+    ("sbg_directions_edit", _c.c_int, [_c.c_void_p] * 6 + [_c.c_int] * 5 + [_c.c_void_p]),
     ("sbg_prof_enable", _c.c_int, [_c.c_int]),
     ("sbg_prof_fetch", _c.c_int, [_c.POINTER(ProfRecord), _c.c_int]),
 ]

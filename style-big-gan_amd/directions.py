@@ -1,0 +1,270 @@
+"""Latent directions of a trained generator: which knobs does it have, and what do they do to an image?
+
+The other snapshot tools judge images; this one finds the directions of W along which the generator varies most and moves latents along them.
+Both standard answers are eigen-decompositions of a Gram matrix over W and need neither a detector nor a data set; the reference has no such tool.
+
+* ``--method=pca``: GANSpace (Harkonen et al., "GANSpace: Discovering Interpretable GAN Controls", NeurIPS 2020).  ``--num`` latents
+  ``z = RandomState(--seed).randn(num, z_dim)`` are mapped at psi = 1 (with the class of ``--class`` on a conditional network); the directions are
+  the principal components of the mapped ``w``: the eigenvectors of ``G / (num - 1)``, G the Gram matrix of the centred latents.  A step of
+  sigma moves ``w`` by sigma standard deviations of the component (``scale = stdev``).
+* ``--method=sefa``: SeFa (Shen & Zhou, "Closed-Form Factorization of Latent Semantics in GANs", CVPR 2021).  No sampling: A stacks the rows of the
+  style affines' weights of the convolutions whose ws index is in ``--layers`` (ToRGB layers are left out, as in the authors' code, so the last ws
+  index contributes nothing), each row divided by its l2 norm; the directions are the eigenvectors of ``A^T A``.  ``scale = 1``: a step of sigma
+  is a plain distance in W.
+* The Gram matrix and the column mean come from ``torch_utils/ops/directions.py`` (fp32 fmaf chains on the matrix cores under fixed-order float64
+  sums), the same bits with ``--device=cpu`` and ``cuda``; the eigen-decomposition is ``numpy.linalg.eigh`` on the host:
+  eigenvalues descending, each eigenvector's entry of largest magnitude positive (ties to the lowest index).  Within one machine everything
+  downstream is therefore identical on both devices; across machines LAPACK may differ.  ``--device=cpu`` emulates fmaf in numpy: small ``--num``.
+* Edits: for every base latent -- ``--seeds`` through the ``G.mapping(z, c, truncation_psi=--trunc)`` call ``generate.py`` makes, or every row of
+  ``w`` in ``--projected-w`` as it is -- and every component k and step t, ``w[l] + sigma_t * scale_k * component_k`` on the ws indices of
+  ``--layers``, the other layers unchanged; ``sigma_t = range * (2 t - (T - 1)) / (T - 1)``, symmetric, the centre exactly 0, so the centre column is
+  the image ``generate.py`` writes.  ``--from=directions.npz`` skips the analysis and edits with a stored one, on other layers or latents.
+* ``directions.npz``: ``method``, ``components`` (fp32 [K, D]), ``eigenvalues`` (float64 [D], all of them, descending), ``stdev`` (fp32 [K],
+  sqrt(max(eigenvalue, 0))), ``mean`` (float64 [D]; zeros for sefa), ``total_variance`` (the eigenvalues' sum), ``layers``, ``num`` (rows analysed),
+  ``seed`` (-1 for sefa), ``sigmas``.
+* ``directions.json`` (strict JSON): ``method``, ``num``, ``w_dim``, ``num_ws``, ``layers``, ``sigmas``; per component ``eigenvalue``, ``stdev``,
+  ``explained`` (its share of the total variance) and ``cumulative``; ``effective_dim`` = (sum of eigenvalues)^2 / (sum of their squares) over all D:
+  how many directions W really uses.
+* ``seed<seed:04d>.png`` / ``w<i:02d>.png``: one grid per base latent, rows components, columns sigmas.
+
+    python -m style_big_gan_amd.directions exp.config_dir=<dir> exp.config=<file.yaml> --snapshot=<network-snapshot-*.pt> --outdir=<dir> \\
+        [--method=pca|sefa] [--num=65536] [--seed=0] [--components=8] [--layers=all|a-b|a,b,c] [--from=<directions.npz>] \\
+        [--seeds=0-3 | --projected-w=<projected_w.npz>] [--range=R] [--steps=5] [--trunc=1] [--class=<idx>] [--noise-mode=const|random|none] \\
+        [--device=auto|cuda|cpu] [--batch=64]
+"""
+import argparse
+import json
+import os
+
+import numpy as np
+import torch
+
+from .tool_support import (add_device_option, add_sampling_options, add_snapshot_option, class_label, config_overrides, device_of, load_generator, num_range,
+                           require_file, save_png, seed_latents, tool_device)
+from .torch_utils.ops import directions as ops, image_export
+
+METHODS = ('pca', 'sefa')
+DEFAULT_RANGE = dict(pca=2.0, sefa=3.0)
+
+
+def parse_layers(text, num_ws):
+    """'all' | 'a-b' | 'a,b,c' -> sorted ws indices, all below `num_ws`"""
+    layers = list(range(num_ws)) if text in (None, 'all') else sorted(set(num_range(text)))
+    if not layers or layers[-1] >= num_ws:
+        raise ValueError(f'--layers={text}: the generator has the ws indices 0 to {num_ws - 1}')
+    return layers
+
+
+def sigma_table(extent, steps):
+    """-> fp32 [T]: float32(float64(range) (2 t - (T - 1)) / (T - 1)), symmetric, the centre exactly 0; T = 1: the single value 0"""
+    steps = int(steps)
+    if steps < 1 or steps % 2 == 0:
+        raise ValueError(f'--steps={steps}: must be odd and at least 1')
+    if not float(extent) >= 0 or not np.isfinite(float(extent)):
+        raise ValueError(f'--range={extent}: must be finite and not negative')
+    if steps == 1:
+        return np.zeros([1], dtype=np.float32)
+    t = np.arange(steps, dtype=np.float64)
+    return (np.float64(extent) * (2 * t - (steps - 1)) / (steps - 1)).astype(np.float32)
+
+
+def eigen(matrix, components):
+    """float64 symmetric [D, D] -> (components fp32 [K, D], all eigenvalues float64 [D] descending, stdev fp32 [K]); every eigenvector's entry
+    of largest magnitude is positive, ties to the lowest index"""
+    matrix = np.asarray(matrix, dtype=np.float64)
+    values, vectors = np.linalg.eigh(matrix)
+    order = np.argsort(-values, kind='stable')
+    values, vectors = values[order], vectors[:, order].T            # rows: eigenvectors
+    kept = vectors[:components].copy()
+    for v in kept:
+        if v[np.argmax(np.abs(v))] < 0:
+            v *= -1
+    return kept.astype(np.float32), values, np.sqrt(np.maximum(values[:components], 0)).astype(np.float32)
+
+
+def require_w_space(G):
+    if not (hasattr(G, 'mapping') and hasattr(G, 'synthesis')):
+        raise ValueError('the directions tool needs a generator with mapping and synthesis networks')
+
+
+def sefa_rows(G, layers):
+    """-> fp32 [R, D] on the host: the style affines' weight rows of the convolutions whose ws index is in `layers`, each divided by its float64
+    l2 norm; ToRGB layers are left out"""
+    layers = set(layers)
+    rows = [affine.weight.detach().cpu().to(torch.float64).numpy() for name, affine, idx in G.synthesis.style_slots()
+            if idx in layers and not name.endswith('.torgb')]
+    if not rows:
+        raise ValueError(f'--layers={sorted(layers)}: no convolution takes its style from these ws indices (the last index feeds ToRGB alone, which '
+                         '--method=sefa leaves out)')
+    rows = np.concatenate(rows)
+    norm = np.sqrt((rows * rows).sum(axis=1, keepdims=True))
+    return (rows / np.where(norm > 0, norm, 1)).astype(np.float32)
+
+
+@torch.no_grad()
+def mapped_latents(G, num, seed, label, batch, device):
+    """-> fp32 [num, w_dim] on `device`: w = mapping(z) at psi = 1 of z = RandomState(seed).randn(num, z_dim), in batches"""
+    z = np.random.RandomState(seed).randn(num, G.z_dim)
+    out = []
+    for lo in range(0, num, batch):
+        zb = torch.from_numpy(z[lo:lo + batch]).to(device)
+        out.append(G.mapping(zb, label.expand(len(zb), -1), truncation_psi=1)[:, 0].to(torch.float32))
+    return torch.cat(out).contiguous()
+
+
+def analyse(G, method, layers, num, seed, components, class_idx, batch, device):
+    """-> the arrays of directions.npz without `sigmas`"""
+    if method == 'pca':
+        if num < 2:
+            raise ValueError(f'--num={num}: the principal components need at least 2 latents')
+        x = mapped_latents(G, num, seed, class_label(G, class_idx, device), batch, device)
+        mean = ops.column_mean(x)
+        matrix = ops.gram(x, mean.to(torch.float32)).cpu().numpy() / np.float64(num - 1)
+        mean = mean.cpu().numpy()
+    else:
+        x = torch.from_numpy(sefa_rows(G, layers)).to(device)
+        num, seed = x.shape[0], -1
+        matrix = ops.gram(x, None).cpu().numpy()
+        mean = np.zeros([x.shape[1]], dtype=np.float64)
+    comps, values, stdev = eigen(matrix, components)
+    return dict(method=np.array(method), components=comps, eigenvalues=values, stdev=stdev, mean=mean, total_variance=np.float64(values.sum()),
+                layers=np.asarray(layers, dtype=np.int64), num=np.int64(num), seed=np.int64(seed))
+
+
+def report(arrays, w_dim, num_ws):
+    """what directions.json holds"""
+    values = np.maximum(arrays['eigenvalues'], 0)
+    total, squares = float(values.sum()), float((values * values).sum())
+    share = [float(v) / total if total > 0 else 0.0 for v in values[:len(arrays['stdev'])]]
+    return dict(method=str(arrays['method']), num=int(arrays['num']), w_dim=int(w_dim), num_ws=int(num_ws), layers=[int(i) for i in arrays['layers']],
+                sigmas=[float(s) for s in arrays['sigmas']],
+                components=[dict(eigenvalue=float(arrays['eigenvalues'][k]), stdev=float(arrays['stdev'][k]), explained=share[k],
+                                 cumulative=float(sum(share[:k + 1]))) for k in range(len(share))],
+                effective_dim=total * total / squares if squares > 0 else 0.0)
+
+
+@torch.no_grad()
+def latent_directions(G, method='pca', num=65536, seed=0, components=8, layers=None, from_file=None, seeds=None, projected_w=None, extent=None, steps=5,
+                      truncation_psi=1, class_idx=None, noise_mode='const', batch=64, outdir=None, device=None):
+    """The analysis (or the stored one of `from_file`) and the edit grids of `seeds` or `projected_w` (a file name or an array [n, num_ws, w_dim]) ->
+    dict with `arrays` (what directions.npz holds), `stats` (what directions.json holds) and `grids` ({file name: uint8 [K H, T W, C]}).  With
+    `outdir` the files of the module docstring are written."""
+    require_w_space(G)
+    if seeds is not None and projected_w is not None:
+        raise ValueError('--seeds and --projected-w exclude one another')
+    if method not in METHODS:
+        raise ValueError(f'--method={method}: one of {", ".join(METHODS)}')
+    device = device_of(G, device)
+    batch, components = int(batch), int(components)
+    if batch < 1:
+        raise ValueError(f'--batch={batch}: must be at least 1')
+    w_dim, num_ws = int(G.w_dim), int(G.mapping.num_ws)
+    if from_file is not None:
+        with np.load(from_file) as f:
+            arrays = {k: f[k] for k in ('method', 'components', 'eigenvalues', 'stdev', 'mean', 'total_variance', 'layers', 'num', 'seed')}
+        if arrays['components'].ndim != 2 or arrays['components'].shape[1] != w_dim:
+            raise ValueError(f'--from={from_file}: components of shape {arrays["components"].shape} do not belong to a generator with w_dim {w_dim}')
+        method = str(arrays['method'])
+        arrays['layers'] = np.asarray(parse_layers(layers, num_ws) if layers is not None else [int(i) for i in arrays['layers']], dtype=np.int64)
+    else:
+        if not 1 <= components <= w_dim:
+            raise ValueError(f'--components={components}: must be between 1 and w_dim = {w_dim}')
+        arrays = analyse(G, method, parse_layers(layers, num_ws), int(num), int(seed), components, class_idx, batch, device)
+    sigmas = sigma_table(DEFAULT_RANGE[method] if extent is None else extent, steps)
+    arrays['sigmas'] = sigmas
+    stats = report(arrays, w_dim, num_ws)
+    if outdir is not None:
+        os.makedirs(outdir, exist_ok=True)
+        np.savez(os.path.join(outdir, 'directions.npz'), **arrays)
+        with open(os.path.join(outdir, 'directions.json'), 'w') as f:
+            json.dump(stats, f, indent=2, allow_nan=False)
+
+    # Base latents: the seeds through the mapping call generate.py makes, or the projected rows as they are.
+    names, base = [], None
+    if seeds is not None:
+        label = class_label(G, class_idx, device)
+        names = [f'seed{int(s):04d}.png' for s in seeds]
+        rows = [G.mapping(torch.from_numpy(seed_latents(G, [int(s)])).to(device), label, truncation_psi=truncation_psi) for s in seeds]
+        base = torch.cat(rows).to(torch.float32).contiguous() if rows else None
+    elif projected_w is not None:
+        if isinstance(projected_w, (str, os.PathLike)):
+            projected_w = np.load(projected_w)['w']
+        base = torch.as_tensor(projected_w).to(device).to(torch.float32).contiguous()
+        if base.ndim != 3 or tuple(base.shape[1:]) != (num_ws, w_dim):
+            raise ValueError(f'--projected-w: w of shape {tuple(base.shape)} does not belong to a generator with {num_ws} x {w_dim} latents')
+        names = [f'w{i:02d}.png' for i in range(base.shape[0])]
+
+    grids = {}
+    if names:
+        comps = torch.from_numpy(arrays['components']).to(device)
+        K, T = comps.shape[0], len(sigmas)
+        scale = torch.from_numpy(arrays['stdev'] if method == 'pca' else np.ones([K], dtype=np.float32)).to(device)
+        table = ops.edit_table(base, comps, scale, torch.from_numpy(sigmas).to(device), [int(i) for i in arrays['layers']])
+        for i, name in enumerate(names):
+            canvas = None
+            for lo in range(0, K * T, batch):
+                img = G.synthesis(table[i * K * T + lo:i * K * T + min(lo + batch, K * T)], noise_mode=noise_mode).to(torch.float32)
+                canvas = image_export.tile(img, (T, K), 'clamp', canvas=canvas, cell0=lo)
+            grids[name] = canvas.cpu().numpy()
+            if outdir is not None:
+                save_png(grids[name], os.path.join(outdir, name))
+    return dict(arrays=arrays, stats=stats, grids=grids)
+
+
+# ---------------------------------------------------------------------------------------------------------------- CLI
+
+def parse_args(argv=None):
+    """-> (config overrides as `key=value` strings, the tool's options)"""
+    ap = argparse.ArgumentParser(prog='python -m style_big_gan_amd.directions', description=__doc__.split('\n')[0])
+    add_snapshot_option(ap)
+    ap.add_argument('--outdir', required=True, help='where to save directions.npz / directions.json and the edit grids')
+    ap.add_argument('--method', choices=METHODS, default='pca', help='pca: GANSpace, principal components of sampled w; sefa: closed form, eigenvectors '
+                    'of the style affines (default: pca)')
+    ap.add_argument('--num', type=int, default=65536, help='latents sampled by --method=pca (default: 65536)')
+    ap.add_argument('--seed', type=int, default=0, help='seed of the sampled latents (default: 0)')
+    ap.add_argument('--components', type=int, default=8, help='directions kept, at most w_dim (default: 8)')
+    ap.add_argument('--layers', help='ws indices edited (and, for sefa, analysed): all | a-b | a,b,c (default: all, or those of --from)')
+    ap.add_argument('--from', dest='from_file', help='a directions.npz: skip the analysis and only make edits')
+    ap.add_argument('--seeds', type=num_range, help='seeds whose images are edited')
+    ap.add_argument('--projected-w', help='edit every row of w in this projected_w.npz of the projector (no truncation)')
+    ap.add_argument('--range', dest='extent', type=float, help='largest step: standard deviations of the component for pca (default: 2), a plain '
+                    'distance in W for sefa, whose scale is 1 (default: 3)')
+    ap.add_argument('--steps', type=int, default=5, help='columns of a grid, odd; the centre is the unedited image (default: 5)')
+    add_sampling_options(ap)
+    add_device_option(ap)
+    ap.add_argument('--batch', type=int, default=64, help='latents mapped and images synthesised at a time (default: 64)')
+    args, rest = ap.parse_known_args(argv)
+    if args.seeds is not None and args.projected_w is not None:
+        ap.error('--seeds and --projected-w exclude one another')
+    if args.steps < 1 or args.steps % 2 == 0:
+        ap.error(f'--steps={args.steps}: must be odd and at least 1')
+    if args.components < 1:
+        ap.error(f'--components={args.components}: must be at least 1')
+    if args.num < 2:
+        ap.error(f'--num={args.num}: must be at least 2')
+    if args.batch < 1:
+        ap.error(f'--batch={args.batch}: must be at least 1')
+    if args.extent is not None and not (args.extent >= 0 and np.isfinite(args.extent)):
+        ap.error(f'--range={args.extent}: must be finite and not negative')
+    require_file(ap, '--snapshot', args.snapshot)
+    require_file(ap, '--from', args.from_file)
+    require_file(ap, '--projected-w', args.projected_w)
+    return config_overrides(ap, rest), args
+
+
+def run_directions(argv=None):
+    overrides, args = parse_args(argv)
+    from . import arguments
+    config = arguments.load_config(overrides)
+    device = tool_device(args.device)
+    G = load_generator(config, args.snapshot, device)
+    result = latent_directions(G, method=args.method, num=args.num, seed=args.seed, components=args.components, layers=args.layers,
+                               from_file=args.from_file, seeds=args.seeds, projected_w=args.projected_w, extent=args.extent, steps=args.steps,
+                               truncation_psi=args.truncation_psi, class_idx=args.class_idx, noise_mode=args.noise_mode, batch=args.batch,
+                               outdir=args.outdir, device=device)
+    print(json.dumps(result['stats'], allow_nan=False))
+    return result
+
+
+if __name__ == '__main__':
+    run_directions()

@@ -1,4 +1,4 @@
-"""What the snapshot tools (generate, style_mixing, projector, calc_metrics, nearest_neighbors, avg_spectra, diversity, realism) share, each piece once: a
+"""What the nine snapshot tools (generate, style_mixing, projector, calc_metrics, nearest_neighbors, avg_spectra, diversity, realism, directions) share, each piece once: a
 generator built from the run's config and a ``network-snapshot-*.pt`` of this build (written by ``BaseTrainer.save_snapshot``), the ``key=value`` config
 overrides ``starter`` takes, the options several tools declare alike, the device and the data set of a run, the class label, the seeded latents,
 the bytes of generated images and the ``vgg16.pt`` features of a data set.  What a tool validates and the options whose help differs per tool stay

@@ -580,6 +580,20 @@ class SynthesisNetwork(torch.nn.Module):
             img = misc.cat0(imgs)
         return img
 
+    def style_slots(self):
+        """yields (layer name, affine module, ws index) of every styled layer in forward order: the indexing `_style_bank` walks (read-only;
+        a block's ToRGB shares its ws index with the next block's first convolution)"""
+        w_idx = 0
+        for res in self.block_resolutions:
+            block = getattr(self, f'b{res}')
+            has0 = block.in_channels != 0
+            if has0:
+                yield f'b{res}.conv0', block.conv0.affine, w_idx
+            yield f'b{res}.conv1', block.conv1.affine, w_idx + (1 if has0 else 0)
+            if block.num_torgb:
+                yield f'b{res}.torgb', block.torgb.affine, w_idx + block.num_conv
+            w_idx += block.num_conv
+
     def _style_bank(self, ws):
         """every layer's styles of this pass from ONE launch (torch_utils/ops/grouped_gemm.py) instead of one addmm per layer (reference :333, :397), its
         backward two launches instead of two GEMMs and a reduction per layer.  First-order passes and inference only (the switch the fused synthesis
