@@ -719,6 +719,23 @@ int sbg_directions_edit(const float* ws, const float* comps, const float* scale,
                         int S, int L, int D, int K, int T, sbg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * k-means centroid update on uint8 rows (modes.py: the number of statistically different bins, Richardson & Weiss, NeurIPS 2018; the
+ * reference has no counterpart; csrc/kmeans_u8.hip).  points uint8 [N, F], labels int32 [N], old_centroids and
+ * centroids uint8 [K, F], sums int64 [K, F], counts int64 [K], all dense:
+ *   counts[k] = the number of rows with labels[n] == k;  sums[k, f] = the int64 sum of points[n, f] over those rows;
+ *   centroids[k, f] = (2 sums[k, f] + counts[k]) / (2 counts[k]) in integer division (the mean rounded half up); an empty cluster keeps
+ *   old_centroids[k] and has a sums row of 0.  A row whose label lies outside [0, K) is skipped (the caller's error; nothing is written
+ *   out of bounds for it).  Integer arithmetic only: the result depends on the inputs alone; no floating point, no global atomics.
+ * Limits: 1 <= N <= 2^24, 1 <= K <= 256, F a multiple of 16 and at most 3 * 2^20; points, old_centroids, centroids, sums and workspace
+ * 16-byte aligned, counts 8, labels 4.  A refused call (bad sizes, a null or misaligned pointer) launches nothing, returns
+ * SBG_ERR_INVALID and names the shape in sbg_last_error().  sbg_kmeans_u8_update_workspace(N, F, K) bytes of workspace = 4 * chunks * K * (F + 1)
+ * for the i32 partial sums and counts of the row chunks (-1: unsupported sizes); chunks is chosen so that column tiles x chunks fills the
+ * chip and is 1 once F / tile alone does (100 MB at N = 2^17, F = 196608, K = 128).  Two launches: accumulate, finish. */
+int64_t sbg_kmeans_u8_update_workspace(int64_t N, int64_t F, int K);
+int sbg_kmeans_u8_update(const uint8_t* points, const int32_t* labels, const uint8_t* old_centroids, uint8_t* centroids, int64_t* sums,
+                         int64_t* counts, void* workspace, int64_t N, int64_t F, int K, sbg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * In-process launch timing (measurement only; bench.py's roofline figures come from here).
  * While enabled, every kernel launch of this library is bracketed by two hipEvents recorded on the launch stream
  * and logged with its algorithmic flops / bytes.  sbg_prof_fetch() synchronises the logged events, writes up to `max`
@@ -746,8 +763,9 @@ enum sbg_kernel_kind {
                                  * 4 project (M, K, D) / 5 l1 (D, M, chunks) / 6 merge of the float64 partials (values, chunks); M clipped to INT32_MAX */
     SBG_K_SPECTRUM = 28,        /* dims[0] = variant: 0 rows / 1 cols; then BC (image-channels of the call), R, S */
     SBG_K_MSSSIM = 29,          /* dims[0] = variant: 0 level / 1 down / 2 merge; then BC (image-channels of the call, clipped to INT32_MAX), S */
-    SBG_K_DIRECTIONS = 30       /* dims[0] = variant: 0 mean (N, D, chunks) / 1 gram (N, D, groups) / 2 merge (N, D, chunks or groups: the launch
+    SBG_K_DIRECTIONS = 30,      /* dims[0] = variant: 0 mean (N, D, chunks) / 1 gram (N, D, groups) / 2 merge (N, D, chunks or groups: the launch
                                  * it finishes) / 3 edit (S, K, T, L, D); N clipped to INT32_MAX */
+    SBG_K_KMEANS_U8 = 31        /* dims[0] = variant: 0 accumulate / 1 finish; then N, F (both clipped to INT32_MAX), K, row chunks, lanes per row */
 };
 /* Kernel-variant codes in the records of the streaming kernels (which kernel served the launch):
  *   bias_act     dims[4] = 1 vec8 / 2 scalar,  dims[5] = bias mode (0 none, 1 channel-minor vector, 2 one per 8-vector, 3 generic)

@@ -46,41 +46,15 @@ import os
 import numpy as np
 import torch
 
-from .tool_support import (add_device_option, add_sampling_options, add_snapshot_option, checked_features, class_label, config_overrides,  # noqa: F401
-                           dataset_features, dataset_kwargs_for, detector_kwargs, device_of, generated_images, load_generator, num_range, open_dataset,
-                           require_file, save_png, snapshot_generator_state, tool_device, vgg16_feature_options)
-from .torch_utils.ops import knn_manifold, nn_u8, resample_u8, resident_set
+from .tool_support import (STORE_CHUNK_BYTES, add_device_option, add_sampling_options, add_snapshot_option, check_res, checked_features,  # noqa: F401
+                           class_label, config_overrides, dataset_features, dataset_kwargs_for, detector_kwargs, device_of, generated_images, load_generator,
+                           num_range, open_dataset, reduce_images, reduce_store, require_file, save_png, snapshot_generator_state, tool_device,
+                           vgg16_feature_options)
+from .torch_utils.ops import knn_manifold, nn_u8, resident_set
 
 SPACES = ('pixel', 'vgg16')
 QUANTILES = (0.01, 0.05, 0.25, 0.50, 0.75)
-STORE_CHUNK_BYTES = 256 << 20           # full-size store bytes reduced (--res) or searched as queries (the baseline) at a time
 _ROW_BITS = 24                          # nn_u8's row limit: (d2, flip, row) as one int64 key
-
-
-def check_res(res, resolution):
-    """--res: a power of two in [4, the data resolution]; None keeps the full size"""
-    if res is None:
-        return None
-    res = int(res)
-    if res < 4 or res & (res - 1) or res > resolution:
-        raise ValueError(f'--res={res}: must be a power of two, at least 4 and at most the data resolution {resolution}')
-    return None if res == resolution else res
-
-
-def reduce_images(images, res):
-    """uint8 [N, C, H, W] -> its box-reduced copy [N, C, res, res] (the exact uint8 box filter of resample_u8)"""
-    if res is None:
-        return images
-    out = resample_u8.resize(images.permute(0, 2, 3, 1).contiguous(), res, res, 'box')
-    return out.permute(0, 3, 1, 2).contiguous()
-
-
-def reduce_store(store, res):
-    """the whole store reduced once, in chunks of at most STORE_CHUNK_BYTES"""
-    if res is None:
-        return store
-    rows = max(1, STORE_CHUNK_BYTES // max(store[0].numel(), 1))
-    return torch.cat([reduce_images(store[lo:lo + rows], res) for lo in range(0, store.shape[0], rows)])
 
 
 def item_table(slot, flip, rows):

@@ -1,8 +1,8 @@
-"""What the nine snapshot tools (generate, style_mixing, projector, calc_metrics, nearest_neighbors, avg_spectra, diversity, realism, directions) share, each piece once: a
-generator built from the run's config and a ``network-snapshot-*.pt`` of this build (written by ``BaseTrainer.save_snapshot``), the ``key=value`` config
-overrides ``starter`` takes, the options several tools declare alike, the device and the data set of a run, the class label, the seeded latents,
-the bytes of generated images and the ``vgg16.pt`` features of a data set.  What a tool validates and the options whose help differs per tool stay
-in the tool."""
+"""What the ten snapshot tools (generate, style_mixing, projector, calc_metrics, nearest_neighbors, avg_spectra, diversity, realism, directions, modes) share,
+each piece once: a generator built from the run's config and a ``network-snapshot-*.pt`` of this build (written by ``BaseTrainer.save_snapshot``), the
+``key=value`` config overrides ``starter`` takes, the options several tools declare alike, the device and the data set of a run, the class label, the
+seeded latents, the bytes of generated images, the box reduction behind ``--res`` and the ``vgg16.pt`` features of a data set.  What a tool validates
+and the options whose help differs per tool stay in the tool."""
 import contextlib
 import os
 import re
@@ -10,9 +10,10 @@ import re
 import numpy as np
 import torch
 
-from .torch_utils.ops import image_export
+from .torch_utils.ops import image_export, resample_u8
 
 NOISE_MODES = ('const', 'random', 'none')
+STORE_CHUNK_BYTES = 256 << 20           # full-size store bytes reduced (--res) or searched as queries (nearest_neighbors' baseline) at a time
 SNAPSHOT_HELP = 'network-snapshot-*.pt of this build (G_ema, or G when there is no EMA)'
 
 
@@ -197,6 +198,32 @@ def generated_images(G, seeds, label, truncation_psi, noise_mode, device):
     z = torch.from_numpy(seed_latents(G, seeds)).to(device)
     img = G(z, label.expand(len(seeds), -1), truncation_psi=truncation_psi, noise_mode=noise_mode)
     return image_export.quantize(img.to(torch.float32), 'clamp').permute(0, 3, 1, 2).contiguous()
+
+
+def check_res(res, resolution):
+    """--res: a power of two in [4, the data resolution]; None keeps the full size"""
+    if res is None:
+        return None
+    res = int(res)
+    if res < 4 or res & (res - 1) or res > resolution:
+        raise ValueError(f'--res={res}: must be a power of two, at least 4 and at most the data resolution {resolution}')
+    return None if res == resolution else res
+
+
+def reduce_images(images, res):
+    """uint8 [N, C, H, W] -> its box-reduced copy [N, C, res, res] (the exact uint8 box filter of resample_u8)"""
+    if res is None:
+        return images
+    out = resample_u8.resize(images.permute(0, 2, 3, 1).contiguous(), res, res, 'box')
+    return out.permute(0, 3, 1, 2).contiguous()
+
+
+def reduce_store(store, res):
+    """the whole store reduced once, in chunks of at most STORE_CHUNK_BYTES"""
+    if res is None:
+        return store
+    rows = max(1, STORE_CHUNK_BYTES // max(store[0].numel(), 1))
+    return torch.cat([reduce_images(store[lo:lo + rows], res) for lo in range(0, store.shape[0], rows)])
 
 
 def save_png(img, path):
