@@ -221,7 +221,9 @@ int sbg_moments_hw(const void* x, float* r, int dtype, int N, int C, int64_t HW,
  * pass in the reference.  Problem p:  C[m][n] = sum_{t < nterms} alpha_t * sum_k A_t[m][k] B_t[k][n]  (+ bias[n] * bias_scale),
  * every operand addressed by element strides (row stride, column stride), so transposes and slices of larger tensors cost nothing;
  * `rowsum` (optional): rowsum[m] = rowsum_scale * sum_k A_0[m][k]  (the bias gradient next to the weight gradient).
- * fp32, fixed summation order (ascending k, term 0 then term 1).  Outputs of different problems must not overlap. */
+ * fp32, fixed summation order (ascending k, term 0 then term 1).  Outputs of different problems must not overlap.
+ * Empty extents are served: a problem with M = 0 or N = 0 writes nothing, a term with K = 0 adds nothing (C is then the bias or zeros);
+ * the pointers of such empty tensors may be NULL. */
 typedef struct sbg_gg_problem {
     const float *a0, *b0, *a1, *b1;         /* term 1 is ignored when nterms == 1 */
     float* c; const float* bias; float* rowsum;
@@ -297,8 +299,9 @@ int sbg_split_bf16_cat_nd(const float* x, const int64_t* shape, const int64_t* x
  * Exact-fp32 matrix-core kernel (v_mfma_f32_16x16x4_f32); the [Q, M] attention map never touches HBM.
  * M <= 256: the whole key strip of a wave's 16 queries is held at once (M / 16 in {1, 2, 4, 8, 16}).  M > 256: the keys are walked in chunks
  * with a running maximum, sum and output per row (online softmax), one division at the end; any M % 16 == 0.
- * Supported: Q % 16 == 0, M % 16 == 0, D % 4 == 0, DV % 16 == 0, and for M > 256 per-sample matrices of at most 2^31 - 1 elements
- * (M * max(D, DV), Q * max(D, DV)) (sbg_attention_supported). */
+ * Supported (sbg_attention_supported returns 1 for exactly the shapes sbg_attention_fwd serves): Q % 16 == 0, M % 16 == 0, D % 4 == 0,
+ * DV % 16 == 0; for M <= 256, M / 16 in {1, 2, 4, 8, 16} (M = 48, 80, 96, ... 240 are refused); for M > 256, per-sample matrices of at most
+ * 2^31 - 1 elements (M * max(D, DV), Q * max(D, DV)). */
 int sbg_attention_supported(int Q, int M, int D, int DV);
 int sbg_attention_fwd(const float* theta, const float* phi, const float* g, float* out, int N, int Q, int M, int D, int DV,
                       sbg_stream_t stream);
@@ -308,7 +311,8 @@ int sbg_attention_fwd(const float* theta, const float* phi, const float* g, floa
  * queries stays inside one wave (fixed order).  workspace: sbg_attention_bwd_workspace(N, Q) bytes of row statistics.
  * M > 256 takes three launches: the forward recomputed in registers for lse and delta = rowsum(dout o out) (nothing of the forward is saved),
  * dtheta streamed over the key chunks from those statistics, then the same per-key-tile pass as M <= 256.
- * Supported: the forward's shapes with D <= 64 and DV / 16 in {1, 2, 4, 8, 16} (sbg_attention_bwd_supported). */
+ * Supported (sbg_attention_bwd_supported): the forward's shapes with ceil(D / 16) in {1, 2, 4} (D <= 16, 20 .. 32, 52 .. 64) and
+ * DV / 16 in {1, 2, 4, 8, 16}. */
 int sbg_attention_bwd_supported(int Q, int M, int D, int DV);
 int64_t sbg_attention_bwd_workspace(int N, int Q);
 int sbg_attention_bwd(const float* theta, const float* phi, const float* g, const float* dout, float* dtheta, float* dphi, float* dg,

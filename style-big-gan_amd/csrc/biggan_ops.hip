@@ -10,6 +10,7 @@
 //  * attention_fwd_stream_kernel / attention_bwd_dq_stream_kernel: the same wave-per-16-queries structure for any number of keys,
 //    walking them in chunks with a running (max, sum, output) per row; the [Q, M] map still never reaches HBM.
 #include "sbg_common.h"
+#include <type_traits>
 
 namespace {
 
@@ -87,6 +88,26 @@ __global__ __launch_bounds__(256) void sn_ufinish_kernel(const float* t, float* 
 
 // ---------------------------------------------------------------------------------------------------------------- attention
 #define ATT_MAX_M 256
+
+// The tile counts the attention kernels are instantiated for: 1, 2, 4, 8, 16, up to MAXT (M / 16 key tiles of the single-chunk kernels, DV / 16
+// output tiles, ceil(D / 16) column tiles with MAXT = 4).  This switch is the only list of them: the launchers dispatch through it and the
+// shape predicates ask it (att_tiles_dispatched), so a shape the predicates accept is a shape the launchers serve.
+// f(std::integral_constant<int, T>) -> status; ATT_NO_TILES for a count that has no instantiation.
+#define ATT_NO_TILES (-1)
+template <int MAXT, class F>
+static int att_for_tiles(int tiles, F&& f)
+{
+    switch (tiles) {
+        case 1:  return f(std::integral_constant<int, 1>{});
+        case 2:  if constexpr (MAXT >= 2) return f(std::integral_constant<int, 2>{}); else return ATT_NO_TILES;
+        case 4:  if constexpr (MAXT >= 4) return f(std::integral_constant<int, 4>{}); else return ATT_NO_TILES;
+        case 8:  if constexpr (MAXT >= 8) return f(std::integral_constant<int, 8>{}); else return ATT_NO_TILES;
+        case 16: if constexpr (MAXT >= 16) return f(std::integral_constant<int, 16>{}); else return ATT_NO_TILES;
+        default: return ATT_NO_TILES;
+    }
+}
+template <int MAXT>
+static bool att_tiles_dispatched(int tiles) { return att_for_tiles<MAXT>(tiles, [](auto) { return (int)SBG_OK; }) == SBG_OK; }
 
 template <int MT>   // MT = M / 16 key tiles held in accumulators
 __global__ __launch_bounds__(256) void attention_fwd_kernel(const float* theta, const float* phi, const float* g, float* out,
@@ -501,14 +522,9 @@ template <bool STATS>
 static int launch_att_stream_dvt(int dvt, const float* theta, const float* phi, const float* g, const float* dout, float* out, float* lse, float* delta,
                                  int N, int Q, int M, int D, int DV, hipStream_t s)
 {
-    switch (dvt) {
-        case 1:  return launch_att_stream<1, STATS>(theta, phi, g, dout, out, lse, delta, N, Q, M, D, DV, s);
-        case 2:  return launch_att_stream<2, STATS>(theta, phi, g, dout, out, lse, delta, N, Q, M, D, DV, s);
-        case 4:  return launch_att_stream<4, STATS>(theta, phi, g, dout, out, lse, delta, N, Q, M, D, DV, s);
-        case 8:  return launch_att_stream<8, STATS>(theta, phi, g, dout, out, lse, delta, N, Q, M, D, DV, s);
-        case 16: return launch_att_stream<16, STATS>(theta, phi, g, dout, out, lse, delta, N, Q, M, D, DV, s);
-        default: return sbg_fail(SBG_ERR_UNSUPPORTED, "attention (streamed): %d output tiles per workgroup", dvt);
-    }
+    const int rc = att_for_tiles<16>(dvt, [&](auto t) {
+        return launch_att_stream<decltype(t)::value, STATS>(theta, phi, g, dout, out, lse, delta, N, Q, M, D, DV, s); });
+    return rc == ATT_NO_TILES ? sbg_fail(SBG_ERR_UNSUPPORTED, "attention (streamed): %d output tiles per workgroup", dvt) : rc;
 }
 
 template <int DT>
@@ -562,7 +578,7 @@ extern "C" int sbg_sn_power_iteration(const float* W, const float* u, float* v, 
 extern "C" int sbg_attention_supported(int Q, int M, int D, int DV)
 {
     if (!(Q >= 16 && Q % 16 == 0 && M >= 16 && M % 16 == 0 && D >= 4 && D % 4 == 0 && DV >= 16 && DV % 16 == 0)) return 0;
-    if (M <= ATT_MAX_M) return 1;
+    if (M <= ATT_MAX_M) return att_tiles_dispatched<16>(M / 16) ? 1 : 0;     // the whole key strip at once: M / 16 must be an instantiated MT
     // streamed form: any M whose per-sample matrices keep 32-bit element counts (sample bases are 64-bit)
     const int64_t w = D > DV ? D : DV;
     return ((int64_t)M * w <= INT32_MAX && (int64_t)Q * w <= INT32_MAX) ? 1 : 0;
@@ -583,19 +599,24 @@ static int launch_att_bwd_dkv(const float* theta, const float* phi, const float*
                               float* dphi, float* dg, int N, int Q, int M, int D, int DV, hipStream_t s)
 {
     const dim3 grid((M + 63) / 64, N);
-    switch ((D + 15) / 16) {
-        case 1: SBG_LAUNCH((attention_bwd_dkv_kernel<DVT, 1>), grid, dim3(256), 0, s, theta, phi, g, dout, lse, delta, dphi, dg, Q, M, D, DV); break;
-        case 2: SBG_LAUNCH((attention_bwd_dkv_kernel<DVT, 2>), grid, dim3(256), 0, s, theta, phi, g, dout, lse, delta, dphi, dg, Q, M, D, DV); break;
-        case 4: SBG_LAUNCH((attention_bwd_dkv_kernel<DVT, 4>), grid, dim3(256), 0, s, theta, phi, g, dout, lse, delta, dphi, dg, Q, M, D, DV); break;
-        default: return sbg_fail(SBG_ERR_UNSUPPORTED, "attention_bwd: D = %d needs 1, 2 or 4 column tiles of 16", D);
-    }
-    return SBG_OK;
+    const int rc = att_for_tiles<4>((D + 15) / 16, [&](auto t) -> int {
+        SBG_LAUNCH((attention_bwd_dkv_kernel<DVT, decltype(t)::value>), grid, dim3(256), 0, s, theta, phi, g, dout, lse, delta, dphi, dg, Q, M, D, DV);
+        return (int)SBG_OK; });
+    return rc == ATT_NO_TILES ? sbg_fail(SBG_ERR_UNSUPPORTED, "attention_bwd: D = %d needs 1, 2 or 4 column tiles of 16", D) : rc;
+}
+
+// both directions' per-key-tile pass: DV / 16 output tiles
+static int launch_att_bwd_dkv_dvt(const float* theta, const float* phi, const float* g, const float* dout, const float* lse, const float* delta,
+                                  float* dphi, float* dg, int N, int Q, int M, int D, int DV, hipStream_t s)
+{
+    const int rc = att_for_tiles<16>(DV / 16, [&](auto t) {
+        return launch_att_bwd_dkv<decltype(t)::value>(theta, phi, g, dout, lse, delta, dphi, dg, N, Q, M, D, DV, s); });
+    return rc == ATT_NO_TILES ? sbg_fail(SBG_ERR_UNSUPPORTED, "attention_bwd: DV / 16 must be 1, 2, 4, 8 or 16 (got DV = %d)", DV) : rc;
 }
 
 extern "C" int sbg_attention_bwd_supported(int Q, int M, int D, int DV)
 {
-    const int dt = (D + 15) / 16, dvt = DV / 16;
-    return (sbg_attention_supported(Q, M, D, DV) && (dt == 1 || dt == 2 || dt == 4) && (dvt == 1 || dvt == 2 || dvt == 4 || dvt == 8 || dvt == 16)) ? 1 : 0;
+    return (sbg_attention_supported(Q, M, D, DV) && att_tiles_dispatched<4>((D + 15) / 16) && att_tiles_dispatched<16>(DV / 16)) ? 1 : 0;
 }
 
 extern "C" int64_t sbg_attention_bwd_workspace(int N, int Q) { return 2 * (int64_t)N * Q * (int64_t)sizeof(float); }
@@ -614,24 +635,14 @@ static int attention_bwd_stream(const float* theta, const float* phi, const floa
     if (rc != SBG_OK) return rc;
     {
         SbgProfScope prof(s, SBG_K_ATTENTION, qm * (2.0 * D + DV), 4.0 * N * (2.0 * qd + mk + qv + 2.0 * Q), {N, Q, M, D, DV, 1, ATT_V_STREAM_DQ});
-        switch ((D + 15) / 16) {
-            case 1: rc = launch_att_bwd_dq_stream<1>(theta, phi, g, dout, lse, delta, dtheta, N, Q, M, D, DV, s); break;
-            case 2: rc = launch_att_bwd_dq_stream<2>(theta, phi, g, dout, lse, delta, dtheta, N, Q, M, D, DV, s); break;
-            case 4: rc = launch_att_bwd_dq_stream<4>(theta, phi, g, dout, lse, delta, dtheta, N, Q, M, D, DV, s); break;
-            default: rc = sbg_fail(SBG_ERR_UNSUPPORTED, "attention_bwd: D = %d needs 1, 2 or 4 column tiles of 16", D);
-        }
+        rc = att_for_tiles<4>((D + 15) / 16, [&](auto t) {
+            return launch_att_bwd_dq_stream<decltype(t)::value>(theta, phi, g, dout, lse, delta, dtheta, N, Q, M, D, DV, s); });
+        if (rc == ATT_NO_TILES) rc = sbg_fail(SBG_ERR_UNSUPPORTED, "attention_bwd: D = %d needs 1, 2 or 4 column tiles of 16", D);
     }
     if (rc != SBG_OK) return rc;
     {
         SbgProfScope prof(s, SBG_K_ATTENTION, qm * (2.0 * D + 2.0 * DV), 4.0 * N * (qd + qv + 2.0 * mk + 2.0 * Q), {N, Q, M, D, DV, 1, ATT_V_STREAM_DKV});
-        switch (DV / 16) {
-            case 1:  rc = launch_att_bwd_dkv<1>(theta, phi, g, dout, lse, delta, dphi, dg, N, Q, M, D, DV, s); break;
-            case 2:  rc = launch_att_bwd_dkv<2>(theta, phi, g, dout, lse, delta, dphi, dg, N, Q, M, D, DV, s); break;
-            case 4:  rc = launch_att_bwd_dkv<4>(theta, phi, g, dout, lse, delta, dphi, dg, N, Q, M, D, DV, s); break;
-            case 8:  rc = launch_att_bwd_dkv<8>(theta, phi, g, dout, lse, delta, dphi, dg, N, Q, M, D, DV, s); break;
-            case 16: rc = launch_att_bwd_dkv<16>(theta, phi, g, dout, lse, delta, dphi, dg, N, Q, M, D, DV, s); break;
-            default: rc = sbg_fail(SBG_ERR_UNSUPPORTED, "attention_bwd: DV / 16 must be 1, 2, 4, 8 or 16 (got DV = %d)", DV);
-        }
+        rc = launch_att_bwd_dkv_dvt(theta, phi, g, dout, lse, delta, dphi, dg, N, Q, M, D, DV, s);
     }
     if (rc != SBG_OK) return rc;
     SBG_HIP_LAUNCH_CHECK();
@@ -650,24 +661,11 @@ extern "C" int sbg_attention_bwd(const float* theta, const float* phi, const flo
     float* delta = lse + (int64_t)N * Q;
     if (M > ATT_MAX_M) return attention_bwd_stream(theta, phi, g, dout, dtheta, dphi, dg, lse, delta, N, Q, M, D, DV, s);
     SbgProfScope prof(s, SBG_K_ATTENTION, 2.0 * N * (double)Q * M * (3.0 * D + 3.0 * DV), 4.0 * N * (2.0 * Q * D + 2.0 * M * (D + DV) + 2.0 * Q * DV), {N, Q, M, D, DV, 1});
-    int rc = SBG_OK;
-    switch (M / 16) {
-        case 1:  rc = launch_att_bwd_dq<1>(theta, phi, g, dout, dtheta, lse, delta, N, Q, M, D, DV, s); break;
-        case 2:  rc = launch_att_bwd_dq<2>(theta, phi, g, dout, dtheta, lse, delta, N, Q, M, D, DV, s); break;
-        case 4:  rc = launch_att_bwd_dq<4>(theta, phi, g, dout, dtheta, lse, delta, N, Q, M, D, DV, s); break;
-        case 8:  rc = launch_att_bwd_dq<8>(theta, phi, g, dout, dtheta, lse, delta, N, Q, M, D, DV, s); break;
-        case 16: rc = launch_att_bwd_dq<16>(theta, phi, g, dout, dtheta, lse, delta, N, Q, M, D, DV, s); break;
-        default: return sbg_fail(SBG_ERR_UNSUPPORTED, "attention_bwd: M / 16 must be 1, 2, 4, 8 or 16 (got M = %d)", M);
-    }
+    int rc = att_for_tiles<16>(M / 16, [&](auto t) {
+        return launch_att_bwd_dq<decltype(t)::value>(theta, phi, g, dout, dtheta, lse, delta, N, Q, M, D, DV, s); });
+    if (rc == ATT_NO_TILES) return sbg_fail(SBG_ERR_UNSUPPORTED, "attention_bwd: M / 16 must be 1, 2, 4, 8 or 16 (got M = %d)", M);
     if (rc != SBG_OK) return rc;
-    switch (DV / 16) {
-        case 1:  rc = launch_att_bwd_dkv<1>(theta, phi, g, dout, lse, delta, dphi, dg, N, Q, M, D, DV, s); break;
-        case 2:  rc = launch_att_bwd_dkv<2>(theta, phi, g, dout, lse, delta, dphi, dg, N, Q, M, D, DV, s); break;
-        case 4:  rc = launch_att_bwd_dkv<4>(theta, phi, g, dout, lse, delta, dphi, dg, N, Q, M, D, DV, s); break;
-        case 8:  rc = launch_att_bwd_dkv<8>(theta, phi, g, dout, lse, delta, dphi, dg, N, Q, M, D, DV, s); break;
-        case 16: rc = launch_att_bwd_dkv<16>(theta, phi, g, dout, lse, delta, dphi, dg, N, Q, M, D, DV, s); break;
-        default: return sbg_fail(SBG_ERR_UNSUPPORTED, "attention_bwd: DV / 16 must be 1, 2, 4, 8 or 16 (got DV = %d)", DV);
-    }
+    rc = launch_att_bwd_dkv_dvt(theta, phi, g, dout, lse, delta, dphi, dg, N, Q, M, D, DV, s);
     if (rc != SBG_OK) return rc;
     SBG_HIP_LAUNCH_CHECK();
     return SBG_OK;
@@ -692,14 +690,8 @@ extern "C" int sbg_attention_fwd(const float* theta, const float* phi, const flo
         SBG_HIP_LAUNCH_CHECK();
         return SBG_OK;
     }
-    switch (M / 16) {
-        case 1:  rc = launch_att<1>(theta, phi, g, out, N, Q, M, D, DV, s); break;
-        case 2:  rc = launch_att<2>(theta, phi, g, out, N, Q, M, D, DV, s); break;
-        case 4:  rc = launch_att<4>(theta, phi, g, out, N, Q, M, D, DV, s); break;
-        case 8:  rc = launch_att<8>(theta, phi, g, out, N, Q, M, D, DV, s); break;
-        case 16: rc = launch_att<16>(theta, phi, g, out, N, Q, M, D, DV, s); break;
-        default: return sbg_fail(SBG_ERR_UNSUPPORTED, "attention_fwd: M / 16 must be 1, 2, 4, 8 or 16 (got M = %d)", M);
-    }
+    rc = att_for_tiles<16>(M / 16, [&](auto t) { return launch_att<decltype(t)::value>(theta, phi, g, out, N, Q, M, D, DV, s); });
+    if (rc == ATT_NO_TILES) return sbg_fail(SBG_ERR_UNSUPPORTED, "attention_fwd: M / 16 must be 1, 2, 4, 8 or 16 (got M = %d)", M);
     if (rc != SBG_OK) return rc;
     SBG_HIP_LAUNCH_CHECK();
     return SBG_OK;

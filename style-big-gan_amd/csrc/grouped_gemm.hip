@@ -115,7 +115,11 @@ extern "C" int sbg_grouped_gemm(const sbg_gg_problem* problems, int count, sbg_s
     if (count < 0 || (count > 0 && !problems)) return sbg_fail(SBG_ERR_INVALID, "sbg_grouped_gemm: null table");
     for (int i = 0; i < count; i++) {
         const sbg_gg_problem& q = problems[i];
-        if (q.M < 0 || q.N < 0 || q.nterms < 1 || q.nterms > 2 || q.K0 < 0 || (q.nterms == 2 && q.K1 < 0) || !q.c || !q.a0 || !q.b0 || (q.nterms == 2 && (!q.a1 || !q.b1)))
+        if (q.M < 0 || q.N < 0 || q.nterms < 1 || q.nterms > 2 || q.K0 < 0 || (q.nterms == 2 && q.K1 < 0))
+            return sbg_fail(SBG_ERR_INVALID, "sbg_grouped_gemm: malformed problem");
+        // a pointer is needed only where elements are read or written: an empty tensor (M = 0, N = 0, or an operand with K = 0) has none
+        const bool writes = q.M > 0 && q.N > 0;
+        if (writes && (!q.c || (q.K0 > 0 && (!q.a0 || !q.b0)) || (q.nterms == 2 && q.K1 > 0 && (!q.a1 || !q.b1))))
             return sbg_fail(SBG_ERR_INVALID, "sbg_grouped_gemm: malformed problem");
     }
     for (int i = 0; i < count;) {
