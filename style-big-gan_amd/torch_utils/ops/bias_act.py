@@ -5,6 +5,8 @@ Host-side mirror of the reference op ``stylegan2ada/torch_utils/ops/bias_act.py`
 ``sbg_bias_act`` (csrc/bias_act.hip).  First and second derivatives are autograd Functions built on the same
 kernel (grad = 1, 2), so R1 / path-length double-backward works as in the reference (:129-210).
 """
+import typing
+
 import numpy as np
 import torch
 
@@ -34,25 +36,50 @@ activation_funcs = {
 }
 
 
-class _Cfg(tuple):
-    """(dim, act name, alpha, gain, clamp) -- hashable op configuration carried through autograd."""
-    dim = property(lambda s: s[0]); act = property(lambda s: s[1]); alpha = property(lambda s: s[2])
-    gain = property(lambda s: s[3]); clamp = property(lambda s: s[4])
+class Act(typing.NamedTuple):
+    """(name, alpha, gain, clamp): the settings of one bias_act, hashable, no tensors -- what every fused tail of the op layer carries
+    through autograd (ops/_tail.py adds the operands).  clamp < 0 means none.  Build it with `Act.make`, which applies the defaults."""
+    name: str = "linear"
+    alpha: float = 0.0
+    gain: float = 1.0
+    clamp: float = -1.0
+
+    @classmethod
+    def make(cls, name="linear", alpha=None, gain=None, clamp=None):
+        """the defaults rule of the reference (bias_act.py:80-82): alpha / gain None -> the activation's own, clamp None -> -1"""
+        spec = activation_funcs[name]
+        return cls(name, float(alpha if alpha is not None else spec.def_alpha), float(gain if gain is not None else spec.def_gain),
+                   float(clamp if clamp is not None else -1))
 
     @property
     def spec(self):
-        return activation_funcs[self.act]
+        return activation_funcs[self.name]
+
+    @property
+    def code(self):
+        return self.spec.cuda_idx
+
+    @property
+    def fused(self):
+        """piecewise linear: the activations the fused kernels take (their slope is recovered from the saved output)"""
+        return self.name in ("linear", "relu", "lrelu")
 
     @property
     def trivial(self):
-        return self.act == "linear" and self.gain == 1 and self.clamp < 0
+        return self.name == "linear" and self.gain == 1 and self.clamp < 0
 
     @property
     def needs_y(self):
         # The gradient's clamp mask is evaluated on the forward output.  The reference's CUDA plugin does not keep `y` for
         # 'linear' (ref=''), which makes its gradient ignore the clamp there; the reference's eager CPU path (the parity
         # target) zeroes the gradient of clamped elements for every activation, so `y` is kept for linear + clamp too.
-        return "y" in self.spec.ref or (self.act == "linear" and self.clamp >= 0)
+        return "y" in self.spec.ref or (self.name == "linear" and self.clamp >= 0)
+
+
+class _Cfg(typing.NamedTuple):
+    """a bias_act as autograd carries it: the settings and the dimension the bias runs along"""
+    act: Act
+    dim: int = 1
 
 
 def _dense_like_format(x):
@@ -83,7 +110,7 @@ def _run(x, b, xref, yref, dy, grad, cfg, fmt):
     if x.numel() == 0:          # empty batch: nothing to launch (an empty tensor has no device pointer)
         return y
     status = lib.sbg_bias_act(_lib.ptr(x), _lib.ptr(b), _lib.ptr(aux[0]), _lib.ptr(aux[1]), _lib.ptr(aux[2]), _lib.ptr(y),
-                              _lib.dtype_code(x.dtype), grad, cfg.spec.cuda_idx, cfg.alpha, cfg.gain, cfg.clamp,
+                              _lib.dtype_code(x.dtype), grad, cfg.act.code, cfg.act.alpha, cfg.act.gain, cfg.act.clamp,
                               x.numel(), size_b, max(step_b, 1), _lib.stream_ptr(x.device))
     _lib.check(status, "sbg_bias_act")
     return y
@@ -98,15 +125,12 @@ def _sum_to_bias(t, dim):
     return t.sum([i for i in range(t.ndim) if i != dim])
 
 
-_FUSED_ACTS = {"linear": 1, "relu": 2, "lrelu": 3}
-
-
 def _grad_and_bias_sum(dy, y, cfg):
     """First-order backward of a piecewise-linear bias_act in ONE pass over (dy, y): returns (dx, db) with
     dx = dy * gain * (y > 0 ? 1 : alpha) * [|y| < clamp] and db = dx summed over N, H, W (fp32 accumulation, fixed order).
     Uses sbg_modconv_bwd with unit demodulation (csrc/modulate.hip); None when the layout / activation does not fit, in which
     case the caller takes the generic differentiable path (bias_act.py:159-210 of the reference)."""
-    if (torch.is_grad_enabled() or cfg.act not in _FUSED_ACTS or cfg.dim != 1 or y.ndim != 4 or y.device.type != "cuda"
+    if (torch.is_grad_enabled() or not cfg.act.fused or cfg.dim != 1 or y.ndim != 4 or y.device.type != "cuda"
             or y.dtype not in (torch.bfloat16, torch.float16) or not y.is_contiguous(memory_format=torch.channels_last) or y.shape[1] == 1):
         return None
     lib = _lib.load()
@@ -119,8 +143,8 @@ def _grad_and_bias_sum(dy, y, cfg):
     part = torch.empty([2, ns, n, c], dtype=torch.float32, device=y.device)
     dx = torch.empty_like(y)
     _lib.check(lib.sbg_modconv_bwd(_lib.ptr(dy), _lib.ptr(y), _lib.ptr(ones), None, None, _lib.ptr(dx), _lib.ptr(part), None,
-                                   _lib.dtype_code(y.dtype), n, c, h * w, 0, _FUSED_ACTS[cfg.act], float(cfg.alpha), float(cfg.gain),
-                                   float(cfg.clamp), _lib.stream_ptr(y.device)), "sbg_modconv_bwd")
+                                   _lib.dtype_code(y.dtype), n, c, h * w, 0, cfg.act.code, cfg.act.alpha, cfg.act.gain,
+                                   cfg.act.clamp, _lib.stream_ptr(y.device)), "sbg_modconv_bwd")
     return dx, part[0].sum([0, 1])
 
 
@@ -129,10 +153,10 @@ class _BiasAct(torch.autograd.Function):
     def forward(ctx, x, b, cfg):
         fmt = _dense_like_format(x)
         x = x.contiguous(memory_format=fmt)
-        y = x if (cfg.trivial and b is None) else _run(x, b, None, None, None, 0, cfg, fmt)
-        spec = cfg.spec
+        y = x if (cfg.act.trivial and b is None) else _run(x, b, None, None, None, 0, cfg, fmt)
+        spec = cfg.act.spec
         keep_x = ("x" in spec.ref) or spec.has_2nd_grad
-        ctx.save_for_backward(x if keep_x else None, b if keep_x else None, y if cfg.needs_y else None)
+        ctx.save_for_backward(x if keep_x else None, b if keep_x else None, y if cfg.act.needs_y else None)
         ctx.cfg, ctx.fmt = cfg, fmt
         return y
 
@@ -141,13 +165,13 @@ class _BiasAct(torch.autograd.Function):
         x, b, y = ctx.saved_tensors
         cfg = ctx.cfg
         dx = db = None
-        if ctx.needs_input_grad[1] and not cfg.trivial and y is not None and b is not None:
+        if ctx.needs_input_grad[1] and not cfg.act.trivial and y is not None and b is not None:
             fused = _grad_and_bias_sum(dy, y, cfg)          # first order, piecewise-linear activation: dx and db in one pass
             if fused is not None:
                 return fused[0], fused[1].to(b.dtype), None
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
             dx = dy.contiguous(memory_format=ctx.fmt)
-            if not cfg.trivial:
+            if not cfg.act.trivial:
                 dx = _BiasActGrad.apply(dx, x, b, y, cfg, ctx.fmt)
         if ctx.needs_input_grad[1]:
             db = _sum_to_bias(dx, cfg.dim)
@@ -158,7 +182,7 @@ class _BiasActGrad(torch.autograd.Function):
     @staticmethod
     def forward(ctx, dy, x, b, y, cfg, fmt):
         dx = _run(dy, b, x, y, None, 1, cfg, fmt)
-        ctx.save_for_backward(dy if cfg.spec.has_2nd_grad else None, x, b, y)
+        ctx.save_for_backward(dy if cfg.act.spec.has_2nd_grad else None, x, b, y)
         ctx.cfg, ctx.fmt = cfg, fmt
         return dx
 
@@ -170,7 +194,7 @@ class _BiasActGrad(torch.autograd.Function):
         d_dy = d_x = d_b = None
         if ctx.needs_input_grad[0]:
             d_dy = _BiasActGrad.apply(d_dx, x, b, y, cfg, ctx.fmt)
-        if cfg.spec.has_2nd_grad and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]):
+        if cfg.act.spec.has_2nd_grad and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]):
             d_x = _run(d_dx, b, x, y, dy, 2, cfg, ctx.fmt)
             if ctx.needs_input_grad[2]:
                 d_b = _sum_to_bias(d_x, cfg.dim)
@@ -188,9 +212,5 @@ def bias_act(x, b=None, dim=1, act="linear", alpha=None, gain=None, clamp=None, 
     if impl == "ref":
         raise RuntimeError("bias_act: impl='ref' is not part of the MI355X build (the CPU restatement is oracle/, test-only)")
     _lib.require_cuda(x, "bias_act")
-    spec = activation_funcs[act]
-    cfg = _Cfg((int(dim), act,
-                float(alpha if alpha is not None else spec.def_alpha),
-                float(gain if gain is not None else spec.def_gain),
-                float(clamp if clamp is not None else -1)))
+    cfg = _Cfg(Act.make(act, alpha, gain, clamp), int(dim))
     return _BiasAct.apply(x, b, cfg)

@@ -13,14 +13,16 @@ bf16 / f16 tensors take one MFMA pass with fp32 accumulation; fp32 tensors are s
 the fp32-input MFMA, which runs at 1/16 of the bf16 rate on gfx950).
 """
 import contextlib
-
+import ctypes
+import typing
 import weakref
 
 import numpy as np
-
 import torch
 
 from ... import _lib
+from . import bias_act
+from ._tail import Tail
 
 enabled = False                     # kept for API parity; the HIP path is always used on a ROCm device
 weight_gradients_disabled = False   # forcefully disable computation of gradients with respect to the weights
@@ -83,30 +85,10 @@ def _operand_passes(a, b):
     raise RuntimeError(f"conv2d: unsupported dtype {a.dtype}")
 
 
-class Epilogue:
-    """fused tail of a convolution launch: y = clamp(act(acc * oscale[n, co] + noise[n, pixel] + bias[co]) * gain)"""
-    __slots__ = ("oscale", "noise", "bias", "act", "alpha", "gain", "clamp", "_keep")
-
-    def __init__(self, oscale=None, noise=None, bias=None, act="linear", alpha=0.0, gain=1.0, clamp=-1.0):
-        assert act in ("linear", "relu", "lrelu")
-        self.oscale, self.noise, self.bias = oscale, noise, bias
-        self.act, self.alpha, self.gain, self.clamp = {"linear": 1, "relu": 2, "lrelu": 3}[act], float(alpha), float(gain), float(clamp)
-        self._keep = []
-
-    def fill(self, p, n, cout, oh, ow):
-        def f32(t, shape):
-            t = t.detach().to(torch.float32).reshape(shape).contiguous()
-            self._keep.append(t)
-            return t
-        if self.oscale is not None:
-            p.oscale = f32(self.oscale, [n, cout]).data_ptr()
-        if self.bias is not None:
-            p.bias = f32(self.bias, [cout]).data_ptr()
-        if self.noise is not None:
-            per_sample = self.noise.numel() != oh * ow
-            nz = f32(self.noise, [n if per_sample else 1, oh * ow])
-            p.noise, p.noise_stride_n = nz.data_ptr(), (oh * ow if per_sample else 0)
-        p.act, p.alpha, p.gain, p.clamp = self.act, self.alpha, self.gain, self.clamp
+def Epilogue(oscale=None, noise=None, bias=None, act="linear", alpha=0.0, gain=1.0, clamp=-1.0):
+    """fused tail of a convolution launch: y = clamp(act(acc * oscale[n, co] + noise[n, pixel] + bias[co]) * gain) -- the Tail record (ops/_tail.py)
+    under the name and with the keyword defaults this module has always offered"""
+    return Tail.make(act, alpha, gain, clamp, oscale=oscale, noise=noise, bias=bias)
 
 
 # fp32 operands up to this many elements run as ONE launch over the concatenated hi / mid / lo parts (each operand built by one pass of
@@ -125,7 +107,6 @@ def _split_cat(t, dim, order, dense=False):
     kernel.  By default the result keeps t's memory order (channel-minor stays channel-minor: sbg_split_bf16_cat); `dense` asks for a
     contiguous result whatever t's strides are (sbg_split_bf16_cat_nd: a permuted weight view becomes the packed operand without the
     transposing copy of six times the data that `.contiguous()` would add)."""
-    import ctypes
     arr = (ctypes.c_int * len(order))(*order)
     if dense and t.ndim <= 4 and not t.is_contiguous():
         lead = 4 - t.ndim
@@ -274,8 +255,12 @@ def _igemm(x, wp, y, taps, stride, oh, ow, y_off=(0, 0), y_step=(1, 1), oscale=N
         p.tap_dy[i], p.tap_dx[i], p.tap_slab[i] = dy, dx, slab
     p.accumulate = int(accumulate)
     if epi is not None:
-        assert not accumulate and y_step == (1, 1)
-        epi.fill(p, x.shape[0], wp.shape[1], oh, ow)
+        assert not accumulate and y_step == (1, 1) and epi.act.fused and epi.post is None
+        osc32, nz32, p.noise_stride_n, b32, _ = epi.operands(x.shape[0], wp.shape[1], oh, ow)       # these locals live until the launch has returned
+        if osc32 is not None:
+            p.oscale = osc32.data_ptr()
+        p.noise, p.bias = _lib.ptr(nz32), _lib.ptr(b32)
+        p.act, p.alpha, p.gain, p.clamp = epi.act.code, epi.act.alpha, epi.act.gain, epi.act.clamp
     # few output tiles but a long reduction: the library splits K over workgroups (ksplit stays 0: its choice) when it is handed the scratch for it
     nbytes = lib.sbg_conv2d_igemm_workspace(p)
     if nbytes < 0:
@@ -444,29 +429,41 @@ def _wgrad(a, b, stride, taps):
 # ----------------------------------------------------------------------------------------------------------------
 # autograd
 
-def _output_padding_for(transpose, stride, padding, in_hw, out_hw, k_hw):
-    """output_padding of the data-gradient op (reference: conv2d_gradfix.py:95-104)."""
-    if transpose:
-        return (0, 0)
-    return tuple(in_hw[i] - (out_hw[i] - 1) * stride[i] - (1 - 2 * padding[i]) - (k_hw[i] - 1) for i in range(2))
+class ConvCfg(typing.NamedTuple):
+    """configuration of one convolution as autograd carries it.  `wgain`: with the fp32 master weight and 16-bit x ("mixed") the operand is
+    cast(w * wgain) and the weight gradient comes back already multiplied by it; 1.0 otherwise."""
+    transpose: bool
+    stride: tuple
+    padding: tuple
+    output_padding: tuple = (0, 0)
+    wgain: float = 1.0
+
+    @classmethod
+    def make(cls, transpose, stride=1, padding=0, output_padding=0, wgain=1.0):
+        return cls(bool(transpose), _pair(stride), _pair(padding), _pair(output_padding), float(wgain))
+
+    def adjoint(self, x_hw, dy_hw, k_hw):
+        """the data-gradient op: the opposite (transposed / plain) convolution, with the output_padding that gives dx the size of x
+        (reference: conv2d_gradfix.py:95-104)"""
+        op = (0, 0)
+        if not self.transpose:
+            op = tuple(x_hw[i] - (dy_hw[i] - 1) * self.stride[i] - (1 - 2 * self.padding[i]) - (k_hw[i] - 1) for i in range(2))
+        return self._replace(transpose=not self.transpose, output_padding=op)
 
 
 class _Conv(torch.autograd.Function):
-    """cfg = (transpose, stride, padding, output_padding[, wgain]); weight is [Cout, Cin, kh, kw] (plain) or [Cin, Cout, kh, kw]
-    (transpose), in x's dtype -- or the fp32 master weight with 16-bit x ("mixed": the operand is cast(w * wgain), the weight
-    gradient comes back in fp32 in the parameter's layout, already multiplied by wgain)."""
+    """cfg: ConvCfg; weight is [Cout, Cin, kh, kw] (plain) or [Cin, Cout, kh, kw] (transpose), in x's dtype -- or the fp32 master weight
+    with 16-bit x (the weight gradient then comes back in fp32 in the parameter's layout)."""
 
     @staticmethod
     def forward(ctx, x, w, cfg):
-        transpose, stride, padding, output_padding = cfg[:4]
-        wgain = cfg[4] if len(cfg) > 4 else 1.0
         _lib.require_cuda(x, "conv2d")
         if x.dtype != w.dtype and not is_mixed(x, w):
             raise RuntimeError(f"conv2d: input ({x.dtype}) and weight ({w.dtype}) must have the same dtype (or an fp32 weight with 16-bit input)")
-        if not transpose:
-            y = _conv_forward(x, w, stride, padding, wgain=wgain)
+        if not cfg.transpose:
+            y = _conv_forward(x, w, cfg.stride, cfg.padding, wgain=cfg.wgain)
         else:
-            y = _conv_transpose_forward(x, w, stride, padding, output_padding, wgain=wgain)
+            y = _conv_transpose_forward(x, w, cfg.stride, cfg.padding, cfg.output_padding, wgain=cfg.wgain)
         ctx.save_for_backward(x, w)
         ctx.cfg = cfg
         return y
@@ -474,14 +471,11 @@ class _Conv(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, w = ctx.saved_tensors
-        transpose, stride, padding, output_padding = ctx.cfg[:4]
-        wgain = ctx.cfg[4] if len(ctx.cfg) > 4 else 1.0
         dx = dw = None
         if ctx.needs_input_grad[0]:
-            op = _output_padding_for(transpose, stride, padding, x.shape[2:], dy.shape[2:], w.shape[2:])
             if dy.dtype != x.dtype:
                 dy = dy.to(x.dtype)
-            dx = _Conv.apply(dy, w, (not transpose, stride, padding, op, wgain))
+            dx = _Conv.apply(dy, w, ctx.cfg.adjoint(x.shape[2:], dy.shape[2:], w.shape[2:]))
             assert dx.shape == x.shape
         if ctx.needs_input_grad[1] and not weight_gradients_disabled:
             dw = _ConvWgrad.apply(dy, x, ctx.cfg, tuple(w.shape), wmeta_of(x, w))
@@ -499,19 +493,18 @@ class _ConvWgrad(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, dy, x, cfg, wshape, wmeta=None):
-        transpose, stride, padding, _ = cfg[:4]
-        wgain = cfg[4] if len(cfg) > 4 else 1.0
+        stride, padding = cfg.stride, cfg.padding
         kh, kw = wshape[2], wshape[3]
         taps = [(i - padding[0], j - padding[1]) for i in range(kh) for j in range(kw)]
         assert stride[0] == stride[1]
         if dy.dtype != x.dtype:
             dy = dy.to(x.dtype)
-        if not transpose:
+        if not cfg.transpose:
             out = _wgrad(dy, x, stride[0], taps)     # [t, Cout, Cin]
         else:
             out = _wgrad(x, dy, stride[0], taps)     # [t, Cin, Cout]
         if wmeta is not None:
-            dw = _unpack_wgrad(out, wshape[0], wshape[1], wshape, wmeta, 0, wgain)
+            dw = _unpack_wgrad(out, wshape[0], wshape[1], wshape, wmeta, 0, cfg.wgain)
         else:
             dw = out.reshape(kh, kw, wshape[0], wshape[1]).permute(2, 3, 0, 1).to(x.dtype)
         ctx.save_for_backward(dy, x)
@@ -521,19 +514,17 @@ class _ConvWgrad(torch.autograd.Function):
     @staticmethod
     def backward(ctx, ddw):
         dy, x = ctx.saved_tensors
-        transpose, stride, padding, output_padding = ctx.cfg[:4]
         d_dy = d_x = None
         if ctx.needs_input_grad[0]:
             d_dy = _Conv.apply(x, ddw, ctx.cfg)
             assert d_dy.shape == dy.shape
         if ctx.needs_input_grad[1]:
-            op = _output_padding_for(transpose, stride, padding, x.shape[2:], dy.shape[2:], ctx.wshape[2:])
-            d_x = _Conv.apply(dy, ddw, (not transpose, stride, padding, op) + tuple(ctx.cfg[4:]))
+            d_x = _Conv.apply(dy, ddw, ctx.cfg.adjoint(x.shape[2:], dy.shape[2:], ctx.wshape[2:]))
             assert d_x.shape == x.shape
         return d_dy, d_x, None, None, None
 
 
-def _grouped(fn, input, weight, groups, transpose):
+def _grouped(fn, input, weight, groups):
     """groups > 1: one launch set per group (only the eval-time fused modulated conv and depthwise filters use it)."""
     cin_g = input.shape[1] // groups
     outs = []
@@ -543,37 +534,28 @@ def _grouped(fn, input, weight, groups, transpose):
     return torch.cat(outs, dim=1)
 
 
-def _add_bias(y, bias):
-    if bias is None:
-        return y
-    from . import bias_act
-    return bias_act.bias_act(y, bias.to(y.dtype))
+def _conv_op(what, input, weight, bias, cfg, dilation, groups):
+    """what conv2d and conv_transpose2d share: the checks, the Function (per group) and the bias"""
+    _lib.require_cuda(input, what)
+    assert _pair(dilation) == (1, 1), f"{what}: dilation is not implemented"
+    assert groups == 1 or not is_mixed(input, weight)
+    if groups == 1:
+        y = _Conv.apply(input, weight, cfg)
+    else:
+        y = _grouped(lambda a, b: _Conv.apply(a, b, cfg), input, weight, groups)
+    return y if bias is None else bias_act.bias_act(y, bias.to(y.dtype))
 
 
 def conv2d(input, weight, bias=None, stride=1, padding=0, dilation=1, groups=1, wgain=1.0):
     """Same contract as torch.nn.functional.conv2d / the reference's conv2d (conv2d_gradfix.py:35), HIP kernels inside.
     Extension: `weight` may be the fp32 master parameter with a 16-bit input; the operand is then cast(weight * wgain)."""
-    _lib.require_cuda(input, "conv2d")
-    assert _pair(dilation) == (1, 1), "conv2d: dilation is not implemented"
-    cfg = (False, _pair(stride), _pair(padding), (0, 0), float(wgain))
-    assert groups == 1 or not is_mixed(input, weight)
-    assert all(p >= 0 for p in cfg[2]) and all(s >= 1 for s in cfg[1])
-    if groups == 1:
-        y = _Conv.apply(input, weight, cfg)
-    else:
-        y = _grouped(lambda a, b: _Conv.apply(a, b, cfg), input, weight, groups, False)
-    return _add_bias(y, bias)
+    cfg = ConvCfg.make(False, stride, padding, wgain=wgain)
+    assert all(p >= 0 for p in cfg.padding) and all(s >= 1 for s in cfg.stride)
+    return _conv_op("conv2d", input, weight, bias, cfg, dilation, groups)
 
 
 def conv_transpose2d(input, weight, bias=None, stride=1, padding=0, output_padding=0, groups=1, dilation=1, wgain=1.0):
     """Same contract as torch.nn.functional.conv_transpose2d / the reference's conv_transpose2d (conv2d_gradfix.py:40)."""
-    _lib.require_cuda(input, "conv_transpose2d")
-    assert _pair(dilation) == (1, 1), "conv_transpose2d: dilation is not implemented"
-    cfg = (True, _pair(stride), _pair(padding), _pair(output_padding), float(wgain))
-    assert groups == 1 or not is_mixed(input, weight)
-    assert all(0 <= cfg[3][i] < max(cfg[1][i], 1) or cfg[3][i] == 0 for i in range(2))
-    if groups == 1:
-        y = _Conv.apply(input, weight, cfg)
-    else:
-        y = _grouped(lambda a, b: _Conv.apply(a, b, cfg), input, weight, groups, True)
-    return _add_bias(y, bias)
+    cfg = ConvCfg.make(True, stride, padding, output_padding, wgain)
+    assert all(0 <= cfg.output_padding[i] < max(cfg.stride[i], 1) or cfg.output_padding[i] == 0 for i in range(2))
+    return _conv_op("conv_transpose2d", input, weight, bias, cfg, dilation, groups)

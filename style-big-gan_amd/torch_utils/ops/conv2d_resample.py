@@ -10,18 +10,18 @@ import torch
 from . import bias_act
 from . import conv2d_gradfix
 from . import conv_bias_act
+from . import modulate
 from . import upfirdn2d
 from .upfirdn2d import _get_filter_size, _parse_padding
 
 
 def _conv(x, w, stride=1, padding=0, groups=1, transpose=False, flip_weight=True, tail=None, wgain=1.0):
     """plain / transposed convolution; flips the taps when a true convolution is requested.
-    `tail` = dict(b, act, alpha, gain, clamp): the bias_act that follows, fused into the kernel epilogue when possible."""
+    `tail` (a Tail of bias and settings): the bias_act that follows, fused into the kernel epilogue when possible."""
     if not flip_weight:
         w = w.flip([2, 3])
-    if tail is not None and not transpose and conv_bias_act.fusable(x, w, tail["act"], groups):
-        return conv_bias_act.conv2d_bias_act(x, w, tail["b"], stride=stride, padding=padding, act=tail["act"], alpha=tail["alpha"],
-                                             gain=tail["gain"], clamp=tail["clamp"], wgain=wgain)
+    if tail is not None and not transpose and conv_bias_act.fusable(x, w, tail.act.name, groups):
+        return conv_bias_act.conv2d_bias_act(x, w, tail.bias, stride, padding, *tail.act, wgain=wgain)
     fn = conv2d_gradfix.conv_transpose2d if transpose else conv2d_gradfix.conv2d
     y = fn(x, w, stride=stride, padding=padding, groups=groups, wgain=wgain)
     return _tail(y, tail)
@@ -30,10 +30,10 @@ def _conv(x, w, stride=1, padding=0, groups=1, transpose=False, flip_weight=True
 def _tail(y, tail):
     if tail is None:
         return y
-    b = tail["b"]
+    b = tail.bias
     if b is not None and b.dtype != y.dtype:        # layers hand over their fp32 bias parameter (the fused conv epilogue reads fp32)
         b = b.to(y.dtype)
-    return bias_act.bias_act(y, b, act=tail["act"], alpha=tail["alpha"], gain=tail["gain"], clamp=tail["clamp"])
+    return bias_act._BiasAct.apply(y, b, bias_act._Cfg(tail.act))
 
 
 def lowpass_padding(f, down, padding):
@@ -47,9 +47,9 @@ def conv2d_resample(x, w, f=None, up=1, down=1, padding=0, groups=1, flip_weight
                     wgain=1.0, prefiltered=False):
     """x: [N, Cin, H, W]; w: [Cout, Cin // groups, kh, kw] (same dtype); f: filter from upfirdn2d.setup_filter().
     `padding` is relative to the upsampled image.  Returns [N, Cout, H * up // down (+ padding), ...].
-    `bias_act_tail` (extension): dict(b, act, alpha, gain, clamp) -- apply that bias_act to the result, fused into the
+    `bias_act_tail` (extension): a Tail (ops/_tail.py) of bias and settings -- apply that bias_act to the result, fused into the
     convolution kernel when the convolution is the last stage.
-    `fir_tail` (extension, up-sampling branch): dict(dcoefs, noise, b, act, alpha, gain, clamp[, post]) -- the demodulation + noise + bias_act
+    `fir_tail` (extension, up-sampling branch): a Tail with any of its operands -- the demodulation + noise + bias_act (+ post scale)
     of a synthesis layer, fused into the low-pass kernel that ends the branch (first order only; the caller checks
     upfirdn2d.fir_tail_supported on the result of fir_tail_probe).
     `wgain` (extension): with 16-bit x, `w` may be the layer's fp32 parameter; the convolution operand is then cast(w * wgain), prepared
@@ -101,16 +101,16 @@ def conv2d_resample(x, w, f=None, up=1, down=1, padding=0, groups=1, flip_weight
         x = _conv(x, wt, stride=up, padding=[pyt, pxt], groups=groups, transpose=True, flip_weight=(not flip_weight), wgain=wgain)
         fpad = [px0 + pxt, px1 + pxt, py0 + pyt, py1 + pyt]
         if fir_tail is not None and down == 1 and upfirdn2d.fir_tail_supported(x, f, fpad, flip_filter):
-            return upfirdn2d.fir_bias_act(x, f, fpad, up ** 2, fir_tail["dcoefs"], fir_tail["noise"], fir_tail["b"], act=fir_tail["act"],
-                                          alpha=fir_tail["alpha"], act_gain=fir_tail["gain"], clamp=fir_tail["clamp"], flip_filter=flip_filter,
-                                          post_scale=fir_tail.get("post"))
+            return upfirdn2d.fir_bias_act(x, f, fpad, up ** 2, fir_tail.oscale, fir_tail.noise, fir_tail.bias, *fir_tail.act, flip_filter=flip_filter,
+                                          post_scale=fir_tail.post)
         x = upfirdn2d.upfirdn2d(x, f, padding=fpad, gain=up ** 2, flip_filter=flip_filter)
         if fir_tail is not None:       # unfused composition of the same tail
-            from . import modulate
-            x = modulate.scale_nc(x, fir_tail["dcoefs"], fir_tail["noise"]) if fir_tail["dcoefs"] is not None else (x if fir_tail["noise"] is None else x + fir_tail["noise"].to(x.dtype))
-            x = bias_act.bias_act(x, fir_tail["b"].to(x.dtype) if fir_tail["b"] is not None else None, act=fir_tail["act"], alpha=fir_tail["alpha"],
-                                  gain=fir_tail["gain"], clamp=(fir_tail["clamp"] if fir_tail["clamp"] >= 0 else None))
-            return x if fir_tail.get("post") is None else modulate.scale_nc(x, fir_tail["post"])
+            if fir_tail.oscale is not None:
+                x = modulate.scale_nc(x, fir_tail.oscale, fir_tail.noise)
+            elif fir_tail.noise is not None:
+                x = x + fir_tail.noise.to(x.dtype)
+            x = _tail(x, fir_tail)
+            return x if fir_tail.post is None else modulate.scale_nc(x, fir_tail.post)
         if down > 1:
             x = upfirdn2d.upfirdn2d(x, f, down=down, flip_filter=flip_filter)
         return _tail(x, tail)

@@ -10,71 +10,59 @@ the pre-activation tensor is never materialised (the activation is piecewise lin
 First order only: path-length regularisation differentiates twice through the synthesis network, so trainers switch ``enabled``
 off when a generator regulariser is configured and the layer falls back to the differentiable composition.
 """
+import os
+
 import torch
 
 from ... import _lib
-from . import bias_act as _ba
 from . import conv2d_gradfix as _cg
 from . import modulate as _mod
 from . import upfirdn2d as _up
+from ._tail import Act, Tail, finish_grads
 
 enabled = True      # module switch: False -> SynthesisLayer uses modulated_conv2d + bias_act (arbitrarily differentiable)
-import os as _os
-chain_heads = _os.environ.get("SBG_CHAIN_HEADS", "1") != "0"       # a layer's backward also runs the backward head of the layer that feeds it (x_sole_consumer)
-
-_ACT = {"linear": 1, "relu": 2, "lrelu": 3}
+chain_heads = os.environ.get("SBG_CHAIN_HEADS", "1") != "0"       # a layer's backward also runs the backward head of the layer that feeds it (x_sole_consumer)
 
 
 def usable(x, weight, act, up):
-    return (enabled and up == 1 and act in _ACT and x.device.type == "cuda" and x.dtype in (torch.bfloat16, torch.float16)
+    return (enabled and up == 1 and Act(act).fused and x.device.type == "cuda" and x.dtype in (torch.bfloat16, torch.float16)
             and weight.shape[2] == weight.shape[3] and bool(_lib.load().sbg_modconv_bwd_supported(weight.shape[0])))
 
 
 class _ModConvBiasAct(torch.autograd.Function):
-    """y = clamp(act(conv(x * s, w) * dcoefs + noise + b) * gain);  cfg = (padding, act, alpha, gain, clamp)"""
+    """y = clamp(act(conv(x * s, w) * dcoefs + noise + b) * gain);  ccfg: ConvCfg of the convolution, act: the tail's settings (bias_act.Act)"""
 
     @staticmethod
-    def forward(ctx, x, w, styles, dcoefs, noise, b, cfg, x_tail=None):
+    def forward(ctx, x, w, styles, dcoefs, noise, b, ccfg, act, x_tail=None):
         ctx.x_tail = x_tail          # upfirdn2d.TailHandle of the layer that produced x, when this layer is x's ONLY consumer (see backward)
-        padding, act, alpha, gain, clamp = cfg
         xs = _mod._scale_nc_launch(x, styles, None)
-        epi = _cg.Epilogue(oscale=dcoefs, noise=noise, bias=b, act=act, alpha=alpha, gain=gain, clamp=clamp)
-        y = _cg._conv_forward(xs, w, (1, 1), (padding, padding), epi=epi)
+        y = _cg._conv_forward(xs, w, ccfg.stride, ccfg.padding, epi=Tail(act, dcoefs, noise, b))
         ctx.save_for_backward(x, xs, w, styles, dcoefs, noise, b, y)
-        ctx.cfg = cfg
+        ctx.ccfg, ctx.act = ccfg, act
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, xs, w, styles, dcoefs, noise, b, y = ctx.saved_tensors
-        padding, act, alpha, gain, clamp = ctx.cfg
+        ccfg = ctx.ccfg
         if torch.is_grad_enabled():
             raise RuntimeError("modconv: the fused layer is first-order only; set torch_utils.ops.modconv.enabled = False "
                                "before building a graph that is differentiated twice (path-length regularisation)")
-        n, cout, h, wd = y.shape
-        want_dn = noise is not None and ctx.needs_input_grad[4]
-        d2, sums, dn, dc32 = _up.backward_head(dy, y, dcoefs, noise, b, act, alpha, gain, clamp, want_dn)      # [2, N, Cout] sums, fixed order
-        dx = dw = dstyles = ddcoefs = dnoise = db = None
-        if ctx.needs_input_grad[3]:
-            ddcoefs = (sums[1] / dc32).to(dcoefs.dtype).reshape(dcoefs.shape)
-        if b is not None and ctx.needs_input_grad[5]:
-            db = sums[0].sum(0).to(b.dtype)
-        if want_dn:
-            dnoise = dn if noise.numel() != h * wd else dn.sum(0, keepdim=True)
-            dnoise = dnoise.reshape(noise.shape).to(noise.dtype)
-        ccfg = (False, (1, 1), (padding, padding), (0, 0))
+        own = Tail(ctx.act, dcoefs, noise, b)
+        d2, sums, dn, dc32 = _up.backward_head(dy, y, own, noise is not None and ctx.needs_input_grad[4])      # [2, N, Cout] sums, fixed order
+        ddcoefs, dnoise, db = finish_grads(own, sums, dn, dc32, *ctx.needs_input_grad[3:6])
+        dx = dw = dstyles = None
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[2]:
-            dxs = _cg._Conv.apply(d2, w, (True, (1, 1), (padding, padding), (0, 0)))
-            tail = ctx.x_tail
+            dxs = _cg._Conv.apply(d2, w, ccfg.adjoint(x.shape[2:], d2.shape[2:], w.shape[2:]))
+            handle = ctx.x_tail
             both = None
-            if (tail is not None and ctx.needs_input_grad[0] and ctx.needs_input_grad[2] and dxs.dtype == x.dtype
+            if (handle is not None and ctx.needs_input_grad[0] and ctx.needs_input_grad[2] and dxs.dtype == x.dtype
                     and _lib.load().sbg_modconv_bwd_supported(x.shape[1])):
                 # x = clamp(act(...)) is the output of an up-sampling layer's fused tail and feeds nothing but this convolution: `dxs * s`, `sum dxs * x`
                 # and THAT layer's backward head (activation slope at x, bias / demodulation / noise sums) are one pass over (dxs, x).  What goes back
                 # as "the gradient of x" is already the gradient of that layer's pre-activation; its backward recognises the tensor (TailHandle).
-                hd2, hsums, hdn, hdc32, dst = _up.backward_head(dxs, x, tail.dcoefs, tail.noise, tail.b, tail.act, tail.alpha, tail.act_gain, tail.clamp,
-                                                                tail.noise is not None, prescale=styles)
-                tail.result = dict(ptr=hd2.data_ptr(), sums=hsums, dn=hdn, dc32=hdc32)
+                hd2, hsums, hdn, hdc32, dst = _up.backward_head(dxs, x, handle.tail, handle.tail.noise is not None, prescale=styles)
+                handle.result = dict(ptr=hd2.data_ptr(), sums=hsums, dn=hdn, dc32=hdc32)
                 dx, dstyles = hd2, dst.to(styles.dtype).reshape(styles.shape)
             else:
                 if ctx.needs_input_grad[0] and ctx.needs_input_grad[2]:
@@ -88,7 +76,7 @@ class _ModConvBiasAct(torch.autograd.Function):
                         dstyles = _mod._dot_hw_launch(dxs, x).to(styles.dtype).reshape(styles.shape)
         if ctx.needs_input_grad[1] and not _cg.weight_gradients_disabled:
             dw = _cg._ConvWgrad.apply(d2, xs, ccfg, tuple(w.shape), _cg.wmeta_of(xs, w))
-        return dx, dw, dstyles, ddcoefs, dnoise, db, None, None
+        return dx, dw, dstyles, ddcoefs, dnoise, db, None, None, None
 
 
 class _DemodCoefs(torch.autograd.Function):
@@ -137,8 +125,5 @@ def modconv_bias_act(x, weight, styles, dcoefs, noise, bias, padding, act="lrelu
     dcoefs [N, Cout] (demodulation coefficients, differentiable), noise None / [N, 1, H, W] / [H, W], bias [Cout].
     `x_sole_consumer`: the caller guarantees that nothing else reads x; if x is the output of upfirdn2d.fir_bias_act (an up-sampling layer's fused tail),
     this layer's backward then also runs that layer's backward head, in the same pass as its own input gradients."""
-    spec = _ba.activation_funcs[act]
-    cfg = (int(padding), act, float(alpha if alpha is not None else spec.def_alpha), float(gain if gain is not None else spec.def_gain),
-           float(clamp if clamp is not None else -1))
     x_tail = getattr(x, "_sbg_tail", None) if (x_sole_consumer and chain_heads) else None
-    return _ModConvBiasAct.apply(x, weight, styles, dcoefs, noise, bias, cfg, x_tail)
+    return _ModConvBiasAct.apply(x, weight, styles, dcoefs, noise, bias, _cg.ConvCfg.make(False, 1, int(padding)), Act.make(act, alpha, gain, clamp), x_tail)

@@ -6,10 +6,14 @@ gradient definition (:214-268 -- the gradient of an upfirdn is the upfirdn with 
 flipped and the complementary padding, hence gradients of any order).  The arithmetic runs in ``sbg_upfirdn2d``
 (csrc/upfirdn2d.hip) for both memory layouts.
 """
+import typing
+import weakref
+
 import numpy as np
 import torch
 
 from ... import _lib
+from ._tail import Act, Tail, finish_grads
 
 
 def _pair(v):
@@ -49,6 +53,30 @@ def _get_filter_size(f):
     return fw, fh
 
 
+class FirCfg(typing.NamedTuple):
+    """configuration of one upfirdn2d as autograd carries it; the field order is the argument order of _launch after (x, f)"""
+    upx: int = 1
+    upy: int = 1
+    downx: int = 1
+    downy: int = 1
+    padx0: int = 0
+    padx1: int = 0
+    pady0: int = 0
+    pady1: int = 0
+    flip: bool = False
+    gain: float = 1.0
+
+    def adjoint(self, in_hw, out_hw, f):
+        """the gradient op for an input of size in_hw and an output of size out_hw: up and down swapped, the filter flipped, the complementary
+        padding (reference: upfirdn2d.py:252-262)"""
+        (ih, iw), (oh, ow) = in_hw, out_hw
+        fw, fh = _get_filter_size(f)
+        return FirCfg(self.downx, self.downy, self.upx, self.upy,
+                      fw - self.padx0 - 1, iw * self.upx - ow * self.downx + self.padx0 - self.upx + 1,
+                      fh - self.pady0 - 1, ih * self.upy - oh * self.downy + self.pady0 - self.upy + 1,
+                      not self.flip, self.gain)
+
+
 def setup_filter(f, device=torch.device("cpu"), normalize=True, flip_filter=False, gain=1, separable=None):
     """Prepare a float32 FIR filter: [fh, fw] (non-separable) or [taps] (separable; chosen automatically for
     1-D inputs with >= 8 taps).  None -> identity.  Same contract as the reference's ``setup_filter`` (:72-116)."""
@@ -71,9 +99,9 @@ def setup_filter(f, device=torch.device("cpu"), normalize=True, flip_filter=Fals
 
 def _launch(x, f2d, upx, upy, downx, downy, padx0, padx1, pady0, pady1, flip, gain, tail=None, probe=False, dact=None):
     """One sbg_upfirdn2d launch on a rank-2 filter; output keeps x's memory format (reference: upfirdn2d.cpp:35).
-    `tail` = dict(oscale, noise, bias, act, alpha, gain, clamp): fused demodulation / noise / bias_act epilogue (matrix-core FIR path only);
+    `tail` (a Tail): fused demodulation / noise / bias_act epilogue (matrix-core FIR path only);
     `probe=True` returns whether that path would take this launch with a tail, without launching.
-    `dact` = dict(y, act, alpha, gain, clamp): backward tail -- the result is multiplied by the slope of that bias_act at its saved output y and summed
+    `dact` = (y, Act): backward tail -- the result is multiplied by the slope of that bias_act at its saved output y and summed
     per channel; returns (result, bias gradient [C] fp32), or None when the sliding-window matrix-core FIR does not take the launch."""
     lib = _lib.load()
     if x.ndim != 4:
@@ -106,35 +134,21 @@ def _launch(x, f2d, upx, upy, downx, downy, padx0, padx1, pady0, pady1, flip, ga
     if probe:
         return bool(cl and lib.sbg_upfirdn2d_tail_supported(p))
     if dact is not None:
-        ys = dact["y"]
+        ys, act = dact
         rows = int(lib.sbg_upfirdn2d_dact_rows(p)) if cl else -1
         if rows <= 0 or ys.shape != y.shape or ys.dtype != y.dtype or ys.stride() != y.stride():
             return None
         part = torch.empty([rows, 64], dtype=torch.float32, device=x.device)
         p.dact_y, p.dact_partial = ys.data_ptr(), part.data_ptr()
-        p.dact_act = {"linear": 1, "relu": 2, "lrelu": 3}[dact["act"]]
-        p.dact_alpha, p.dact_gain, p.dact_clamp = float(dact["alpha"]), float(dact["gain"]), float(dact["clamp"])
+        assert act.fused
+        p.dact_act, p.dact_alpha, p.dact_gain, p.dact_clamp = act.code, act.alpha, act.gain, act.clamp
         _lib.check(lib.sbg_upfirdn2d(p, _lib.stream_ptr(x.device)), "sbg_upfirdn2d")
         return y, part.reshape(-1, c // 64, 64).sum(0).reshape(c)       # rows: (sample, segment, strip) x channel block; fixed order
-    keep = []
     if tail is not None:
-        def f32(t, shape):
-            t = t.detach().to(torch.float32).reshape(shape).contiguous()
-            keep.append(t)
-            return t.data_ptr()
-        if tail.get("oscale") is not None:
-            p.oscale = f32(tail["oscale"], [n, c])
-        if tail.get("bias") is not None:
-            p.bias = f32(tail["bias"], [c])
-        if tail.get("noise") is not None:
-            nz = tail["noise"]
-            per_sample = nz.numel() != oh * ow
-            p.noise = f32(nz, [n if per_sample else 1, oh * ow])
-            p.noise_stride_n = oh * ow if per_sample else 0
-        p.act = {"linear": 1, "relu": 2, "lrelu": 3}[tail["act"]]
-        p.alpha, p.act_gain, p.clamp = float(tail["alpha"]), float(tail["gain"]), float(tail["clamp"])
-        if tail.get("post") is not None:            # (inference) the next layer's style modulation applied on the way out
-            p.post_scale = f32(tail["post"], [n, c])
+        assert tail.act.fused
+        osc32, nz32, p.noise_stride_n, b32, post32 = tail.operands(n, c, oh, ow)       # these locals live until the launch has returned
+        p.oscale, p.noise, p.bias, p.post_scale = _lib.ptr(osc32), _lib.ptr(nz32), _lib.ptr(b32), _lib.ptr(post32)
+        p.act, p.alpha, p.act_gain, p.clamp = tail.act.code, tail.act.alpha, tail.act.gain, tail.act.clamp
     _lib.check(lib.sbg_upfirdn2d(p, _lib.stream_ptr(x.device)), "sbg_upfirdn2d")
     return y
 
@@ -159,8 +173,6 @@ def _launch_separable(x, f, up, down, padx0, padx1, pady0, pady1, flip, gain):
                                                        padx0, pady0, int(bool(flip)), float(gain), _lib.stream_ptr(x.device)), "sbg_upfirdn2d_separable")
     return y
 
-
-import weakref
 
 _filter_facts = {}      # id(filter tensor) -> [weakref, version, sightings, {fact: value}]
 
@@ -208,7 +220,7 @@ def _rank1_factor(f):
 
 
 class _Upfirdn2d(torch.autograd.Function):
-    """cfg = (upx, upy, downx, downy, padx0, padx1, pady0, pady1, flip_filter, gain)"""
+    """cfg: FirCfg"""
 
     @staticmethod
     def forward(ctx, x, f, cfg):
@@ -222,7 +234,7 @@ class _Upfirdn2d(torch.autograd.Function):
         if g1 is not None and _separable_fused_ok(x, g1, upx, upy, downx, downy):
             y = _launch_separable(x, g1, upx, downx, padx0, padx1, pady0, pady1, flip, gain)
         elif f.ndim == 2:
-            y = _launch(x, f, upx, upy, downx, downy, padx0, padx1, pady0, pady1, flip, gain)
+            y = _launch(x, f, *cfg)
         elif _separable_fused_ok(x, f, upx, upy, downx, downy):
             y = _launch_separable(x, f, upx, downx, padx0, padx1, pady0, pady1, flip, gain)
         else:   # separable: a row pass then a column pass, sqrt(gain) each
@@ -236,61 +248,48 @@ class _Upfirdn2d(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         (f,) = ctx.saved_tensors
-        upx, upy, downx, downy, padx0, padx1, pady0, pady1, flip, gain = ctx.cfg
         dx = None
         if ctx.needs_input_grad[0]:
-            ih, iw = ctx.in_hw
-            oh, ow = dy.shape[2], dy.shape[3]
-            fw, fh = _get_filter_size(f)
-            gcfg = (downx, downy, upx, upy,
-                    fw - padx0 - 1, iw * upx - ow * downx + padx0 - upx + 1,
-                    fh - pady0 - 1, ih * upy - oh * downy + pady0 - upy + 1,
-                    not flip, gain)
-            dx = _Upfirdn2d.apply(dy, f, gcfg)
+            dx = _Upfirdn2d.apply(dy, f, ctx.cfg.adjoint(ctx.in_hw, dy.shape[2:], f))
         return dx, None, None
 
 
 class TailHandle:
     """What the sole consumer of a fir_bias_act output needs in order to run THAT layer's backward head itself, fused with its own input
-    gradients (ops/modconv.py: `dx = dxs * s`, `sum dxs * x` and the head below are three passes over the same two tensors), and the slot through
-    which it hands the result back to _FirBiasAct.backward."""
-    __slots__ = ("dcoefs", "noise", "b", "act", "alpha", "act_gain", "clamp", "result")
+    gradients (ops/modconv.py: `dx = dxs * s`, `sum dxs * x` and the head below are three passes over the same two tensors): the layer's
+    tail, and the slot through which the consumer hands the result back to _FirBiasAct.backward."""
+    __slots__ = ("tail", "result")
 
-    def __init__(self, dcoefs, noise, b, act, alpha, act_gain, clamp):
-        self.dcoefs, self.noise, self.b, self.act, self.alpha, self.act_gain, self.clamp = dcoefs, noise, b, act, alpha, act_gain, clamp
-        self.result = None
+    def __init__(self, tail):
+        self.tail, self.result = tail, None
 
 
-def backward_head(dy, y, dcoefs, noise, b, act, alpha, act_gain, clamp, want_dn, prescale=None):
-    """one pass over (dy, y) for y = clamp(act(c * dcoefs + noise + b) * act_gain): (d2 = gradient w.r.t. c, sums [2, N, C] = bias / demodulation
-    partial sums, dn = per-pixel noise gradient or None, dc32) -- sbg_modconv_bwd.  With `prescale` [N, C]: dy is the gradient w.r.t. y * prescale; also
-    returns sum_hw dy * y (the gradient of prescale) as a fifth value -- sbg_modconv_bwd_prescaled."""
+def backward_head(dy, y, tail, want_dn, prescale=None):
+    """one pass over (dy, y) for y = clamp(act(c * oscale + noise + bias) * gain), the Tail `tail`: (d2 = gradient w.r.t. c, sums [2, N, C] = bias /
+    demodulation partial sums, dn = per-pixel noise gradient or None, dc32) -- sbg_modconv_bwd.  With `prescale` [N, C]: dy is the gradient w.r.t.
+    y * prescale; also returns sum_hw dy * y (the gradient of prescale) as a fifth value -- sbg_modconv_bwd_prescaled."""
     lib = _lib.load()
     n, c, oh, ow = y.shape
+    act = tail.act
+    assert act.fused
     dy = dy.to(y.dtype).contiguous(memory_format=torch.channels_last)
-    dc32 = (dcoefs.detach().to(torch.float32).reshape(n, c) if dcoefs is not None else torch.ones([n, c], dtype=torch.float32, device=y.device)).contiguous()
-    nz = nsn = None
-    if noise is not None:
-        nz = noise.detach().to(torch.float32)
-        per_sample = nz.numel() != oh * ow
-        nz = nz.reshape(n if per_sample else 1, oh * ow).contiguous()
-        nsn = oh * ow if per_sample else 0
-    b32 = b.detach().to(torch.float32).contiguous() if b is not None else None
+    dc32, nz, nsn, b32, _ = tail.operands(n, c, oh, ow)
+    if dc32 is None:
+        dc32 = torch.ones([n, c], dtype=torch.float32, device=y.device)
     ns = lib.sbg_dot_hw_splits(1, n, c, oh * ow)
     part = torch.empty([2, ns, n, c], dtype=torch.float32, device=y.device)
     d2 = torch.empty_like(y)
     dn = torch.empty([n, 1, oh, ow], dtype=torch.float32, device=y.device) if want_dn else None
-    code = {"linear": 1, "relu": 2, "lrelu": 3}[act]
     if prescale is None:
         _lib.check(lib.sbg_modconv_bwd(_lib.ptr(dy), _lib.ptr(y), _lib.ptr(dc32), _lib.ptr(nz), _lib.ptr(b32), _lib.ptr(d2), _lib.ptr(part),
-                                       _lib.ptr(dn), _lib.dtype_code(y.dtype), n, c, oh * ow, nsn or 0, code,
-                                       float(alpha), float(act_gain), float(clamp), _lib.stream_ptr(y.device)), "sbg_modconv_bwd")
+                                       _lib.ptr(dn), _lib.dtype_code(y.dtype), n, c, oh * ow, nsn, act.code,
+                                       act.alpha, act.gain, act.clamp, _lib.stream_ptr(y.device)), "sbg_modconv_bwd")
         return d2, part.sum(1), dn, dc32
     ps32 = prescale.detach().to(torch.float32).reshape(n, c).contiguous()
     part3 = torch.empty([ns, n, c], dtype=torch.float32, device=y.device)
     _lib.check(lib.sbg_modconv_bwd_prescaled(_lib.ptr(dy), _lib.ptr(y), _lib.ptr(ps32), _lib.ptr(dc32), _lib.ptr(nz), _lib.ptr(b32), _lib.ptr(d2),
-                                             _lib.ptr(part), _lib.ptr(part3), _lib.ptr(dn), _lib.dtype_code(y.dtype), n, c, oh * ow, nsn or 0, code,
-                                             float(alpha), float(act_gain), float(clamp), _lib.stream_ptr(y.device)), "sbg_modconv_bwd_prescaled")
+                                             _lib.ptr(part), _lib.ptr(part3), _lib.ptr(dn), _lib.dtype_code(y.dtype), n, c, oh * ow, nsn, act.code,
+                                             act.alpha, act.gain, act.clamp, _lib.stream_ptr(y.device)), "sbg_modconv_bwd_prescaled")
     return d2, part.sum(1), dn, dc32, part3.sum(0)
 
 
@@ -298,25 +297,21 @@ class _FirBiasAct(torch.autograd.Function):
     """y = clamp(act(upfirdn2d(t, f, padding, gain) * dcoefs[n, c] + noise + b) * act_gain) in one kernel (up = down = 1; the low-pass after
     the transposed convolution of an up-sampling synthesis layer with the layer's whole tail, generators.py:84-88,328).  Backward: one pass
     over (dy, y) (sbg_modconv_bwd) gives the gradient w.r.t. the filtered tensor and the bias / demodulation / noise gradients, then the
-    transposed FIR.  First order only (see ops/modconv.py).   cfg = (padx0, padx1, pady0, pady1, flip, gain, act, alpha, act_gain, clamp)"""
+    transposed FIR.  First order only (see ops/modconv.py).   cfg: FirCfg of the low-pass, act: the tail's settings (bias_act.Act)"""
 
     @staticmethod
-    def forward(ctx, t, f, dcoefs, noise, b, cfg, handle):
-        padx0, padx1, pady0, pady1, flip, gain, act, alpha, act_gain, clamp = cfg
-        y = _launch(t, f, 1, 1, 1, 1, padx0, padx1, pady0, pady1, flip, gain,
-                    tail=dict(oscale=dcoefs, noise=noise, bias=b, act=act, alpha=alpha, gain=act_gain, clamp=clamp))
+    def forward(ctx, t, f, dcoefs, noise, b, cfg, act, handle):
+        y = _launch(t, f, *cfg, tail=Tail(act, dcoefs, noise, b))
         ctx.save_for_backward(f, dcoefs, noise, b, y)
-        ctx.cfg, ctx.in_hw, ctx.handle = cfg, (t.shape[2], t.shape[3]), handle
+        ctx.cfg, ctx.act, ctx.in_hw, ctx.handle = cfg, act, (t.shape[2], t.shape[3]), handle
         return y
 
     @staticmethod
     def backward(ctx, dy):
         f, dcoefs, noise, b, y = ctx.saved_tensors
-        padx0, padx1, pady0, pady1, flip, gain, act, alpha, act_gain, clamp = ctx.cfg
+        tail = Tail(ctx.act, dcoefs, noise, b)
         if torch.is_grad_enabled():
             raise RuntimeError("fir_bias_act: first-order only; set torch_utils.ops.modconv.enabled = False for double backward")
-        n, c, oh, ow = y.shape
-        want_dn = noise is not None and ctx.needs_input_grad[3]
         handed = ctx.handle.result if ctx.handle is not None else None
         if handed is not None:      # the consumer of y ran this head together with its own input gradients (ops/modconv.py): dy IS d2
             ctx.handle.result = None
@@ -324,37 +319,25 @@ class _FirBiasAct(torch.autograd.Function):
                 raise RuntimeError("fir_bias_act: the consumer handed over a backward head, but the incoming gradient is another tensor -- "
                                    "the output must have exactly that one consumer (TailHandle)")
             d2, sums, dn, dc32 = dy, handed["sums"], handed["dn"], handed["dc32"]
-            want_dn = want_dn and dn is not None
         else:
-            d2, sums, dn, dc32 = backward_head(dy, y, dcoefs, noise, b, act, alpha, act_gain, clamp, want_dn)
-        dt = ddc = dnoise = db = None
-        if dcoefs is not None and ctx.needs_input_grad[2]:
-            ddc = (sums[1] / dc32).to(dcoefs.dtype).reshape(dcoefs.shape)
-        if b is not None and ctx.needs_input_grad[4]:
-            db = sums[0].sum(0).to(b.dtype)
-        if want_dn:
-            dnoise = (dn if noise.numel() != oh * ow else dn.sum(0, keepdim=True)).reshape(noise.shape).to(noise.dtype)
+            d2, sums, dn, dc32 = backward_head(dy, y, tail, noise is not None and ctx.needs_input_grad[3])
+        ddc, dnoise, db = finish_grads(tail, sums, dn, dc32, *ctx.needs_input_grad[2:5])
+        dt = None
         if ctx.needs_input_grad[0]:
-            ih, iw = ctx.in_hw
-            fw, fh = _get_filter_size(f)
-            gcfg = (1, 1, 1, 1, fw - padx0 - 1, iw - ow + padx0, fh - pady0 - 1, ih - oh + pady0, not flip, gain)
-            dt = _Upfirdn2d.apply(d2, f, gcfg)
-        return dt, None, ddc, dnoise, db, None, None
+            dt = _Upfirdn2d.apply(d2, f, ctx.cfg.adjoint(ctx.in_hw, y.shape[2:], f))
+        return dt, None, ddc, dnoise, db, None, None, None
 
 
 def fir_transposed_dact(dy, f, cfg, in_hw, y_saved, act, alpha, gain, clamp):
     """Backward of `bias_act -> upfirdn2d(f, cfg)` with respect to the bias_act's pre-activation, in ONE launch: the transposed low-pass of dy
     (what _Upfirdn2d.backward computes) times the activation's slope at the saved output, plus the bias gradient.  up = down = 1 only.
-    Returns (gradient [like y_saved], db [C] fp32) or None when the launch does not fit the sliding-window matrix-core FIR."""
-    upx, upy, downx, downy, padx0, padx1, pady0, pady1, flip, fgain = cfg
-    if (upx, upy, downx, downy) != (1, 1, 1, 1) or f is None or f.ndim != 2 or dy.device.type != "cuda":
+    cfg: FirCfg or the plain 10-tuple.  Returns (gradient [like y_saved], db [C] fp32) or None when the launch does not fit the sliding-window
+    matrix-core FIR."""
+    cfg = FirCfg(*cfg)
+    if cfg[:4] != (1, 1, 1, 1) or f is None or f.ndim != 2 or dy.device.type != "cuda":
         return None
-    ih, iw = in_hw
-    fw, fh = _get_filter_size(f)
-    oh, ow = dy.shape[2], dy.shape[3]
     dy = dy.to(y_saved.dtype).contiguous(memory_format=torch.channels_last)
-    return _launch(dy, f, 1, 1, 1, 1, fw - padx0 - 1, iw - ow + padx0, fh - pady0 - 1, ih - oh + pady0, not flip, fgain,
-                   dact=dict(y=y_saved, act=act, alpha=alpha, gain=gain, clamp=clamp))
+    return _launch(dy, f, *cfg.adjoint(in_hw, dy.shape[2:], f), dact=(y_saved, Act.make(act, alpha, gain, clamp)))
 
 
 def fir_tail_supported(x, f, padding, flip_filter=False):
@@ -367,14 +350,13 @@ def fir_tail_supported(x, f, padding, flip_filter=False):
 
 def fir_bias_act(x, f, padding, gain, dcoefs, noise, b, act="lrelu", alpha=0.2, act_gain=1.0, clamp=-1.0, flip_filter=False, post_scale=None):
     """`post_scale` [N, C] (inference only: no graph is recorded): the result times post_scale[n, c], i.e. already modulated for the layer that reads it"""
-    padx0, padx1, pady0, pady1 = _parse_padding(padding)
+    cfg = FirCfg(1, 1, 1, 1, *_parse_padding(padding), bool(flip_filter), float(gain))
+    tail = Tail.make(act, alpha, act_gain, clamp, oscale=dcoefs, noise=noise, bias=b, post=post_scale)
     if post_scale is not None:
         assert not (torch.is_grad_enabled() and (x.requires_grad or (dcoefs is not None and dcoefs.requires_grad))), "fir_bias_act: post_scale is an inference-only extension"
-        return _launch(x, f, 1, 1, 1, 1, padx0, padx1, pady0, pady1, bool(flip_filter), float(gain),
-                       tail=dict(oscale=dcoefs, noise=noise, bias=b, act=act, alpha=float(alpha), gain=float(act_gain), clamp=float(clamp), post=post_scale))
-    cfg = (padx0, padx1, pady0, pady1, bool(flip_filter), float(gain), act, float(alpha), float(act_gain), float(clamp))
-    handle = TailHandle(dcoefs, noise, b, act, float(alpha), float(act_gain), float(clamp))
-    y = _FirBiasAct.apply(x, f, dcoefs, noise, b, cfg, handle)
+        return _launch(x, f, *cfg, tail=tail)
+    handle = TailHandle(tail)
+    y = _FirBiasAct.apply(x, f, dcoefs, noise, b, cfg, tail.act, handle)
     y._sbg_tail = handle        # a consumer that KNOWS it is the only one may take over this layer's backward head (ops/modconv.py, x_tail)
     return y
 
@@ -387,12 +369,8 @@ def upfirdn2d(x, f, up=1, down=1, padding=0, flip_filter=False, gain=1, impl="cu
     if impl == "ref":
         raise RuntimeError("upfirdn2d: impl='ref' is not part of the MI355X build (the CPU restatement is oracle/, test-only)")
     _lib.require_cuda(x, "upfirdn2d")
-    upx, upy = _parse_scaling(up)
-    downx, downy = _parse_scaling(down)
-    padx0, padx1, pady0, pady1 = _parse_padding(padding)
     assert f is None or (isinstance(f, torch.Tensor) and f.dtype == torch.float32 and not f.requires_grad)
-    cfg = (upx, upy, downx, downy, padx0, padx1, pady0, pady1, bool(flip_filter), float(gain))
-    return _Upfirdn2d.apply(x, f, cfg)
+    return _Upfirdn2d.apply(x, f, FirCfg(*_parse_scaling(up), *_parse_scaling(down), *_parse_padding(padding), bool(flip_filter), float(gain)))
 
 
 def filter2d(x, f, padding=0, flip_filter=False, gain=1, impl="cuda"):

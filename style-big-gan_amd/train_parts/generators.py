@@ -23,6 +23,7 @@ import torch
 from .. import utils
 from ..torch_utils import misc
 from ..torch_utils.ops import bias_act, conv2d_gradfix, conv2d_resample, conv_bias_act, grouped_gemm, modconv, modulate, torgb, upfirdn2d
+from ..torch_utils.ops._tail import Tail
 
 generators = utils.ClassRegistry()
 
@@ -224,7 +225,7 @@ class Conv2dLayer(torch.nn.Module):
             return conv_bias_act.conv2d_bias_act_fir(x, self.weight, b, nxt.resample_filter, conv2d_resample.lowpass_padding(nxt.resample_filter, nxt.down, nxt.padding),
                                                      padding=self.padding, act=self.activation, gain=self.act_gain * gain, clamp=clamp, wgain=self.weight_gain)
         # conv2d_resample + bias_act (reference :179-184); the bias_act rides in the convolution kernel's epilogue when it can
-        tail = dict(b=b, act=self.activation, alpha=None, gain=self.act_gain * gain, clamp=clamp)
+        tail = Tail.make(self.activation, gain=self.act_gain * gain, clamp=clamp, bias=b)
         if conv2d_gradfix.is_mixed(x, self.weight) and x.device.type == 'cuda':
             # 16-bit block: hand the fp32 parameter over; `w * weight_gain`, the cast and the operand layout are one (cached) kernel
             return conv2d_resample.conv2d_resample(x=x, w=self.weight, f=self.resample_filter, up=self.up, down=self.down, padding=self.padding,
@@ -352,9 +353,7 @@ class SynthesisLayer(torch.nn.Module):
             with torch.no_grad():
                 dcoefs = demod_coefficients(self.weight, styles, x.dtype)
                 xs = x if x_premodulated else modulate.scale_nc(x, styles)
-                spec = bias_act.activation_funcs[self.activation]
-                epi = conv2d_gradfix.Epilogue(oscale=dcoefs, noise=noise, bias=self.bias, act=self.activation, alpha=spec.def_alpha,
-                                              gain=self.act_gain * gain, clamp=(clamp if clamp is not None else -1))
+                epi = Tail.make(self.activation, gain=self.act_gain * gain, clamp=clamp, oscale=dcoefs, noise=noise, bias=self.bias)
                 y = conv2d_gradfix._conv_forward(xs, self.weight, (1, 1), (self.padding, self.padding), epi=epi)
                 return y if post_scale is None else modulate.scale_nc(y, post_scale)
         assert not x_premodulated, 'x_premodulated: the caller checks premodulated_input_ok() first'
@@ -367,9 +366,8 @@ class SynthesisLayer(torch.nn.Module):
                 and self.activation in ('linear', 'relu', 'lrelu')):
             # up-sampling layer, first-order training pass: x * s -> transposed convolution (one multi-phase launch) -> low-pass whose kernel
             # epilogue carries demodulation, noise, bias, activation, gain and clamp (falls back to the composition inside conv2d_resample)
-            spec = bias_act.activation_funcs[self.activation]
-            tail = dict(dcoefs=demod_coefficients(self.weight, styles, x.dtype), noise=noise, b=self.bias, act=self.activation, alpha=spec.def_alpha,
-                        gain=self.act_gain * gain, clamp=(clamp if clamp is not None else -1), post=post_scale)
+            tail = Tail.make(self.activation, gain=self.act_gain * gain, clamp=clamp, oscale=demod_coefficients(self.weight, styles, x.dtype),
+                             noise=noise, bias=self.bias, post=post_scale)
             return conv2d_resample.conv2d_resample(x=modulate.scale_nc(x, styles), w=self.weight, f=self.resample_filter, up=2,
                                                    padding=self.padding, flip_weight=False, fir_tail=tail)
         x = modulated_conv2d(x=x, weight=self.weight, styles=styles, noise=noise, up=self.up, padding=self.padding,
