@@ -740,6 +740,26 @@ int sbg_kmeans_u8_update(const uint8_t* points, const int32_t* labels, const uin
                          int64_t* counts, void* workspace, int64_t N, int64_t F, int K, sbg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Latent walks (interpolate.py; the reference has no counterpart; csrc/walk.hip).  torch_utils/ops/walk.py evaluates
+ * both for CPU tensors to the same bits.  Dense tensors; no atomics: two runs give the same bits.
+ *   sbg_walk_blend:   keys fp32 [K, L, D], index int32 [T, 4], weight fp32 [T, 4] -> out fp32 [T, L, D].  On a layer whose layer_mask (int32 [L])
+ *                     entry is nonzero (layer_mask NULL: every layer) out[t, l, d] is the fp32 chain acc = weight[t, 0] * keys[index[t, 0], l, d]
+ *                     (one rounded product), acc = fmaf(weight[t, j], keys[index[t, j], l, d], acc) for j = 1, 2, 3 in this order; on the other
+ *                     layers it is a copy of keys[hold[t], l, d] (hold int32 [T], needed with a mask).  K >= 1, L >= 1, 1 <= D <= 1024,
+ *                     T L D < 2^31; pointers 4-byte aligned.  The CALLER checks that every index and hold value lies in [0, K); an element whose
+ *                     index lies outside is skipped, never read.  One launch; T = 0 launches nothing.
+ *   sbg_walk_sqdiff:  a, b uint8 [N, F], rows F bytes apart, any alignment (they may be slices of one tensor) -> out int64 [N],
+ *                     out[n] = sum_f (a[n, f] - b[n, f])^2, exact.  1 <= N <= 2^24, 1 <= F <= 2^26; out and workspace 8-byte aligned.  Rows are
+ *                     cut into sbg_walk_sqdiff_splits(N, F) = ceil(F / 16384) chunks (-1: unsupported sizes); with more than one, the chunks' int64
+ *                     partials go to sbg_walk_sqdiff_workspace(N, F) = 8 N splits bytes (0 with one split, -1 unsupported) and a second launch
+ *                     adds them.  A refused call launches nothing, returns SBG_ERR_INVALID and names the shape in sbg_last_error(). */
+int sbg_walk_blend(const float* keys, const int32_t* index, const float* weight, const int32_t* layer_mask, const int32_t* hold, float* out,
+                   int K, int T, int L, int D, sbg_stream_t stream);
+int64_t sbg_walk_sqdiff_splits(int64_t N, int64_t F);
+int64_t sbg_walk_sqdiff_workspace(int64_t N, int64_t F);
+int sbg_walk_sqdiff(const uint8_t* a, const uint8_t* b, int64_t* out, void* workspace, int64_t N, int64_t F, sbg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * In-process launch timing (measurement only; bench.py's roofline figures come from here).
  * While enabled, every kernel launch of this library is bracketed by two hipEvents recorded on the launch stream
  * and logged with its algorithmic flops / bytes.  sbg_prof_fetch() synchronises the logged events, writes up to `max`
@@ -769,7 +789,9 @@ enum sbg_kernel_kind {
     SBG_K_MSSSIM = 29,          /* dims[0] = variant: 0 level / 1 down / 2 merge; then BC (image-channels of the call, clipped to INT32_MAX), S */
     SBG_K_DIRECTIONS = 30,      /* dims[0] = variant: 0 mean (N, D, chunks) / 1 gram (N, D, groups) / 2 merge (N, D, chunks or groups: the launch
                                  * it finishes) / 3 edit (S, K, T, L, D); N clipped to INT32_MAX */
-    SBG_K_KMEANS_U8 = 31        /* dims[0] = variant: 0 accumulate / 1 finish; then N, F (both clipped to INT32_MAX), K, row chunks, lanes per row */
+    SBG_K_KMEANS_U8 = 31,       /* dims[0] = variant: 0 accumulate / 1 finish; then N, F (both clipped to INT32_MAX), K, row chunks, lanes per row */
+    SBG_K_WALK = 32             /* dims[0] = variant: 0 blend (T, L, D, 1 with a layer mask) / 1 sqdiff (N, F, splits) / 2 merge (N, F, splits: the
+                                 * second launch of a split sqdiff); N, F clipped to INT32_MAX */
 };
 /* Kernel-variant codes in the records of the streaming kernels (which kernel served the launch):
  *   bias_act     dims[4] = 1 vec8 / 2 scalar,  dims[5] = bias mode (0 none, 1 channel-minor vector, 2 one per 8-vector, 3 generic)

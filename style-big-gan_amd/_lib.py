@@ -112,7 +112,8 @@ class ProfRecord(ctypes.Structure):
 KERNEL_KINDS = {1: "bias_act", 2: "upfirdn2d", 3: "conv_igemm", 4: "conv_wgrad", 5: "wgrad_reduce", 6: "scale_nc", 7: "dot_hw", 9: "sn_power", 10: "attention",
                 11: "grid_sample", 12: "filter1d", 13: "color", 14: "weight_prep", 15: "torgb", 16: "fromrgb", 17: "grouped_gemm", 18: "ppl",
                 19: "projector", 20: "image_export", 21: "resample", 22: "pr", 23: "grad_finish", 24: "resident", 25: "diffaug", 26: "nn_u8", 27: "swd", 28: "spectrum",
-                29: "msssim", 30: "directions", 31: "kmeans_u8"}
+                29: "msssim", 30: "directions", 31: "kmeans_u8", 32: "walk"}
+WALK_VARIANTS = {0: "blend", 1: "sqdiff", 2: "merge"}       # dims[0] of a "walk" launch record (blend: T, L, D, layers given; the others: N, F, splits)
 KMEANS_VARIANTS = {0: "accumulate", 1: "finish"}            # dims[0] of a "kmeans_u8" launch record (then N, F clipped to int, K, row chunks, lanes per row)
 DIRECTIONS_VARIANTS = {0: "mean", 1: "gram", 2: "merge", 3: "edit"}     # dims[0] of a "directions" launch record
 MSSSIM_VARIANTS = {0: "level", 1: "down", 2: "merge"}      # dims[0] of an "msssim" launch record (then BC, S)
@@ -252,6 +253,10 @@ SYMBOLS = [
     ("sbg_directions_edit", _c.c_int, [_c.c_void_p] * 6 + [_c.c_int] * 5 + [_c.c_void_p]),
     ("sbg_kmeans_u8_update_workspace", _c.c_int64, [_c.c_int64, _c.c_int64, _c.c_int]),
     ("sbg_kmeans_u8_update", _c.c_int, [_c.c_void_p] * 7 + [_c.c_int64, _c.c_int64, _c.c_int, _c.c_void_p]),
+    ("sbg_walk_blend", _c.c_int, [_c.c_void_p] * 6 + [_c.c_int] * 4 + [_c.c_void_p]),
+    ("sbg_walk_sqdiff_splits", _c.c_int64, [_c.c_int64, _c.c_int64]),
+    ("sbg_walk_sqdiff_workspace", _c.c_int64, [_c.c_int64, _c.c_int64]),
+    ("sbg_walk_sqdiff", _c.c_int, [_c.c_void_p] * 4 + [_c.c_int64, _c.c_int64, _c.c_void_p]),
     ("sbg_prof_enable", _c.c_int, [_c.c_int]),
     ("sbg_prof_fetch", _c.c_int, [_c.POINTER(ProfRecord), _c.c_int]),
 ]

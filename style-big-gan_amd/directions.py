@@ -40,19 +40,11 @@ import numpy as np
 import torch
 
 from .tool_support import (add_device_option, add_sampling_options, add_snapshot_option, class_label, config_overrides, device_of, load_generator, num_range,
-                           require_file, save_png, seed_latents, tool_device)
+                           parse_layers, require_file, save_png, seed_latents, tool_device)
 from .torch_utils.ops import directions as ops, image_export
 
 METHODS = ('pca', 'sefa')
 DEFAULT_RANGE = dict(pca=2.0, sefa=3.0)
-
-
-def parse_layers(text, num_ws):
-    """'all' | 'a-b' | 'a,b,c' -> sorted ws indices, all below `num_ws`"""
-    layers = list(range(num_ws)) if text in (None, 'all') else sorted(set(num_range(text)))
-    if not layers or layers[-1] >= num_ws:
-        raise ValueError(f'--layers={text}: the generator has the ws indices 0 to {num_ws - 1}')
-    return layers
 
 
 def sigma_table(extent, steps):

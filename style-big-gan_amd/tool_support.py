@@ -1,7 +1,9 @@
-"""What the ten snapshot tools (generate, style_mixing, projector, calc_metrics, nearest_neighbors, avg_spectra, diversity, realism, directions, modes) share,
+"""What the eleven snapshot tools (generate, style_mixing, projector, calc_metrics, nearest_neighbors, avg_spectra, diversity, realism, directions, modes,
+interpolate) share,
 each piece once: a generator built from the run's config and a ``network-snapshot-*.pt`` of this build (written by ``BaseTrainer.save_snapshot``), the
 ``key=value`` config overrides ``starter`` takes, the options several tools declare alike, the device and the data set of a run, the class label, the
-seeded latents, the bytes of generated images, the box reduction behind ``--res`` and the ``vgg16.pt`` features of a data set.  What a tool validates
+seeded latents, the ws indices of ``--layers``, the bytes of generated images, the box reduction behind ``--res``, the ``vgg16.pt`` features of a data set and
+the two image writers (one frame, many frames).  What a tool validates
 and the options whose help differs per tool stay in the tool."""
 import contextlib
 import os
@@ -21,6 +23,14 @@ def num_range(s):
     """a comma separated list of numbers 'a,b,c' or a range 'a-c' -> list of ints (the reference's option type, generate.py :25-33)"""
     m = re.match(r'^(\d+)-(\d+)$', s)
     return list(range(int(m.group(1)), int(m.group(2)) + 1)) if m else [int(x) for x in s.split(',')]
+
+
+def parse_layers(text, num_ws):
+    """'all' | 'a-b' | 'a,b,c' -> sorted ws indices, all below `num_ws`"""
+    layers = list(range(num_ws)) if text in (None, 'all') else sorted(set(num_range(text)))
+    if not layers or layers[-1] >= num_ws:
+        raise ValueError(f'--layers={text}: the generator has the ws indices 0 to {num_ws - 1}')
+    return layers
 
 
 def add_snapshot_option(ap, required=True, help=SNAPSHOT_HELP):
@@ -232,3 +242,23 @@ def save_png(img, path):
     img = np.ascontiguousarray(img)
     assert img.ndim == 3 and img.shape[2] in [1, 3]
     (PIL.Image.fromarray(img[:, :, 0], 'L') if img.shape[2] == 1 else PIL.Image.fromarray(img, 'RGB')).save(path)
+
+
+ANIMATION_FORMATS = {'apng': 'PNG', 'gif': 'GIF', 'webp': 'WEBP'}
+
+
+def save_animation(frames, path, fmt, fps):
+    """uint8 [T, H, W, C] -> an animated PNG ('apng'), GIF ('gif') or lossless WebP ('webp') that plays `fps` frames a second for ever; mode 'L'
+    for one channel, 'RGB' for three.  Pillow gets the frames as a list (from a generator its PNG writer keeps the first frame alone); its writers
+    merge identical consecutive frames into one of a longer duration, and a file whose frames are all equal holds one still image: a reader
+    expands every frame by duration / (1000 / fps) and a still image to the number of frames it expects."""
+    import PIL.Image
+    frames = np.ascontiguousarray(frames)
+    assert frames.ndim == 4 and frames.shape[0] >= 1 and frames.shape[3] in [1, 3] and frames.dtype == np.uint8
+    if fmt not in ANIMATION_FORMATS:
+        raise ValueError(f'--format={fmt}: one of {", ".join(ANIMATION_FORMATS)}')
+    if not float(fps) > 0:
+        raise ValueError(f'--fps={fps}: must be positive')
+    images = [PIL.Image.fromarray(f[:, :, 0], 'L') if f.shape[2] == 1 else PIL.Image.fromarray(f, 'RGB') for f in frames]
+    more = dict(lossless=True) if fmt == 'webp' else {}
+    images[0].save(path, format=ANIMATION_FORMATS[fmt], save_all=True, append_images=images[1:], duration=1000 / float(fps), loop=0, **more)
