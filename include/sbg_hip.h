@@ -760,6 +760,43 @@ int64_t sbg_walk_sqdiff_workspace(int64_t N, int64_t F);
 int sbg_walk_sqdiff(const uint8_t* a, const uint8_t* b, int64_t* out, void* workspace, int64_t N, int64_t F, sbg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Moments of uint8 images (variation.py: per-pixel variance by generator input, figures 4 and 5 of the StyleGAN paper; the reference has no
+ * counterpart; csrc/moments_u8.hip).  torch_utils/ops/moments_u8.py evaluates all three for CPU tensors (numpy int64) to
+ * the same bits.  Integers only; no atomics: the results depend on the inputs alone.  A refused call (bad sizes, a null or misaligned pointer)
+ * launches nothing, returns SBG_ERR_INVALID and names the shape in sbg_last_error().
+ *   sbg_moments_accumulate: images uint8 [G, N, F]; image (g, n) starts at images + g * group_stride + n * row_stride bytes, any base alignment
+ *                     (a slice of a larger batch), row_stride >= F, group_stride >= (N - 1) row_stride + F (ignored when G = 1).  sum, sumsq int64
+ *                     [G, F] dense, 8-byte aligned, RUNNING: sum[g, f] += sum_n images[g, n, f], sumsq[g, f] += sum_n images[g, n, f]^2.
+ *                     1 <= G <= 65535, 1 <= F <= 2^26, 0 <= N <= sbg_moments_accumulate_max_n() = 32768 per call (N = 0 launches nothing): a
+ *                     work-item adds the bytes of its columns into uint32 partials, which cannot overflow while 255^2 N < 2^32 (N <= 66051); 32768
+ *                     leaves a factor of two.  The caller splits a larger N into several calls.
+ *                     THE SPLIT RULE.  The kernel is a byte stream and G * ceil(F / 4096) workgroups (256 work-items of 16 bytes) do not fill the
+ *                     chip at low resolution, so N is split over workgroups: with tiles = ceil(F / 4096),
+ *                         want = max(1, min(ceil(1024 / (G tiles)), ceil(N / 16))),  rows = ceil(N / want),  splits = ceil(N / rows)
+ *                     = sbg_moments_accumulate_splits(G, N, F) (0 for N = 0, -1 for unsupported sizes).  With one split the kernel adds into sum
+ *                     and sumsq itself; otherwise it stores int64 partials [splits, G, 2, F] to sbg_moments_accumulate_workspace(G, N, F) =
+ *                     16 splits G F bytes (0 with one split, -1 unsupported; 8-byte aligned) and a second launch adds them in split order.  The
+ *                     load width W is 16 bytes when row_stride (and, for G > 1, group_stride) is a multiple of 16, 4 when a multiple of 4, else 1.
+ *   sbg_moments_numerator:  sum, sumsq int64 [G, C, P], the count n -> num int64 [G, P], num[g, p] = sum_c (n sumsq[g, c, p] - sum[g, c, p]^2):
+ *                     exact, never negative for the moments of n bytes; num / (C n (n - 1)) is the channel mean of the unbiased variance.  Every
+ *                     term is at most 65025 n^2, so int64 cannot overflow while n^2 * 65025 * C < 2^63: the largest such n is
+ *                     sbg_moments_numerator_max_n(C) (11 909 805 at C = 1, 6 876 129 at C = 3; -1 for C outside [1, 1024]) and a larger n is
+ *                     refused.  1 <= G <= 65535, 1 <= P <= 2^26, G C P <= 2^40.  One launch.
+ *   sbg_moments_render:     num int64 [G, P], thresholds int64 [255], table uint8 [256, 3] -> heat uint8 [G, 3, P], heat[g, :, p] = table[level]
+ *                     with level = the number of thresholds <= num[g, p] (an integer comparison; ascending thresholds make it a scale), and
+ *                     dominant uint8 [P] = the g of the largest num[g, p], ties to the lower g, 255 where every group is <= 0.  1 <= G <= 255,
+ *                     1 <= P <= 2^26.  One launch. */
+int64_t sbg_moments_accumulate_max_n(void);
+int64_t sbg_moments_accumulate_splits(int64_t G, int64_t N, int64_t F);
+int64_t sbg_moments_accumulate_workspace(int64_t G, int64_t N, int64_t F);
+int sbg_moments_accumulate(const uint8_t* images, int64_t row_stride, int64_t group_stride, int64_t* sum, int64_t* sumsq, void* workspace,
+                           int64_t G, int64_t N, int64_t F, sbg_stream_t stream);
+int64_t sbg_moments_numerator_max_n(int64_t C);
+int sbg_moments_numerator(const int64_t* sum, const int64_t* sumsq, int64_t* num, int64_t G, int64_t C, int64_t P, int64_t n, sbg_stream_t stream);
+int sbg_moments_render(const int64_t* num, const int64_t* thresholds, const uint8_t* table, uint8_t* heat, uint8_t* dominant, int64_t G, int64_t P,
+                       sbg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * In-process launch timing (measurement only; bench.py's roofline figures come from here).
  * While enabled, every kernel launch of this library is bracketed by two hipEvents recorded on the launch stream
  * and logged with its algorithmic flops / bytes.  sbg_prof_fetch() synchronises the logged events, writes up to `max`
@@ -790,8 +827,10 @@ enum sbg_kernel_kind {
     SBG_K_DIRECTIONS = 30,      /* dims[0] = variant: 0 mean (N, D, chunks) / 1 gram (N, D, groups) / 2 merge (N, D, chunks or groups: the launch
                                  * it finishes) / 3 edit (S, K, T, L, D); N clipped to INT32_MAX */
     SBG_K_KMEANS_U8 = 31,       /* dims[0] = variant: 0 accumulate / 1 finish; then N, F (both clipped to INT32_MAX), K, row chunks, lanes per row */
-    SBG_K_WALK = 32             /* dims[0] = variant: 0 blend (T, L, D, 1 with a layer mask) / 1 sqdiff (N, F, splits) / 2 merge (N, F, splits: the
+    SBG_K_WALK = 32,            /* dims[0] = variant: 0 blend (T, L, D, 1 with a layer mask) / 1 sqdiff (N, F, splits) / 2 merge (N, F, splits: the
                                  * second launch of a split sqdiff); N, F clipped to INT32_MAX */
+    SBG_K_MOMENTS = 33          /* dims[0] = variant: 0 accumulate (G, N, F, splits, load width W) / 1 merge (G, N, F, splits: the second launch of a
+                                 * split accumulate) / 2 numerator (G, C, P) / 3 render (G, P); F, P clipped to INT32_MAX */
 };
 /* Kernel-variant codes in the records of the streaming kernels (which kernel served the launch):
  *   bias_act     dims[4] = 1 vec8 / 2 scalar,  dims[5] = bias mode (0 none, 1 channel-minor vector, 2 one per 8-vector, 3 generic)

@@ -1,8 +1,9 @@
-"""What the eleven snapshot tools (generate, style_mixing, projector, calc_metrics, nearest_neighbors, avg_spectra, diversity, realism, directions, modes,
-interpolate) share,
+"""What the twelve snapshot tools (the eleven up to the walk tool: generate, style_mixing, projector, calc_metrics, nearest_neighbors, avg_spectra, diversity,
+realism, directions, modes, interpolate; and variation) share,
 each piece once: a generator built from the run's config and a ``network-snapshot-*.pt`` of this build (written by ``BaseTrainer.save_snapshot``), the
 ``key=value`` config overrides ``starter`` takes, the options several tools declare alike, the device and the data set of a run, the class label, the
-seeded latents, the ws indices of ``--layers``, the bytes of generated images, the box reduction behind ``--res``, the ``vgg16.pt`` features of a data set and
+seeded latents, the ws indices of ``--layers``, the noise layers of a synthesis network and the context that hands them noise realisations, the bytes of
+generated images, the box reduction behind ``--res``, the ``vgg16.pt`` features of a data set and
 the two image writers (one frame, many frames).  What a tool validates
 and the options whose help differs per tool stay in the tool."""
 import contextlib
@@ -196,6 +197,44 @@ def class_label(G, class_idx, device):
 def seed_latents(G, seeds):
     """-> float64 [len(seeds), z_dim], every row from a generator of its own seed (the reference's `randn(1, z_dim)` draws the same numbers)"""
     return np.stack([np.random.RandomState(seed).randn(G.z_dim) for seed in seeds])
+
+
+def noise_layers(G):
+    """-> [(layer name, resolution)] of the synthesis layers with `use_noise`, in synthesis order ('b4.conv1', 'b8.conv0', ...); a generator
+    without a synthesis network of such layers (DCGAN, BigGAN) is refused"""
+    synthesis = getattr(G, 'synthesis', None)
+    if synthesis is None or not hasattr(synthesis, 'block_resolutions'):
+        raise ValueError('the generator has no synthesis network with per-layer noise inputs (a mapping/synthesis generator is needed)')
+    found = []
+    for res in synthesis.block_resolutions:
+        block = getattr(synthesis, f'b{res}')
+        for name in ('conv0', 'conv1'):
+            layer = getattr(block, name, None)
+            if layer is not None and getattr(layer, 'use_noise', False):
+                found.append((f'b{res}.{name}', int(layer.resolution)))
+    return found
+
+
+@contextlib.contextmanager
+def noise_inputs(G, inputs):
+    """while the context is open the named noise layers (`noise_layers`) use the given realisation, fp32 [N, 1, res, res], instead of drawing one
+    (noise mode 'random') or reading `noise_const` ('const'); every layer is cleared on exit, an exception included"""
+    known = dict(noise_layers(G))
+    layers = {}
+    for name, noise in inputs.items():
+        if name not in known:
+            raise ValueError(f'noise_inputs: {name} is not a noise layer of the generator (it has {", ".join(known)})')
+        if noise.dtype != torch.float32 or noise.ndim != 4 or tuple(noise.shape[1:]) != (1, known[name], known[name]):
+            raise ValueError(f'noise_inputs: {name} expects fp32 [N, 1, {known[name]}, {known[name]}], got {noise.dtype} {tuple(noise.shape)}')
+        block, layer = name.split('.')
+        layers[name] = getattr(getattr(G.synthesis, block), layer)
+    try:
+        for name, layer in layers.items():
+            layer.noise_input = inputs[name]
+        yield
+    finally:
+        for layer in layers.values():
+            layer.noise_input = None
 
 
 def to_uint8(img):

@@ -328,6 +328,8 @@ class SynthesisLayer(torch.nn.Module):
             self.noise_strength = torch.nn.Parameter(torch.zeros([]))
         self.bias = torch.nn.Parameter(torch.zeros([out_channels]))
 
+    noise_input = None      # fp32 [N, 1, resolution, resolution]: used instead of the drawn ('random') or the stored ('const') noise while it is set
+
     def forward(self, x, w, noise_mode='random', fused_modconv=True, gain=1, x_sole_consumer=False, post_scale=None, styles=None, x_premodulated=False):
         """Extensions for the block that owns the layer:
         `x_sole_consumer`: the caller guarantees that this layer is the only reader of x (a block's conv1 after its conv0), which lets the fused
@@ -340,9 +342,13 @@ class SynthesisLayer(torch.nn.Module):
         if styles is None:
             styles = self.affine(w)
         noise = None
-        if self.use_noise and noise_mode == 'random':
+        given = self.noise_input if self.use_noise and noise_mode != 'none' else None
+        if given is not None:       # a realisation handed to this layer (tool_support.noise_inputs) stands for the drawn and for the constant one
+            misc.assert_shape(given, [x.shape[0], 1, self.resolution, self.resolution])
+            noise = given.to(device=x.device, dtype=torch.float32) * self.noise_strength
+        elif self.use_noise and noise_mode == 'random':
             noise = torch.randn([x.shape[0], 1, self.resolution, self.resolution], device=x.device) * self.noise_strength
-        if self.use_noise and noise_mode == 'const':
+        elif self.use_noise and noise_mode == 'const':
             noise = self.noise_const * self.noise_strength
         clamp = self.conv_clamp * gain if self.conv_clamp is not None else None
         no_grad = not (torch.is_grad_enabled() and (x.requires_grad or styles.requires_grad or self.weight.requires_grad or self.bias.requires_grad))
@@ -569,12 +575,20 @@ class SynthesisNetwork(torch.nn.Module):
             x, img = getattr(self, f'b{res}')(x, img, cur_ws, styles=(bank[res] if bank else None), **block_kwargs)
         if tail > 0:        # the highest-resolution blocks over slices of the batch (pass_plan), their images concatenated
             imgs = []
-            for i in range(0, ws.shape[0], chunk):
-                xc, ic = x.narrow(0, i, chunk), (img.narrow(0, i, chunk) if img is not None else None)
-                for res, cur_ws in zip(self.block_resolutions[head:], per_block[head:]):
-                    st = tuple(None if s is None else s.narrow(0, i, chunk) for s in bank[res]) if bank else None
-                    xc, ic = getattr(self, f'b{res}')(xc, ic, cur_ws.narrow(0, i, chunk), styles=st, **block_kwargs)
-                imgs.append(ic)
+            layers = [getattr(getattr(self, f'b{res}'), name, None) for res in self.block_resolutions[head:] for name in ('conv0', 'conv1')]
+            given = [(layer, layer.noise_input) for layer in layers if layer is not None and layer.noise_input is not None]
+            try:
+                for i in range(0, ws.shape[0], chunk):
+                    for layer, noise in given:      # a layer of a sliced block sees the slice's rows of its noise input
+                        layer.noise_input = noise.narrow(0, i, chunk)
+                    xc, ic = x.narrow(0, i, chunk), (img.narrow(0, i, chunk) if img is not None else None)
+                    for res, cur_ws in zip(self.block_resolutions[head:], per_block[head:]):
+                        st = tuple(None if s is None else s.narrow(0, i, chunk) for s in bank[res]) if bank else None
+                        xc, ic = getattr(self, f'b{res}')(xc, ic, cur_ws.narrow(0, i, chunk), styles=st, **block_kwargs)
+                    imgs.append(ic)
+            finally:
+                for layer, noise in given:
+                    layer.noise_input = noise
             img = misc.cat0(imgs)
         return img
 
