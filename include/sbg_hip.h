@@ -797,6 +797,46 @@ int sbg_moments_render(const int64_t* num, const int64_t* thresholds, const uint
                        sbg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Activation statistics (network_summary.py: the per-layer, per-channel numerics columns of the network summary; the reference has no
+ * counterpart; csrc/act_stats.hip).  torch_utils/ops/act_stats.py evaluates both entry points for CPU tensors in numpy to
+ * the same bits.  No global atomics; no result depends on the launch geometry or on how samples were batched.  A refused call (bad sizes, a null
+ * or misaligned pointer) launches nothing, returns SBG_ERR_INVALID and names the shape in sbg_last_error().
+ *   sbg_act_stats_planes:  x is logically [N, C, P] of `dtype` (SBG_F32 / SBG_F16 / SBG_BF16); element (n, c, p) sits at x + n sn + c sc + p sp
+ *                     ELEMENTS.  Dense NCHW is (C P, P, 1), channels_last (P C, 1, C), a 2-D [N, F] tensor C = F, P = 1, a batch slice has a
+ *                     larger sn.  The planes must not overlap (the caller's check).  x need only be aligned to its element: a misaligned base or
+ *                     stride takes a narrower load, never an error.  1 <= P < 2^31 - 4096, N C < 2^31 - 256, strides in [1, 2^40] wherever the
+ *                     size is above 1.  One launch.  Every element is converted exactly to fp32; one record per plane (n, c):
+ *                     counts int64 [N, C, SBG_ACT_STATS_COUNTS = 70], 8-byte aligned, dense:
+ *                       [0] n = P     [1] n_zero (x == 0, either sign)     [2] n_nan     [3] n_posinf     [4] n_neginf
+ *                       [5] n_peak: the number of finite elements with |x| == peak, peak the largest finite |x| of the plane; 0 when the plane
+ *                           has no finite element.  (A clamped layer shows as many elements on one peak, whatever clamp and gain produced it.)
+ *                       [6 .. 69] hist[64]: the exponent histogram of the finite non-zero elements: with e = floor(log2 |x|) of the fp32 value,
+ *                           bin = min(max(e, -32), 31) + 32; fp32 subnormals land in bin 0.
+ *                     values float64 [N, C, SBG_ACT_STATS_VALUES = 4], 8-byte aligned, dense:
+ *                       [0] sum, [1] sumsq over the finite elements: (double)x and (double)x * (double)x are both exact and are added IN THE
+ *                           PROJECT'S FIXED ORDER over the logical pixel index p, in every layout: lane t of 256 adds p = t, t + 256, ... in
+ *                           ascending order from +0.0, then block_sum<256> of csrc/reduce.h (_exact_common.strided_sum_np of the float64 plane
+ *                           with the non-finite elements replaced by 0).
+ *                       [2] min, [3] max over the finite elements, as the float64 of the fp32 value, a zero of either sign counting as +0.0
+ *                           (so the two do not depend on which zero is met first); +inf and -inf when the plane has no finite element.
+ *                     sbg_act_stats_path (host only) names the mapping a call takes -- 1 staged (P > 64, sp == 1: 16-byte loads along P through
+ *                     LDS), 2 cminor (P > 64, sc == 1, C a multiple of V = 16 / element bytes, x 16-byte aligned, sn and sp multiples of V: a
+ *                     16-byte vector of V channels per work-item), 3 group (P <= 64: several planes per workgroup), 4 strided (the rest: scalar
+ *                     loads) -- or -1 for a shape sbg_act_stats_planes refuses.  The bits are the same on every mapping.
+ *   sbg_act_stats_fold:    records counts [N, C, 70] / values [N, C, 4] are added into the RUNNING records run_counts [C, 70] / run_values [C, 4]
+ *                     (dense, 8-byte aligned; an empty running record is all zeros with min = +inf and max = -inf), one work-item per
+ *                     (c, field), n ascending: counts add; sum and sumsq add in sample order, so the result does not depend on how the samples
+ *                     were batched; min and max combine; n_peak follows the larger peak max(|min|, |max|) and adds on equal peaks.  N = 0
+ *                     launches nothing.  One launch. */
+#define SBG_ACT_STATS_COUNTS 70
+#define SBG_ACT_STATS_VALUES 4
+int sbg_act_stats_path(const void* x, int dtype, int64_t N, int64_t C, int64_t P, int64_t sn, int64_t sc, int64_t sp);
+int sbg_act_stats_planes(const void* x, int dtype, int64_t N, int64_t C, int64_t P, int64_t sn, int64_t sc, int64_t sp, int64_t* counts,
+                         double* values, sbg_stream_t stream);
+int sbg_act_stats_fold(const int64_t* counts, const double* values, int64_t* run_counts, double* run_values, int64_t N, int64_t C,
+                       sbg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * In-process launch timing (measurement only; bench.py's roofline figures come from here).
  * While enabled, every kernel launch of this library is bracketed by two hipEvents recorded on the launch stream
  * and logged with its algorithmic flops / bytes.  sbg_prof_fetch() synchronises the logged events, writes up to `max`
@@ -829,8 +869,10 @@ enum sbg_kernel_kind {
     SBG_K_KMEANS_U8 = 31,       /* dims[0] = variant: 0 accumulate / 1 finish; then N, F (both clipped to INT32_MAX), K, row chunks, lanes per row */
     SBG_K_WALK = 32,            /* dims[0] = variant: 0 blend (T, L, D, 1 with a layer mask) / 1 sqdiff (N, F, splits) / 2 merge (N, F, splits: the
                                  * second launch of a split sqdiff); N, F clipped to INT32_MAX */
-    SBG_K_MOMENTS = 33          /* dims[0] = variant: 0 accumulate (G, N, F, splits, load width W) / 1 merge (G, N, F, splits: the second launch of a
+    SBG_K_MOMENTS = 33,         /* dims[0] = variant: 0 accumulate (G, N, F, splits, load width W) / 1 merge (G, N, F, splits: the second launch of a
                                  * split accumulate) / 2 numerator (G, C, P) / 3 render (G, P); F, P clipped to INT32_MAX */
+    SBG_K_ACT_STATS = 34        /* dims[0] = variant: 0 planes (N, C, P, mapping 1 staged / 2 cminor / 3 group / 4 strided, dtype) / 1 fold (N, C);
+                                 * N, C, P clipped to INT32_MAX */
 };
 /* Kernel-variant codes in the records of the streaming kernels (which kernel served the launch):
  *   bias_act     dims[4] = 1 vec8 / 2 scalar,  dims[5] = bias mode (0 none, 1 channel-minor vector, 2 one per 8-vector, 3 generic)

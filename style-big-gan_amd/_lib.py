@@ -112,7 +112,9 @@ class ProfRecord(ctypes.Structure):
 KERNEL_KINDS = {1: "bias_act", 2: "upfirdn2d", 3: "conv_igemm", 4: "conv_wgrad", 5: "wgrad_reduce", 6: "scale_nc", 7: "dot_hw", 9: "sn_power", 10: "attention",
                 11: "grid_sample", 12: "filter1d", 13: "color", 14: "weight_prep", 15: "torgb", 16: "fromrgb", 17: "grouped_gemm", 18: "ppl",
                 19: "projector", 20: "image_export", 21: "resample", 22: "pr", 23: "grad_finish", 24: "resident", 25: "diffaug", 26: "nn_u8", 27: "swd", 28: "spectrum",
-                29: "msssim", 30: "directions", 31: "kmeans_u8", 32: "walk", 33: "moments"}
+                29: "msssim", 30: "directions", 31: "kmeans_u8", 32: "walk", 33: "moments", 34: "act_stats"}
+ACT_STATS_VARIANTS = {0: "planes", 1: "fold"}               # dims[0] of an "act_stats" launch record (planes: N, C, P, mapping, dtype; fold: N, C)
+ACT_STATS_PATHS = {1: "staged", 2: "cminor", 3: "group", 4: "strided"}     # dims[4] of a planes record, and sbg_act_stats_path
 MOMENTS_VARIANTS = {0: "accumulate", 1: "merge", 2: "numerator", 3: "render"}   # dims[0] of a "moments" launch record (accumulate: G, N, F, splits, W)
 WALK_VARIANTS = {0: "blend", 1: "sqdiff", 2: "merge"}       # dims[0] of a "walk" launch record (blend: T, L, D, layers given; the others: N, F, splits)
 KMEANS_VARIANTS = {0: "accumulate", 1: "finish"}            # dims[0] of a "kmeans_u8" launch record (then N, F clipped to int, K, row chunks, lanes per row)
@@ -265,6 +267,9 @@ SYMBOLS = [
     ("sbg_moments_numerator_max_n", _c.c_int64, [_c.c_int64]),
     ("sbg_moments_numerator", _c.c_int, [_c.c_void_p] * 3 + [_c.c_int64] * 4 + [_c.c_void_p]),
     ("sbg_moments_render", _c.c_int, [_c.c_void_p] * 5 + [_c.c_int64] * 2 + [_c.c_void_p]),
+    ("sbg_act_stats_path", _c.c_int, [_c.c_void_p, _c.c_int] + [_c.c_int64] * 6),
+    ("sbg_act_stats_planes", _c.c_int, [_c.c_void_p, _c.c_int] + [_c.c_int64] * 6 + [_c.c_void_p] * 3),
+    ("sbg_act_stats_fold", _c.c_int, [_c.c_void_p] * 4 + [_c.c_int64] * 2 + [_c.c_void_p]),
     ("sbg_prof_enable", _c.c_int, [_c.c_int]),
     ("sbg_prof_fetch", _c.c_int, [_c.POINTER(ProfRecord), _c.c_int]),
 ]

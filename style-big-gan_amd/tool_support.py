@@ -1,6 +1,7 @@
-"""What the twelve snapshot tools (the eleven up to the walk tool: generate, style_mixing, projector, calc_metrics, nearest_neighbors, avg_spectra, diversity,
-realism, directions, modes, interpolate; and variation) share,
+"""What the thirteen snapshot tools (the eleven up to the walk tool: generate, style_mixing, projector, calc_metrics, nearest_neighbors, avg_spectra, diversity,
+realism, directions, modes, interpolate; then variation and network_summary) share,
 each piece once: a generator built from the run's config and a ``network-snapshot-*.pt`` of this build (written by ``BaseTrainer.save_snapshot``), the
+discriminator of the same file (network_summary is the one tool that loads it), the
 ``key=value`` config overrides ``starter`` takes, the options several tools declare alike, the device and the data set of a run, the class label, the
 seeded latents, the ws indices of ``--layers``, the noise layers of a synthesis network and the context that hands them noise realisations, the bytes of
 generated images, the box reduction behind ``--res``, the ``vgg16.pt`` features of a data set and
@@ -90,12 +91,21 @@ def generator_common_kwargs(state):
                 img_channels=int(torgb.shape[0]) if torgb is not None else 3)
 
 
+def dcgan_common_kwargs(state):
+    """the same three numbers for the state dict of a DCGAN generator (`main.*` layers: a first transposed convolution [z_dim, 1024, M, M],
+    four stride-2 ones, the last to the image channels): no labels, resolution 16 M"""
+    first = state['main.0.weight']
+    last = [v for k, v in state.items() if re.match(r'main\.\d+\.weight$', k) and v.ndim == 4][-1]
+    return dict(c_dim=0, img_resolution=16 * int(first.shape[2]), img_channels=int(last.shape[1]))
+
+
 def build_generator(config, state, device):
     """G through the `generators` registry with the config's gens_args, weights from `state` (strict)"""
     from .train_parts.generators import generators
     from .train_parts.trainers import BaseTrainer
     name = config.gen.generator
-    kw = BaseTrainer._model_kwargs(config.gens_args[name], generator_common_kwargs(state))
+    dcgan = 'main.0.weight' in state and not any(k.startswith('synthesis.') for k in state)
+    kw = BaseTrainer._model_kwargs(config.gens_args[name], dcgan_common_kwargs(state) if dcgan else generator_common_kwargs(state))
     G = generators[name](**kw)
     G.load_state_dict(state, strict=True)
     return G.eval().requires_grad_(False).to(device)
@@ -115,6 +125,32 @@ def load_generator(config, snapshot, device, announce=True):
     if announce:
         print(f'Loading networks from "{snapshot}"...')
     return build_generator(config, snapshot_generator_state(snapshot), device)
+
+
+def snapshot_discriminator_state(path):
+    """D of a network-snapshot-*.pt; a snapshot written without it (a tool's own, or one stripped for release) is refused by name"""
+    snap = torch.load(path, map_location='cpu', weights_only=True)
+    if snap.get('D') is None:
+        raise RuntimeError(f'{path} holds no discriminator (no "D" entry; it holds {", ".join(sorted(snap)) or "nothing"}): '
+                           'only a snapshot written by a training run can be summarised with --networks=D')
+    return snap['D']
+
+
+def build_discriminator(config, state, G, device):
+    """D through the `discriminators` registry with the config's discs_args; c_dim, img_resolution and img_channels are the generator's;
+    weights from `state` (strict); eval mode, no gradients"""
+    from .train_parts.discriminators import discriminators
+    from .train_parts.trainers import BaseTrainer
+    name = config.gen.discriminator
+    common = dict(c_dim=int(getattr(G, 'c_dim', 0) or 0), img_resolution=int(G.img_resolution), img_channels=int(getattr(G, 'img_channels', 3)))
+    D = discriminators[name](**BaseTrainer._model_kwargs(config.discs_args[name], common))
+    D.load_state_dict(state, strict=True)
+    return D.eval().requires_grad_(False).to(device)
+
+
+def load_discriminator(config, snapshot, G, device):
+    """D of the snapshot file on `device`, shaped after `G`; `build_discriminator` is looked up when called, so a stand-in set on this module is used"""
+    return build_discriminator(config, snapshot_discriminator_state(snapshot), G, device)
 
 
 def dataset_kwargs_for(config, G, data=None, mirror=None):

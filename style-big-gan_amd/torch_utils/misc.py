@@ -2,8 +2,9 @@
 
 Counterparts of the functions the hot path uses from ``stylegan2ada/torch_utils/misc.py``: ``assert_shape`` (:80),
 ``profiled_function`` (:98), ``InfiniteSampler`` (:109), ``params_and_buffers`` / ``copy_params_and_buffers``
-(:145-163), ``ddp_sync`` (:167) and ``check_ddp_consistency`` (:179).  ``ddp_sync`` understands both
-torch's DistributedDataParallel and this package's ``parallel.GradReducer`` wrapper.
+(:145-163), ``ddp_sync`` (:167), ``check_ddp_consistency`` (:179) and ``print_module_summary`` (:193).  ``ddp_sync`` understands both
+torch's DistributedDataParallel and this package's ``parallel.GradReducer`` wrapper.  ``module_summary`` returns the entries the summary
+table is printed from (network_summary.py adds its numerics columns to them).
 """
 import contextlib
 import re
@@ -129,3 +130,108 @@ def cat0(tensors):
         return torch.cat(tensors)
     return _Cat0.apply(*tensors)
 
+
+
+class SummaryEntry:
+    """one row group of the module summary: a module that ran, its name in the summarised module ('<top-level>' for the module itself), the
+    element counts of the parameters and buffers no earlier entry owned, and the tensors it returned (`outputs`; `new_outputs` are those no
+    earlier entry returned)"""
+
+    def __init__(self, module, name, outputs):
+        self.module, self.name, self.outputs = module, name, outputs
+        self.params = self.buffers = 0
+        self.new_outputs = []
+
+    @property
+    def redundant(self):
+        return not (self.params or self.buffers or self.new_outputs)
+
+    def labels(self):
+        """the row names: the entry's name, with ':0', ':1', ... when it returned several tensors"""
+        return [self.name] if len(self.outputs) < 2 else [f'{self.name}:{i}' for i in range(len(self.outputs))]
+
+
+def module_summary(module, inputs, max_nesting=3, skip_redundant=True, visit=None):
+    """Run `module(*inputs)` once with hooks on every submodule -> (entries, outputs): a SummaryEntry for every module call nested at most
+    `max_nesting` deep, in the order the calls RETURNED (children before their parent, the module itself last).  A parameter, buffer or
+    output tensor is counted by the first entry that holds it, so a shared parameter is counted once and the totals are those of the module.
+    With `skip_redundant`, entries that own nothing new (no parameter, no buffer, no output that was not seen before) are dropped.  The
+    forward draws from the random generators if the module does: callers that train afterwards must not call this first.
+    `visit(index, entry)` is called from the module's forward hook the moment a call returns -- before a later in-place layer can change the
+    tensor -- with the entry's index among ALL entries (those `skip_redundant` drops included; two forwards of one control flow number
+    their calls alike)."""
+    if not isinstance(module, torch.nn.Module) or isinstance(module, torch.jit.ScriptModule):
+        raise TypeError('module_summary: expects an eager torch.nn.Module')
+    if not isinstance(inputs, (tuple, list)):
+        raise TypeError('module_summary: inputs must be a tuple or list of the positional arguments')
+    names = {m: name for name, m in module.named_modules()}
+    depth = 0
+    entries = []
+
+    def entering(_module, _args):
+        nonlocal depth
+        depth += 1
+
+    def leaving(mod, _args, result):
+        nonlocal depth
+        depth -= 1
+        if depth <= max_nesting:
+            results = result if isinstance(result, (tuple, list)) else [result]
+            entries.append(SummaryEntry(mod, '<top-level>' if mod is module else names[mod], [t for t in results if isinstance(t, torch.Tensor)]))
+            if visit is not None:
+                visit(len(entries) - 1, entries[-1])
+
+    handles = []
+    for m in module.modules():
+        handles += [m.register_forward_pre_hook(entering), m.register_forward_hook(leaving)]
+    try:
+        outputs = module(*inputs)
+    finally:
+        for h in handles:
+            h.remove()
+
+    seen = set()
+    for e in entries:
+        for attr, tensors in (('params', e.module.parameters()), ('buffers', e.module.buffers())):
+            fresh = [t for t in tensors if id(t) not in seen]
+            seen.update(id(t) for t in fresh)
+            setattr(e, attr, sum(t.numel() for t in fresh))
+        e.new_outputs = [t for t in e.outputs if id(t) not in seen]
+        seen.update(id(t) for t in e.new_outputs)
+    if skip_redundant:
+        entries = [e for e in entries if not e.redundant]
+    return entries, outputs
+
+
+def summary_rows(module, entries):
+    """-> the table's cells: header, rule, one row per output of every entry (an entry without a tensor output gets one row of dashes), rule,
+    totals.  Every row of an entry shows the SHAPE OF THE ENTRY'S FIRST OUTPUT, as the reference's table does (its :239 reads outputs[0]
+    for every row); the dtype is each output's own.  network_summary.py writes the true shapes to summary.json."""
+    header = [type(module).__name__, 'Parameters', 'Buffers', 'Output shape', 'Datatype']
+    rows = [header, ['---'] * len(header)]
+    for e in entries:
+        first = [str(e.params) if e.params else '-', str(e.buffers) if e.buffers else '-']
+        if not e.outputs:
+            rows.append([e.name] + first + ['-', '-'])
+        for i, (label, t) in enumerate(zip(e.labels(), e.outputs)):
+            rows.append([label] + (first if i == 0 else ['-', '-']) + [str(list(e.outputs[0].shape)), str(t.dtype).split('.')[-1]])
+    rows.append(['---'] * len(header))
+    rows.append(['Total', str(sum(e.params for e in entries)), str(sum(e.buffers for e in entries)), '-', '-'])
+    return rows
+
+
+def format_table(rows):
+    """cells -> lines: two-space gaps, every cell padded to its column's width (trailing spaces included)"""
+    widths = [max(len(row[i]) for row in rows) for i in range(len(rows[0]))]
+    return ['  '.join(cell.ljust(width) for cell, width in zip(row, widths)) for row in rows]
+
+
+def print_module_summary(module, inputs, max_nesting=3, skip_redundant=True):
+    """Print the per-layer table of the reference (torch_utils/misc.py :193: class name, Parameters, Buffers, Output shape, Datatype; a blank
+    line before and after) for one forward of `module(*inputs)` and return the module's outputs."""
+    entries, outputs = module_summary(module, inputs, max_nesting=max_nesting, skip_redundant=skip_redundant)
+    print()
+    for line in format_table(summary_rows(module, entries)):
+        print(line)
+    print()
+    return outputs
