@@ -837,6 +837,39 @@ int sbg_act_stats_fold(const int64_t* counts, const double* values, int64_t* run
                        sbg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Per-parameter gradient and update health of the run log (layers.jsonl; the reference has no counterpart; csrc/layer_health.hip, DESIGN.md
+ * section 30).  torch_utils/ops/layer_health.py builds the tables and restates the three entry points in numpy to the same bits.  Nothing
+ * but `out` / `running` is written; no atomics; every order of additions is a function of the segment sizes alone.
+ * A parameter is a SEGMENT of n fp32 elements, 4-byte aligned, cut into ceil(n / SBG_LAYER_HEALTH_CHUNK) chunks counted from its own first
+ * element.  All tables are dense device memory built by the caller, and the kernels trust them:
+ *   wg        int32 [records, 2]: workgroup b reads chunk wg[b][1] of segment wg[b][0]; segment-major, chunks ascending, so the records of
+ *             segment p are rec_start[p] .. rec_start[p + 1)
+ *   rec_start int64 [P + 1]: the running sum of the chunk counts
+ *   total_n   the sum of the sizes (launch log and sanity only)
+ *   sbg_layer_health_grads:    segs int64 [P, 2] = {address of the first element, n}.  Per element, with the scale s, the definition of
+ *                     sbg_grad_finish_sweep without the store: y = x * s (skipped when s == 1.0f); z = isnan(y) ? +0 : y == +inf ? 1e5f :
+ *                     y == -inf ? -1e5f : y.  out[b] = float64 [count of y not finite, sum (double)z * (double)z, max |z|] of chunk b.
+ *   sbg_layer_health_updates:  segs int64 [P, 4] = {address of w, of exp_avg, of exp_avg_sq, n}: three fp32 arrays read in memory order.
+ *                     Per element in float64: d = lr * (m / bc1) / (sqrt(v / bc2) + eps), IEEE division and square root, every operation
+ *                     rounded once.  out[b] = float64 [sum w * w, max |w|, sum d * d] of chunk b.  0 < bc1, bc2 <= 1, eps >= 0.
+ *   Inside a chunk, vector v holds the elements 4 v .. 4 v + 3; lane t of 256 adds the elements of its vectors t, t + 256, t + 512, t + 768 in
+ *   ascending order from +0.0; the lanes are added as in csrc/reduce.h.
+ *   sbg_layer_health_fold:     one workgroup per parameter adds its records (lane t the records t, t + 256, ... of the parameter in ascending
+ *                     order, the lanes as in csrc/reduce.h) into running float64 [P, SBG_LAYER_HEALTH_FIELDS]:
+ *                       [0] steps  [1] steps_with_nonfinite  [2] nonfinite  [3] grad_sumsq  [4] grad_absmax  [5] weight_sumsq  [6] weight_absmax
+ *                       [7] update_sumsq
+ *                     mode 0 (records of _grads):  [0] += 1, [1] += count > 0, [2] += count, [3] += sumsq, [4] = max([4], absmax);
+ *                     mode 1 (records of _updates): [5] = sum w * w, [6] = max |w|, [7] += sum d * d.  A parameter without records (n == 0)
+ *                     contributes zeros.  P == 0 launches nothing. */
+#define SBG_LAYER_HEALTH_CHUNK 4096
+#define SBG_LAYER_HEALTH_FIELDS 8
+int sbg_layer_health_grads(const int64_t* segs, const int32_t* wg, int64_t records, int64_t total_n, float scale, double* out, sbg_stream_t stream);
+int sbg_layer_health_updates(const int64_t* segs, const int32_t* wg, int64_t records, int64_t total_n, double lr, double eps, double bc1, double bc2,
+                             double* out, sbg_stream_t stream);
+int sbg_layer_health_fold(const double* records, const int64_t* rec_start, int64_t P, int64_t nrecords, int mode, double* running,
+                          sbg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * In-process launch timing (measurement only; bench.py's roofline figures come from here).
  * While enabled, every kernel launch of this library is bracketed by two hipEvents recorded on the launch stream
  * and logged with its algorithmic flops / bytes.  sbg_prof_fetch() synchronises the logged events, writes up to `max`
@@ -871,8 +904,10 @@ enum sbg_kernel_kind {
                                  * second launch of a split sqdiff); N, F clipped to INT32_MAX */
     SBG_K_MOMENTS = 33,         /* dims[0] = variant: 0 accumulate (G, N, F, splits, load width W) / 1 merge (G, N, F, splits: the second launch of a
                                  * split accumulate) / 2 numerator (G, C, P) / 3 render (G, P); F, P clipped to INT32_MAX */
-    SBG_K_ACT_STATS = 34        /* dims[0] = variant: 0 planes (N, C, P, mapping 1 staged / 2 cminor / 3 group / 4 strided, dtype) / 1 fold (N, C);
+    SBG_K_ACT_STATS = 34,       /* dims[0] = variant: 0 planes (N, C, P, mapping 1 staged / 2 cminor / 3 group / 4 strided, dtype) / 1 fold (N, C);
                                  * N, C, P clipped to INT32_MAX */
+    SBG_K_LAYER_HEALTH = 35     /* dims[0] = variant: 0 grads (records, n clipped to INT32_MAX, dims[3] = 1 when the scale is applied) /
+                                 * 1 updates (records, n) / 2 fold (P, records, dims[3] = 0 grads / 1 updates) */
 };
 /* Kernel-variant codes in the records of the streaming kernels (which kernel served the launch):
  *   bias_act     dims[4] = 1 vec8 / 2 scalar,  dims[5] = bias mode (0 none, 1 channel-minor vector, 2 one per 8-vector, 3 generic)

@@ -112,7 +112,9 @@ class ProfRecord(ctypes.Structure):
 KERNEL_KINDS = {1: "bias_act", 2: "upfirdn2d", 3: "conv_igemm", 4: "conv_wgrad", 5: "wgrad_reduce", 6: "scale_nc", 7: "dot_hw", 9: "sn_power", 10: "attention",
                 11: "grid_sample", 12: "filter1d", 13: "color", 14: "weight_prep", 15: "torgb", 16: "fromrgb", 17: "grouped_gemm", 18: "ppl",
                 19: "projector", 20: "image_export", 21: "resample", 22: "pr", 23: "grad_finish", 24: "resident", 25: "diffaug", 26: "nn_u8", 27: "swd", 28: "spectrum",
-                29: "msssim", 30: "directions", 31: "kmeans_u8", 32: "walk", 33: "moments", 34: "act_stats"}
+                29: "msssim", 30: "directions", 31: "kmeans_u8", 32: "walk", 33: "moments", 34: "act_stats", 35: "layer_health"}
+LAYER_HEALTH_VARIANTS = {0: "grads", 1: "updates", 2: "fold"}      # dims[0] of a "layer_health" launch record (fold: P, records, dims[3] = 0 grads / 1 updates)
+LAYER_HEALTH_CHUNK, LAYER_HEALTH_FIELDS = 4096, 8           # SBG_LAYER_HEALTH_CHUNK, SBG_LAYER_HEALTH_FIELDS
 ACT_STATS_VARIANTS = {0: "planes", 1: "fold"}               # dims[0] of an "act_stats" launch record (planes: N, C, P, mapping, dtype; fold: N, C)
 ACT_STATS_PATHS = {1: "staged", 2: "cminor", 3: "group", 4: "strided"}     # dims[4] of a planes record, and sbg_act_stats_path
 MOMENTS_VARIANTS = {0: "accumulate", 1: "merge", 2: "numerator", 3: "render"}   # dims[0] of a "moments" launch record (accumulate: G, N, F, splits, W)
@@ -270,6 +272,9 @@ SYMBOLS = [
     ("sbg_act_stats_path", _c.c_int, [_c.c_void_p, _c.c_int] + [_c.c_int64] * 6),
     ("sbg_act_stats_planes", _c.c_int, [_c.c_void_p, _c.c_int] + [_c.c_int64] * 6 + [_c.c_void_p] * 3),
     ("sbg_act_stats_fold", _c.c_int, [_c.c_void_p] * 4 + [_c.c_int64] * 2 + [_c.c_void_p]),
+    ("sbg_layer_health_grads", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_float, _c.c_void_p, _c.c_void_p]),
+    ("sbg_layer_health_updates", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64] + [_c.c_double] * 4 + [_c.c_void_p, _c.c_void_p]),
+    ("sbg_layer_health_fold", _c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int, _c.c_void_p, _c.c_void_p]),
     ("sbg_prof_enable", _c.c_int, [_c.c_int]),
     ("sbg_prof_fetch", _c.c_int, [_c.POINTER(ProfRecord), _c.c_int]),
 ]

@@ -41,7 +41,7 @@ import time
 import torch
 import torch.distributed as dist
 
-from .torch_utils.ops import grad_finish
+from .torch_utils.ops import grad_finish, layer_health
 
 
 class _Bucket:
@@ -78,6 +78,11 @@ class GradReducer(torch.nn.Module):
         self.last_health = None         # float64 [3] on the buckets' device after a finish() with `health`: [non-finite count, sum of squares, max magnitude]
         self._health_ws = None          # float64 [records of all buckets, 3]: the partial records of the sweeps, merged by one launch
         self._health_rows = None
+        self.layer_health = False       # finish() measures every parameter's gradient before it sanitises the buckets (log.layer_health)
+        self.health_running = None      # float64 [parameters, 8] (layer_health.FIELDS), rows in the order of layer_health.segments(self): the running
+                                        # table the passes fold into; whoever reads the log swaps in a table of its own (one per phase) or zeroes this one
+        self._lh_segments = None
+        self._lh_tables = {}            # None -> the device table over all buckets; bucket index -> (first row, table) for buckets that differ in scale
 
         params = [p for p in module.parameters()]
         if self.world_size > 1 and broadcast:
@@ -205,7 +210,10 @@ class GradReducer(torch.nn.Module):
         exchange that was still in flight here, the same ``nan_to_num`` bit for bit and, from the same read, the records that one merge
         launch adds up to ``last_health`` = float64 [non-finite elements before sanitising, sum of squares after, largest magnitude
         after] over all buckets -- a fresh device tensor, no host read.  CPU buckets fill it with the same formulas in torch.
-        ``nan_to_num=False`` (the caller discards the gradients) only waits and averages and leaves ``last_health`` alone."""
+        ``nan_to_num=False`` (the caller discards the gradients) only waits and averages and leaves ``last_health`` alone.
+
+        With ``layer_health`` on, every parameter's gradient is measured first, after the waits and before anything sanitises the buckets
+        (``_layer_health_pass``); with it off, finish() makes exactly the launches described above."""
         fused = self.health and nan_to_num
         unscaled = set()
         if self.world_size > 1:
@@ -221,6 +229,8 @@ class GradReducer(torch.nn.Module):
                         unscaled.add(id(b))
         for b in self._buckets:
             b.ready.clear()
+        if self.layer_health and nan_to_num and self._buckets:
+            self._layer_health_pass([1.0 / self.world_size if id(b) in unscaled else 1.0 for b in self._buckets])
         if not fused:
             for b in self._buckets:
                 if self.nonfinite is not None:
@@ -245,6 +255,40 @@ class GradReducer(torch.nn.Module):
             self.last_health = torch.stack([parts[:, 0].sum(), parts[:, 1].sum(), parts[:, 2].max()])
         if self.nonfinite is not None:
             self.nonfinite += self.last_health[0].to(self.nonfinite.dtype)
+
+    def layer_health_segments(self):
+        """layer_health.segments(self), made once: the buckets never move"""
+        if self._lh_segments is None:
+            self._lh_segments = layer_health.segments(self)
+        return self._lh_segments
+
+    def _layer_health_pass(self, scales):
+        """Per-parameter gradient health before the buckets are sanitised (csrc/layer_health.hip): a read-only pass with the scale finish() is
+        about to apply, folded into `health_running`.  Device buckets take ONE launch over all buckets and one fold (buckets that differ in
+        scale -- some exchanged by a backward hook and already averaged, some still to be -- take one pair each); CPU buckets go through the
+        same arithmetic in numpy.  The buckets are not written."""
+        segs = self.layer_health_segments()
+        dev = self._buckets[0].flat.device
+        if self.health_running is None:
+            self.health_running = layer_health.new_running(len(segs), dev)
+        if dev.type != "cuda":
+            for bi, b in enumerate(self._buckets):
+                rows = [i for i, s in enumerate(segs) if s.bucket == bi]
+                if rows:
+                    layer_health.grads_cpu([b.flat[segs[i].offset:segs[i].offset + segs[i].n] for i in rows], scales[bi],
+                                           self.health_running[rows[0]:rows[-1] + 1])
+            return
+        if len(set(scales)) == 1:
+            if None not in self._lh_tables:
+                self._lh_tables[None] = layer_health.grad_table(segs, dev, keep=[b.flat for b in self._buckets])
+            layer_health.grads(self._lh_tables[None], scales[0], self.health_running)
+            return
+        for bi, b in enumerate(self._buckets):
+            if bi not in self._lh_tables:
+                rows = [i for i, s in enumerate(segs) if s.bucket == bi]
+                self._lh_tables[bi] = (rows[0], layer_health.grad_table([segs[i] for i in rows], dev, keep=b.flat))
+            row0, table = self._lh_tables[bi]
+            layer_health.grads(table, scales[bi], self.health_running[row0:row0 + table.P])
 
     def exposed_wait_ms(self, reset=True):
         """sum of the stalls recorded in `timing` (ms); the caller synchronises the device first"""

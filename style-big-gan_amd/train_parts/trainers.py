@@ -24,11 +24,12 @@ import torch
 from .. import utils
 from ..parallel import GradReducer
 from ..torch_utils import misc, training_stats
+from ..torch_utils.ops import layer_health
 from ..utils import EasyDict
 from .discriminators import discriminators
 from .generators import generators
 from .losses_base import losses_arch
-from .optimizers import optimizers
+from .optimizers import Adam, optimizers
 
 trainers = utils.ClassRegistry()
 
@@ -152,6 +153,8 @@ class StepEngine:
         self.time_phases = False            # a device-event pair around every executed phase (reference :730, :749); nothing on a CPU device
         self.report_grad_health = False     # Grad/<phase>/{norm, absmax, nonfinite} after every phase's finish(): device scalars, no sync (set_grad_health)
         self._phase_events = {}             # phase name -> (start, end): the pair of the phase's latest execution
+        self.layer_health = False           # per-parameter gradient and update health into running device tables (set_layer_health)
+        self._layer_health, self._layer_health_t = {}, {}      # phase name -> its tables; id(optimizer) -> steps taken, counted on the host
 
         torch.manual_seed(seed * max(world_size, 1) + rank)     # reference :507-508
         self.G = generators[generator](**(gen_kwargs or {})).train().requires_grad_(False).to(self.device)
@@ -300,9 +303,12 @@ class StepEngine:
             with torch.autograd.profiler.record_function(phase.name + '_opt'):
                 st = self.comm_stats.setdefault(phase.name, dict(pairs=[], nonfinite=torch.zeros([], dtype=torch.int64, device=self.device), runs=0)) \
                     if self.comm_stats is not None else None
-                for r in phase.reducers:
+                lh = self._layer_health[phase.name] if self.layer_health else None
+                for i, r in enumerate(phase.reducers):
                     if st is not None and self._count_nonfinite:
                         r.nonfinite = st['nonfinite']
+                    if lh is not None:      # the reducer folds into this phase's rows of the running table
+                        r.health_running = lh.running[lh.row0[i]:lh.row0[i + 1]]
                     r.finish()              # wait for the all-reduce, average, nan_to_num (reference :745-747)
                     if st is not None:
                         st['pairs'].extend(r.timing or []); r.timing = []
@@ -312,6 +318,8 @@ class StepEngine:
                 if self.report_grad_health:
                     self._report_grad_health(phase)
                 phase.opt.step()
+                if self.layer_health:
+                    self._layer_health_update(phase)
             if events is not None:
                 events[1].record(torch.cuda.current_stream(self.device))
                 self._phase_events[phase.name] = events
@@ -346,6 +354,95 @@ class StepEngine:
         self.report_grad_health = bool(on)
         for r in self.dp_modules.values():
             r.health = bool(on)
+
+    def set_layer_health(self, on=True):
+        """log.layer_health: per parameter and phase, the gradient's size and non-finite count (GradReducer.layer_health, measured before
+        nan_to_num erases them) and the size of the optimizer's update against the weight's (torch_utils/ops/layer_health.py), kept in one
+        running float64 table [parameters of the phase, 8] per phase on the device until `layer_health_report` reads it.  The update pass
+        restates Adam's step from the moments and needs this project's `adam` with amsgrad off, no weight decay, one parameter group and a
+        host learning rate; for any other optimizer the update fields stay None (`layer_health_unsupported` names the phases).  The step
+        count t of the bias corrections is kept here, per optimizer, read ONCE from the optimizer's own state['step'] -- now, never in
+        steady state."""
+        self.layer_health = bool(on)
+        self._layer_health = {}
+        self._layer_health_t = {}
+        for r in self.dp_modules.values():
+            r.layer_health = bool(on)
+            r.health_running = None
+        if not on:
+            return
+        for phase in self.phases:
+            if phase.idle:
+                continue
+            names = {id(p): name for name, p in phase.module.named_parameters()}
+            segs = [s for r in phase.reducers for s in r.layer_health_segments()]
+            row0 = [0]
+            for r in phase.reducers:
+                row0.append(row0[-1] + len(r.layer_health_segments()))
+            opt, g = phase.opt, phase.opt.param_groups[0]
+            why = None
+            if type(opt) is not Adam:
+                why = f"optimizer {type(opt).__name__}"
+            elif len(opt.param_groups) != 1 or g.get('amsgrad') or g.get('weight_decay') or g.get('maximize') or isinstance(g['lr'], torch.Tensor):
+                why = "adam with amsgrad, weight decay, maximize, a tensor learning rate or several parameter groups"
+            if id(opt) not in self._layer_health_t:
+                steps = [opt.state[s.param]['step'] for s in segs if 'step' in opt.state.get(s.param, {})]
+                self._layer_health_t[id(opt)] = int(float(steps[0])) if steps else 0
+            self._layer_health[phase.name] = EasyDict(names=[names[id(s.param)] for s in segs], numels=[s.n for s in segs], params=[s.param for s in segs],
+                                                      row0=row0, running=layer_health.new_running(len(segs), self.device), unsupported=why, table=None)
+
+    @property
+    def layer_health_unsupported(self):
+        """{phase name: why its update fields are None}"""
+        return {name: lh.unsupported for name, lh in self._layer_health.items() if lh.unsupported}
+
+    def _layer_health_update(self, phase):
+        """after opt.step(): count the optimizer's step on the host and measure |w| and the update the step just made (see set_layer_health)"""
+        opt, lh = phase.opt, self._layer_health[phase.name]
+        t = self._layer_health_t[id(opt)] = self._layer_health_t[id(opt)] + 1
+        if lh.unsupported:
+            return
+        g = opt.param_groups[0]
+        bc1, bc2 = layer_health.bias_corrections(g['betas'][0], g['betas'][1], t)
+        triples = None
+        if lh.table is None or self.device.type != 'cuda':
+            triples = [(p.detach(), opt.state[p]['exp_avg'], opt.state[p]['exp_avg_sq']) for p in lh.params]
+        if self.device.type != 'cuda':
+            layer_health.updates_cpu(triples, g['lr'], g['eps'], bc1, bc2, lh.running)
+            return
+        if lh.table is None:        # the moments exist from the first step on and stay where they are
+            lh.table = layer_health.update_table(triples)
+        layer_health.updates(lh.table, g['lr'], g['eps'], bc1, bc2, lh.running)
+
+    def layer_health_fetch(self):
+        """start the copy of every phase's running table to pinned host memory and zero the tables, without waiting -> an object for
+        `layer_health_report` (the tick calls the two around its one host synchronisation)"""
+        host, event = {}, None
+        for name, lh in self._layer_health.items():
+            if lh.running.is_cuda:
+                buf = torch.empty(lh.running.shape, dtype=lh.running.dtype, pin_memory=True)
+                buf.copy_(lh.running, non_blocking=True)
+                host[name] = buf
+            else:
+                host[name] = lh.running.clone()
+            lh.running.zero_()
+        if self.device.type == 'cuda':
+            event = torch.cuda.Event()
+            event.record(torch.cuda.current_stream(self.device))
+        return host, event
+
+    def layer_health_report(self, fetched):
+        """-> {phase: {steps, params: {name: numbers (layer_health.derive)}, nonfinite_params: [names]}} from a `layer_health_fetch`"""
+        host, event = fetched
+        if event is not None:
+            event.synchronize()
+        out = {}
+        for name, lh in self._layer_health.items():
+            run = host[name].numpy()
+            rows = layer_health.derive(run, lh.numels, with_updates=not lh.unsupported)
+            out[name] = dict(steps=int(run[:, 0].max()) if len(run) else 0, params=dict(zip(lh.names, rows)),
+                             nonfinite_params=[n for n, d in zip(lh.names, rows) if d['nonfinite'] > 0])
+        return out
 
     def _report_grad_health(self, phase):
         """Grad/<phase>/norm = sqrt of the reducers' sums of squares added up, /absmax, /nonfinite (elements that were not finite BEFORE
@@ -429,6 +526,8 @@ class StepEngine:
                 ph.opt.load_state_dict(state['optimizers'][ph.name[0]])
         self.cur_nimg = int(state['progress']['cur_nimg'])
         self.batch_idx = int(state['progress']['batch_idx'])
+        if self.layer_health:       # the optimizers' moments are new tensors and their step counts have moved: set up again
+            self.set_layer_health(True)
 
     @torch.no_grad()
     def update_ema(self):
@@ -534,7 +633,8 @@ class BaseTrainer:
         self.run_log = False        # decided by setup_logs
         self.cur_tick = 0           # the tick in progress
         self.start_time = None
-        self._log_txt = self._stats_jsonl = None
+        self._log_txt = self._stats_jsonl = self._layers_jsonl = None
+        self.layer_health = False   # log.layer_health: layers.jsonl, one line per tick with every parameter's gradient and update health
 
     # -- argument assembly / validation (reference :155-395) -----------------------------------------------------------
     def setup_arguments(self, config):
@@ -563,6 +663,13 @@ class BaseTrainer:
         if mode not in ("auto", "on", "off"):
             raise ValueError(f"log.run_log={mode}: use auto, on or off")
         self.run_log_mode = mode
+        lh = config.log.get("layer_health", "off")
+        lh = {True: "on", False: "off"}.get(lh, lh) if isinstance(lh, bool) else lh
+        if lh not in ("on", "off"):
+            raise ValueError(f"log.layer_health={lh}: use on or off")
+        if lh == "on" and mode == "off":
+            raise ValueError("log.layer_health=on writes layers.jsonl at the ticks of the run log: it needs log.run_log=on (or auto in a run without an iteration cap)")
+        self.layer_health = lh == "on"
         self.kimg_per_tick = float(config.log.kimg_per_tick)
         self.snap_ticks = int(config.log.snap) if config.log.snap else None        # ticks between image / network snapshots of the run log
         self.snapshot_iterations = None     # iterations between snapshots; None = only on request
@@ -690,6 +797,9 @@ class BaseTrainer:
         self.start_time = time.time()
         self.run_log = self.run_log_mode == "on" or (self.run_log_mode == "auto" and not self.run_capped)
         if not self.run_log:
+            if self.layer_health:
+                raise ValueError("log.layer_health=on writes layers.jsonl at the ticks of the run log, and log.run_log=auto keeps no run log in a run with "
+                                 "an iteration cap: set log.run_log=on")
             return
         if self.kimg_per_tick <= 0:
             raise ValueError("log.kimg_per_tick must be positive")
@@ -700,6 +810,8 @@ class BaseTrainer:
         os.makedirs(self.run_dir, exist_ok=True)
         self._log_txt = open(os.path.join(self.run_dir, "log.txt"), "at")
         self._stats_jsonl = open(os.path.join(self.run_dir, "stats.jsonl"), "at")
+        if self.layer_health:
+            self._layers_jsonl = open(os.path.join(self.run_dir, "layers.jsonl"), "at")
         data = self.config.data
         self.log("", "Training options:", *_option_lines(self.config), "",
                  f"Output directory:   {self.run_dir}",
@@ -734,14 +846,14 @@ class BaseTrainer:
             self._log_txt.flush()
 
     def close_logs(self):
-        for fh in (self._log_txt, self._stats_jsonl):
+        for fh in (self._log_txt, self._stats_jsonl, self._layers_jsonl):
             if fh is not None:
                 fh.close()
-        self._log_txt = self._stats_jsonl = None
+        self._log_txt = self._stats_jsonl = self._layers_jsonl = None
 
     def __getstate__(self):
         state = dict(self.__dict__)     # the trainer crosses to the rank processes before any file is open; never carry a handle
-        state["_log_txt"] = state["_stats_jsonl"] = None
+        state["_log_txt"] = state["_stats_jsonl"] = state["_layers_jsonl"] = None
         return state
 
     def distribute_torch(self, temp_dir):
@@ -802,6 +914,10 @@ class BaseTrainer:
                                  seed=gen.seed, **self.aug)
         self.engine.time_phases = self.run_log
         self.engine.set_grad_health(self.run_log)
+        if self.layer_health:
+            self.engine.set_layer_health(True)
+            self.log("Layer health:       layers.jsonl, one line per tick", *[f"Layer health:       {name}: no update fields ({why})"
+                                                                               for name, why in self.engine.layer_health_unsupported.items()], "")
 
     def setup_augmentations(self):
         self.augment_pipe = self.engine.augment_pipe        # built by StepEngine (it owns the loss object the pipe plugs into)
@@ -980,10 +1096,15 @@ class BaseTrainer:
 
         for name, ms in eng.phase_times().items():
             report0('Timing/' + name, ms)
+        layers = eng.layer_health_fetch() if self.layer_health else None       # copies in flight; the update below is the wait
         self.stats.update()
         if self._stats_jsonl is not None:
             self._stats_jsonl.write(json.dumps(dict(self.stats.as_dict(), timestamp=time.time())) + "\n")
             self._stats_jsonl.flush()
+        if self._layers_jsonl is not None:
+            line = dict(tick=cur_tick, kimg=cur_nimg / 1e3, timestamp=time.time(), phases=eng.layer_health_report(layers))
+            self._layers_jsonl.write(json.dumps(line, allow_nan=False) + "\n")
+            self._layers_jsonl.flush()
 
         self.cur_tick = cur_tick + 1
         self._tick_start_nimg, self._tick_start_time = cur_nimg, time.time()
